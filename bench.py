@@ -14,14 +14,28 @@ architectures (no checkpoints offline) -- throughput is weight independent.  Wit
 stream (the order-dependent integer passes run replicated), rank k owns keyframe k of a round for the encoders, and the round's one
 exchange (all-gather of the owners' descriptors over RCCL) sits INSIDE the step.
 
+A plain run sets up, warms up, times the --steps steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the
+result line.  Everything else it can measure runs only with --full (the --no-* options below switch single legs of --full off); without
+--full those fields of the line are null:
+
+    python bench.py --gpus 1 --steps 24 --warmup 3 --full
+
+--dump-outputs DIR: after the timed steps, what the timed path handed its caller in its last step, as DIR/<name>.npy (float32 / float64):
+the instance query (similarity, class, confidence), the instance descriptor table, the dense per-point class map, the point map with its
+instance ids, and a seeded sample of the SAM2 features of the last keyframe; per-point arrays longer than 2^20 rows are a seeded sample of
+rows (`point_sample_index`).  The inputs are seeded, so two builds run with the same arguments can be compared file by file.
+
 Rank 0 prints ONE JSON line: the driver contract fields plus
+  per_step_ms   step cadence statistics of the timed steps
+and, with --full,
   roofline      dominant kernel = the bf16 MFMA GEMM instantiation with the most time, hipEvents around every launch in a second,
                 profiled pass -- as run on three concurrent streams, and with the streams folded under `isolated`; `traffic` = HBM
                 bytes per launch from the committed PMC reduction profiles/pmc_traffic.json; `frame_frac` = the whole frame's
                 flops / step time / peak; `measured_peaks` = stream copy and 8192^3 GEMM measured in this job
   cpu_baseline  the CPU oracle of the same path: 1 warm-up + median of 3 frames, N = 1 only
   parity        GPU vs oracle on one frame of this workload: max |descriptor error|, per-point instance-id mismatches
-  per_step_ms / sustained   step cadence statistics of the timed steps and a >= 2 s continuation of the same stream
+  sustained     a >= 2 s continuation of the same stream
+  online / shared_crops / projection / dense_merge   the other configurations described at their options
 """
 from __future__ import annotations
 
@@ -48,6 +62,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the bench measures: roofline (profiled passes + measured peaks), sustained, online, "
+                         "shared_crops, projection, dense_merge (N > 1), cpu_baseline + parity (N = 1); the --no-* options switch single legs off")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--vit", default="PE-Core-L14-336", help="ViT card (ovo_amd.encoders.vit.SPECS)")
     ap.add_argument("--sam", default="hiera_b+", help="SAM2 image encoder card, or 'none'")
     ap.add_argument("--map-points", type=int, default=1_000_000)
@@ -88,7 +107,11 @@ def parse():
     ap.add_argument("--no-shared-crops", action="store_true", help="skip the `shared_crops` leg (identical TextRegion crops encoded once; not the headline)")
     ap.add_argument("--no-online", action="store_true", help="skip the `online` leg (the same workload with no encoder look-ahead)")
     ap.add_argument("--sustain-seconds", type=float, default=2.0, help="after the timed steps: keep stepping the same stream for this long (0 = off)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:                                              # a plain run: the headline alone
+        args.no_roofline = args.no_cpu_baseline = args.no_online = args.no_shared_crops = True
+        args.sustain_seconds, args.projection_world, args.dense_merge = 0.0, 0, "none"
+    return args
 
 
 def cpu_frame(pipe_args, frame_np, map_xyz, texts):
@@ -460,6 +483,83 @@ def projection_leg(args, dev, frames, sam):
                     f"map / tracking chains + 1/{N} of the dense rows; all-gather replaced by a local copy; NOT a multi-GPU measurement"}
 
 
+FRAME_POINTS_MAX = 72_000                  # points one 640 x 480 keyframe can append at most (its sub-sampled depth pixels)
+TRAJECTORY_POSES = 24                      # synthetic_frames: the camera loops through syn.pose(t % 24)
+REVISIT_POINTS = 2_000                     # allowance per keyframe after the first loop (see map_growth_budget)
+
+
+def map_growth_budget(keyframes: int) -> int:
+    """Point-map rows to reserve beyond the initial map for `keyframes` keyframes of the synthetic stream.  The dense accumulators
+    (f32[rows, D], 4 KB a row at D = 1024) are sized from it once, so the bound of every keyframe appending FRAME_POINTS_MAX would not
+    fit in HBM at ~1000 steps.  The first loop of the trajectory gets that bound; a keyframe on a later loop revisits a pose whose
+    surfaces are mapped, and adds only what its own noise / invalid pixels leave unexplained.  The CPU oracle (oracle.semantic.PointMap)
+    on the bench's own stream: 284 703 points in the first loop, then 48 k / 16 k / 6 k in the next three loops, 82 658 over the 1176
+    keyframes after the first loop, never more than 10 635 in one keyframe -- REVISIT_POINTS per keyframe is 28x that.  main() checks
+    the bound after the timed steps."""
+    first = min(keyframes, TRAJECTORY_POSES)
+    return (first + 2) * FRAME_POINTS_MAX + (keyframes - first) * REVISIT_POINTS
+
+
+def render_frames(n: int, dev, seed: int, world: int = 1):
+    """synthetic_frames(n, dev, seed=seed) -- the same frames, in order -- rendered by a pool of host threads (the numpy rendering
+    releases the GIL; ~0.07 s of host time per frame on one core, so a 1000-step run would spend over a minute on it alone)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from ovo_amd.pipeline import synthetic_frames
+    cpus = min(len(os.sched_getaffinity(0)), int(os.environ.get("OMP_NUM_THREADS") or 16), 16)
+    workers = max(1, cpus // world)                                # every rank renders the whole stream
+    chunk = max(1, -(-n // (4 * workers)))
+    with ThreadPoolExecutor(workers) as ex:
+        parts = list(ex.map(lambda s: synthetic_frames(min(chunk, n - s), dev, seed=seed, start=s), range(0, n, chunk)))
+    torch.cuda.synchronize(dev)                                    # the uploads ran on the workers' streams
+    return [f for p in parts for f in p]
+
+
+DUMP_POINT_ROWS = 1 << 20                  # --dump-outputs: per-point arrays beyond this many rows are a seeded sample of rows
+DUMP_INSTANCE_ROWS = 4096                  # ... instance arrays beyond this many rows likewise
+DUMP_FEATURE_VALUES = 1 << 16              # ... values per SAM2 feature level (always a seeded sample)
+
+
+def _sample(n: int, cap: int, seed: int):
+    """Sorted indices of a fixed, seeded sample of `cap` out of `n`; None when all `n` fit."""
+    return None if n <= cap else np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+
+
+def dump_outputs(pipe, out, path, rank):
+    """--dump-outputs: what the last timed step handed its caller (`out` of FramePipeline.step_round) and the state it left -- the instance
+    descriptor table and the point map -- as float32 / float64 DIR/<name>.npy.  With N > 1 the dense map is gathered from the ranks' shards
+    into point order (a collective: every rank calls this); rank 0 writes."""
+    n = int(out["n_points"])
+    dense = None
+    if pipe.dense:
+        dense = pipe.gather_dense(n)[2:] if (pipe.world > 1 and pipe.incremental_query) else (out["dense_cls"], out["dense_conf"])
+    if rank != 0:
+        return
+
+    def host(t, idx=None):                                         # (rows of) a device tensor as float32 numpy
+        return (t if idx is None else t[torch.from_numpy(idx).to(t.device)]).float().cpu().numpy()
+    arrays = {"n_points": np.array([n], np.float64), "n_instances": np.array([out["n_instances"]], np.float64)}
+    if "sim" in out:
+        idx = _sample(out["sim"].shape[0], DUMP_INSTANCE_ROWS, 1)
+        if idx is not None:
+            arrays["instance_sample_index"] = idx.astype(np.float64)
+        arrays["instance_sim"], arrays["instance_cls"], arrays["instance_conf"] = host(out["sim"], idx), host(out["cls"], idx), host(out["conf"], idx)
+        arrays["instance_descriptors"] = host(pipe.ovo.get_objs_clips(), idx)
+    idx = _sample(n, DUMP_POINT_ROWS, 2)
+    if idx is not None:
+        arrays["point_sample_index"] = idx.astype(np.float64)
+    arrays["map_xyz"], arrays["map_instance_ids"] = host(pipe.slam.pcd, idx), host(pipe.slam.pcd_obj_ids.reshape(-1), idx)
+    if dense is not None:
+        arrays["dense_cls"], arrays["dense_conf"] = host(dense[0][:n], idx), host(dense[1][:n], idx)
+    for k, t in enumerate(pipe.sam_frame or ()):
+        flat = t.reshape(-1)
+        arrays[f"sam2_level{k}_sample"] = host(flat, _sample(flat.numel(), DUMP_FEATURE_VALUES, 3 + k))
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 class Feed:
     """Rounds of `world` frames in order.  A step also sees the frames that follow it INSIDE the same region (warm-up / timed /
     profiled / sustained), so the encoder look-ahead never does work of a timed frame outside the timed region, nor work of later
@@ -487,7 +587,7 @@ class Feed:
 def main():
     args = parse()
     from ovo_amd import _lib as L, parallel
-    from ovo_amd.pipeline import Frame, FramePipeline, synthetic_frames
+    from ovo_amd.pipeline import Frame, FramePipeline
     rank, local_rank, world = parallel.init_distributed()
     assert torch.cuda.is_available(), "bench.py needs a GPU (ovo_amd has no CPU path)"
     dev_index = parallel.local_device(local_rank)
@@ -511,12 +611,14 @@ def main():
         th = [float(x) for x in args.sam_thresholds.split(",")]
         own = {"own_masks": True, "amg_thresholds": (th[0], th[1]), "nms_score_thr": th[2], "min_own_masks": args.sam_min_own}
     pipe = FramePipeline(dev, vit_card=args.vit, sam_card=sam, n_map=args.map_points, n_text=args.texts, dense=not args.no_dense, sam_full=args.sam_full,
-                         extra_capacity=(base_rounds * world + 2) * 72_000 + sustain_rounds * world * 16_000, seed=0, encoder_batch=args.encoder_batch, **own)
+                         extra_capacity=map_growth_budget(base_rounds * world) + sustain_rounds * world * 16_000, seed=0,
+                         encoder_batch=args.encoder_batch, **own)
+    dense_rows = pipe.slam._cap                                    # the dense accumulators are sized once, here: the map must not outgrow them
     # every rank holds the whole stream: the order-dependent passes run replicated (pipeline.py); rank k owns frame k of a round
     # (the two profiled passes re-use the pixels of the warm-up + timed frames under new keyframe ids, as the sustained leg does: rendering a
     # synthetic frame costs ~0.2 s of host time, and an 8-rank job would render 2 x 24 x 8 more of them on every rank)
     fresh = (args.warmup + args.steps) * world
-    frames = synthetic_frames(fresh, dev, seed=int(os.environ.get("OVO_BENCH_SEED", "0")))
+    frames = render_frames(fresh, dev, seed=int(os.environ.get("OVO_BENCH_SEED", "0")), world=world)
     for i in range(2 * prof_rounds * world):
         f = frames[i % fresh]
         frames.append(Frame(fresh + i, f.rgb[:], f.rgb_lr, f.depth, f.c2w, f.seg_map, f.masks))
@@ -544,6 +646,10 @@ def main():
     xchg_ms = (pipe.exchange_ms - x0) / max(pipe.exchanges - n0, 1)
     xchg_dev_ms = pipe.exchange_device_ms() if world > 1 else None              # taken HERE: the profiled / sustained legs below append their own events
     cadence = sorted(a.elapsed_time(b) for a, b in zip([first] + stamps[:-1], stamps))
+    if pipe.dense and pipe.slam._n > dense_rows:
+        raise RuntimeError(f"the map grew to {pipe.slam._n} points, past the {dense_rows} rows of the dense accumulators: raise map_growth_budget()")
+    if args.dump_outputs:                                          # before any leg below steps the pipeline further
+        dump_outputs(pipe, pipe.last, args.dump_outputs, rank)
 
     roof = None
     if prof_rounds > 0:

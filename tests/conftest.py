@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -29,8 +30,21 @@ def pytest_collection_modifyitems(config, items):
             item.add_marker(skip)
 
 
+class _Parts(dict):
+    """The members of a fixture stored in parts, with the `files` list of np.load's result."""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 def golden(name: str):
-    return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    """tests/golden/<name>.npz; a fixture over the 1 MiB file limit continues in <name>.part1.npz, ... (tools/gen_golden.py: save_parts)."""
+    first = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    parts = sorted(glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".part*.npz")), key=lambda p: int(p[:-len(".npz")].rsplit(".part", 1)[1]))
+    if not parts:
+        return first
+    return _Parts((k, f[k]) for f in [first] + [np.load(p, allow_pickle=False) for p in parts] for k in f.files)
 
 
 def unpack(bits: np.ndarray, w: int) -> np.ndarray:

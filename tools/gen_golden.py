@@ -79,10 +79,35 @@ def t2n(x):
     return np.asarray(x)
 
 
+PART_BYTES = 1000 << 10          # a committed fixture file stays under 1 MiB: a larger set goes to <name>.npz + <name>.part<k>.npz
+
+
+def save_parts(path, arrays):
+    """np.savez_compressed split by member into <stem>.npz, <stem>.part1.npz, ... of < PART_BYTES each (tests/conftest.py: golden() merges
+    them in order).  Returns the paths written."""
+    import glob
+    import zlib
+    stem = path[:-len(".npz")]
+    parts, size = [{}], 0
+    for k, v in arrays.items():
+        z = len(zlib.compress(np.ascontiguousarray(v).tobytes())) + 512      # deflated member + npy / zip headers
+        if parts[-1] and size + z > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += z
+    for old in glob.glob(glob.escape(stem) + ".part*.npz"):
+        os.remove(old)
+    paths = [stem + (".npz" if i == 0 else f".part{i}.npz") for i in range(len(parts))]
+    for p, members in zip(paths, parts):
+        np.savez_compressed(p, **members)
+        assert os.path.getsize(p) < 1 << 20, f"{p}: one member is over the size limit on its own"
+    return paths
+
+
 def save(out, name, **arrays):
-    path = os.path.join(out, name + ".npz")
-    np.savez_compressed(path, **{k: t2n(v) for k, v in arrays.items()})
-    print(f"  wrote {path} ({os.path.getsize(path)/1024:.1f} KiB)")
+    for path in save_parts(os.path.join(out, name + ".npz"), {k: t2n(v) for k, v in arrays.items()}):
+        print(f"  wrote {path} ({os.path.getsize(path)/1024:.1f} KiB)")
 
 
 # ----------------------------------------------------------------------------------------------

@@ -26,6 +26,6 @@ def gen_sam2(out_dir):
         arrays[f"fpn{i}"] = f.numpy()
     for k, v in m.state_dict().items():
         arrays["w:" + k] = v.numpy()
-    path = os.path.join(out_dir, "hf_sam2_hiera.npz")
-    np.savez_compressed(path, **arrays)
-    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+    from gen_golden import save_parts                     # (tools/ is on the path: gen_hf_golden.py imports this module as a sibling)
+    for path in save_parts(os.path.join(out_dir, "hf_sam2_hiera.npz"), arrays):
+        print("wrote", path, os.path.getsize(path) // 1024, "KiB")
