@@ -718,6 +718,42 @@ void ovo_host_free(void *p);
 int ovo_host_wait32(const int32_t *flag, int32_t value, int64_t timeout_us);
 int ovo_host_wait64(const int64_t *flag, int64_t value, int64_t timeout_us);
 
+/* ---- evaluation: eval_utils.py:13-41, 108-112 ------------------------------------------------------------------
+ * match_labels_to_vtx: the reference builds a scipy KD-tree over the (assigned) map points, queries the 5 nearest of every
+ * ground-truth mesh vertex and takes torch.mode of their labels.  Here a uniform grid over the points' bounding box:
+ *   lo  = minimum x, y, z of the points (f32, exact);  h = cell edge in metres (host's choice);
+ *   dim = floor(((double)max - (double)lo) * (1.0 / h)) + 1 per axis, so every point falls inside; <= OVO_EVAL_MAX_DIM, product < 2^31.
+ * cell coordinate of x: floor(((double)x - (double)lo) * (1.0 / h)); key = (cz * dim[1] + cy) * dim[0] + cx.
+ *   ovo_eval_cell_keys   : keys i32[n], coordinates clamped into the grid (also used to order the vertices)
+ *   ovo_eval_grid_records: records[i] = (x, y, z as f32, bits of (int32) order[i]) of point order[i]; `order` = argsort of the keys
+ *                          (i64[n]); 16 bytes each, 16-byte aligned
+ *   ovo_knn5_labels      : cell_start i32[cells + 1] = first record of each cell (cell_start[cells] = n_points).  For vertex
+ *                          v: nn_idx[v, 0..4] = ORIGINAL rows of its 5 nearest points, ascending squared distance
+ *                          (dx*dx + dy*dy + dz*dz in f64 on the f64 conversions of the f32 inputs; equal distances: lower row first),
+ *                          nn_d2 f64[V,5] those distances (or NULL), label[v] = most frequent of labels[nn_idx[v, :]], ties to the
+ *                          smallest label as CPU torch.mode (label and labels may both be NULL).  vtx_order i64[V] (or NULL): lane t works
+ *                          on vertex vtx_order[t] -- pass the argsort of the vertices' keys so a wave walks the same cells; results land in
+ *                          the caller's order.  Vertices outside the box are fine.  visited (or NULL): u64 device counter, the number of
+ *                          candidate points examined is ADDED to it.  Needs n_points >= 5.
+ * update_confmat: confusion[gt][pr] += 1 for every pair whose gt is not in `ignore` (a HOST list, <= OVO_EVAL_MAX_IGNORE ids), indexed
+ * as numpy does: an id in [-C, 0) wraps to id + C; any other id outside [0, C) makes the reference raise IndexError -- here it sets
+ * *out_of_range = 1 (device i32, zeroed by the caller) and that pair is not counted.  The counts are ADDED to confusion u64[C,C]. */
+#define OVO_EVAL_MAX_DIM 1024
+#define OVO_EVAL_MAX_IGNORE 64
+#define OVO_EVAL_MAX_CLASSES 4096
+typedef struct {
+    float lo[3];
+    int32_t dim[3];
+    double h;
+} ovo_eval_grid_t;
+int ovo_eval_cell_keys(const float *xyz, int64_t n, const ovo_eval_grid_t *grid, int32_t *keys, ovo_stream_t stream);
+int ovo_eval_grid_records(const float *xyz, const int64_t *order, int64_t n, void *records, ovo_stream_t stream);
+int ovo_knn5_labels(const void *records, const int32_t *cell_start, int64_t n_points, const ovo_eval_grid_t *grid, const float *vtx,
+                    const int64_t *vtx_order, int64_t n_vtx, const int32_t *labels, int32_t *nn_idx, double *nn_d2, int32_t *label,
+                    uint64_t *visited, ovo_stream_t stream);
+int ovo_confusion(const int64_t *gt, const int64_t *pr, int64_t n, int n_classes, const int64_t *ignore_host, int n_ignore,
+                  uint64_t *confusion, int32_t *out_of_range, ovo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

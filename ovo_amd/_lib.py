@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "lib", "libovo_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 E_UNSUPPORTED = -3          # OVO_E_UNSUPPORTED: the entry point does not cover this shape; the caller takes its general path
 
 
@@ -126,6 +126,11 @@ class RoundChain(C.Structure):
     _fields_ = [("params_host", _P), ("barrier", _P), ("arrivals", C.c_uint64), ("next_slot", C.c_uint32), ("workgroups", C.c_int32)]
 
 
+class EvalGrid(C.Structure):
+    """ovo_eval_grid_t"""
+    _fields_ = [("lo", C.c_float * 3), ("dim", C.c_int32 * 3), ("h", C.c_double)]
+
+
 DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.uint8: 3}
 
 _SIGNATURES = {
@@ -221,6 +226,10 @@ _SIGNATURES = {
     "ovo_hiera_workspace_bytes": (_SZ, [C.POINTER(HieraConfig), _I32]),
     "ovo_hiera_forward": (_I32, [C.POINTER(HieraConfig), C.POINTER(HieraWeights), _P, _I32, _P, _P, _P, _P, _SZ, _P]),
     "ovo_hiera_patch_embed": (_I32, [_P, _I32, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
+    "ovo_eval_cell_keys": (_I32, [_P, _I64, C.POINTER(EvalGrid), _P, _P]),
+    "ovo_eval_grid_records": (_I32, [_P, _P, _I64, _P, _P]),
+    "ovo_knn5_labels": (_I32, [_P, _P, _I64, C.POINTER(EvalGrid), _P, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    "ovo_confusion": (_I32, [_P, _P, _I64, _I32, C.POINTER(C.c_int64), _I32, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

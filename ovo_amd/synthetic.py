@@ -139,3 +139,33 @@ def padded_map(n_points: int, frames: int = 4, scale: float = 1.0, seed: int = 0
     rng = np.random.default_rng(5000 + seed)
     fill = rng.uniform(ROOM_MIN, ROOM_MAX, size=(n_points - pts.shape[0], 3)).astype(np.float32)
     return np.ascontiguousarray(np.concatenate([pts, fill]))
+
+
+ROOM = (6.0, 4.0, 2.7)          # metres
+
+
+def eval_scene(n_points: int, n_vtx: int, n_instances: int = 200, seed: int = 0, unassigned: float = 0.15, label_noise: float = 0.05):
+    """A finished map and a ground-truth mesh of one box room, for the evaluation step (utils/eval_utils.py): map points f32[n,3] on the six
+    faces of a ROOM-sized box with 1 cm noise, their instance ids i64[n] (nearest of `n_instances` random centres on the faces; a share
+    `unassigned` is -1, a share `label_noise` is a random id), mesh vertices f32[V,3] exactly on the faces."""
+    g = np.random.default_rng(seed)
+    size = np.array(ROOM)
+
+    def on_faces(n):
+        p = g.random((n, 3)) * size
+        face = g.integers(0, 6, n)
+        axis = face // 2
+        p[np.arange(n), axis] = (face % 2) * size[axis]
+        return p
+
+    vtx = on_faces(n_vtx).astype(np.float32)
+    pts = (on_faces(n_points) + g.normal(0.0, 0.01, (n_points, 3))).astype(np.float32)
+    centres = on_faces(n_instances).astype(np.float32)
+    ids = np.empty(n_points, dtype=np.int64)
+    for s in range(0, n_points, 1 << 16):                       # nearest centre, in slabs that stay small
+        d = ((pts[s:s + (1 << 16), None, :] - centres[None]) ** 2).sum(-1)
+        ids[s:s + (1 << 16)] = d.argmin(1)
+    noisy = g.random(n_points) < label_noise
+    ids[noisy] = g.integers(0, n_instances, int(noisy.sum()))
+    ids[g.random(n_points) < unassigned] = -1
+    return pts, ids, vtx
