@@ -48,19 +48,29 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _compile(src: str, force: bool) -> str:
+def _run(cmd, what: str) -> None:
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"{what} failed:\n{r.stdout}\n{r.stderr}")
+    if r.stderr.strip():
+        sys.stderr.write(r.stderr)
+
+
+def _compile(src: str, flags, force: bool) -> bool:
+    """Compiles csrc/<src> when its object is missing, older than a source or header, or was built by another command line (the `.cmd` file beside it:
+    compiler path and every flag, so that objects of a --gemm-debug / --experimental / OVO_HIPCC_EXTRA build never survive into a normal one).
+    Returns whether it compiled."""
     obj = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
     deps = [os.path.join(CSRC, src)] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
     deps.append(os.path.join(os.path.dirname(HERE), "include", "ovo_hip.h"))
-    deps.append(os.path.abspath(__file__))                       # the flags live here
-    if force or _stale(obj, deps):
-        cmd = [hipcc(), "-c", os.path.join(CSRC, src), "-o", obj] + COMMON + EXTRA.get(src, [])
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"hipcc failed on {src}:\n{r.stdout}\n{r.stderr}")
-        if r.stderr.strip():
-            sys.stderr.write(r.stderr)
-    return obj
+    cmd = [hipcc(), "-c", os.path.join(CSRC, src), "-o", obj] + COMMON + flags
+    line = " ".join(cmd) + "\n"
+    if not force and not _stale(obj, deps) and os.path.exists(obj + ".cmd") and open(obj + ".cmd").read() == line:
+        return False
+    _run(cmd, f"hipcc on {src}")
+    with open(obj + ".cmd", "w") as f:
+        f.write(line)
+    return True
 
 
 def build(force: bool = False, verbose: bool = True, gemm_debug: bool = False, experimental: bool = False) -> str:
@@ -68,25 +78,24 @@ def build(force: bool = False, verbose: bool = True, gemm_debug: bool = False, e
     (OVO_8P_DEBUG, OVO_8P_STAMPS, OVO_8P_DELAY, OVO_8Q_DEBUG) are compiled in; a production build has none of them.
     `experimental` (--experimental): also compiles the two forms that lost their measurements -- the persistent 256 x 128 GEMM (gemm8q.hip,
     OVO_GEMM_TILE=256x128p) and the one-launch round chain (k_round_chain, OVO_ROUND_CHAIN=1); their parity tests skip without it."""
+    extra = {f: list(flags) for f, flags in EXTRA.items()}         # this call's flag table; EXTRA itself stays as written
     if gemm_debug:
         for f in ("gemm8p.hip", "gemm8q.hip", "mlp_stream.hip"):
-            EXTRA[f] = EXTRA.get(f, []) + ["-DOVO_GEMM_DEBUG"]
+            extra.setdefault(f, []).append("-DOVO_GEMM_DEBUG")
     if experimental:                                   # kernels that were measured and lost (persistent 256 x 128 GEMM, one-launch round chain)
         for f in ("gemm8q.hip", "geometry.hip"):
-            EXTRA[f] = EXTRA.get(f, []) + ["-DOVO_EXPERIMENTAL"]
+            extra.setdefault(f, []).append("-DOVO_EXPERIMENTAL")
     # experiments only (tools/): OVO_HIPCC_EXTRA="mlp_stream.hip=-fno-slp-vectorize;gemm8p.hip=-mllvm,-amdgpu-..." adds flags to single translation units
     for item in filter(None, os.environ.get("OVO_HIPCC_EXTRA", "").split(";")):
         f, _, flags = item.partition("=")
-        EXTRA[f] = EXTRA.get(f, []) + [x for x in flags.split(",") if x]
+        extra.setdefault(f, []).extend(x for x in flags.split(",") if x)
     os.makedirs(OBJ_DIR, exist_ok=True)
     srcs = sources()
     with cf.ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
-        objs = list(ex.map(lambda s: _compile(s, force), srcs))
-    if force or _stale(SO, objs):
-        cmd = [hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", SO] + objs
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+        rebuilt = list(ex.map(lambda s: _compile(s, extra.get(s, []), force), srcs))
+    objs = [os.path.join(OBJ_DIR, s.replace(".hip", ".o")) for s in srcs]
+    if any(rebuilt) or _stale(SO, objs):
+        _run([hipcc(), "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", SO] + objs, "link")
     if verbose:
         print(f"[ovo_amd.build] {SO} ({os.path.getsize(SO) / 1024:.0f} KiB, {len(srcs)} translation units)")
     return SO

@@ -736,24 +736,9 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 && KS == 4) ? 3 : 2) k_atten
 
 }  // namespace
 
-namespace {
-struct AttnKnobs {                                   // environment knobs of the dispatcher (see ovo_knobs_dynamic)
-    bool wide, narrow, no_chunk, no_tiny;
-    int force32;
-    void read() {
-        wide = getenv("OVO_ATTN_WIDE"); narrow = getenv("OVO_ATTN_NARROW"); no_chunk = getenv("OVO_ATTN_NO_CHUNK"); no_tiny = getenv("OVO_ATTN_NO_TINY");
-        force32 = getenv("OVO_ATTN32") ? atoi(getenv("OVO_ATTN32")) : -1;
-    }
-};
-const AttnKnobs &attn_knobs() {
-    static AttnKnobs k = [] { AttnKnobs x; x.read(); return x; }();
-    if (ovo_knobs_dynamic()) k.read();
-    return k;
-}
-}  // namespace
-
 extern "C" int ovo_attention(const ovo_attention_t *p, ovo_stream_t stream) {
-    const AttnKnobs &kn = attn_knobs();
+    const struct { bool wide, narrow, no_chunk, no_tiny; int force32; } kn = {      // environment knobs of the dispatcher (common.h: ovo_knob_*)
+        ovo_knob_set("OVO_ATTN_WIDE"), ovo_knob_set("OVO_ATTN_NARROW"), ovo_knob_set("OVO_ATTN_NO_CHUNK"), ovo_knob_set("OVO_ATTN_NO_TINY"), ovo_knob_int("OVO_ATTN32", -1)};
     OVO_REQUIRE(p && p->q && p->k && p->v && p->o, "null pointer");
     OVO_REQUIRE(p->B > 0 && p->H > 0 && p->Tq > 0 && p->Tk > 0, "bad shape");
     OVO_REQUIRE(p->hd > 0 && p->hd <= 128 && p->hd % 8 == 0, "head_dim must be a multiple of 8, <= 128");

@@ -49,13 +49,30 @@ void ovo_prof_count(const int32_t *device_count, double per_item, double fixed, 
         }                                                                         \
     } while (0)
 
-// Tuning knobs (OVO_GEMM_*, OVO_ATTN_*: tools/ and tests only) are read from the environment ONCE per process -- a launch does not call
-// getenv.  Tools and tests that flip them between launches of one process (tools/gemm_bench.py, tools/attn_bench.py, tests/conftest.py) set
-// OVO_KNOBS_DYNAMIC=1 before the first launch: every launch then reads them afresh.
+// Tuning knobs (OVO_*: tools/ and tests only).  The contract, implemented HERE and nowhere else: a launch does not call getenv -- a knob is read from
+// the environment once per process, at the first use of its call site.  Tools and tests that flip knobs between launches of one process
+// (tools/gemm_bench.py, tools/attn_bench.py, tests/conftest.py) set OVO_KNOBS_DYNAMIC=1 before the first launch: every use then reads afresh.
+// ovo_knob_set(name): the variable exists, whatever its value; ovo_knob_int(name, dflt): atoi of it, or dflt; ovo_knob_str(name): a copy of its
+// first 15 characters.  Each expansion owns its cached value (a knob read in several files gets ONE accessor: gemm_common.h), and costs a
+// cached load and a branch when not dynamic.  Outside the contract, each with its reason where it stands: OVO_KNOBS_DYNAMIC itself, OVO_PROF_DUMP
+// (core.hip) and the buffer addresses of the OVO_GEMM_DEBUG builds (gemm8p.hip, mlp_stream.hip).
 static inline bool ovo_knobs_dynamic() {
-    static const bool d = getenv("OVO_KNOBS_DYNAMIC") != nullptr;
+    static const bool d = getenv("OVO_KNOBS_DYNAMIC") != nullptr;       // decides how every other knob is read: itself read once, always
     return d;
 }
+struct OvoKnobStr { bool set; char s[16]; };
+static inline int ovo_env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
+static inline OvoKnobStr ovo_env_str(const char *name) {
+    OvoKnobStr k;
+    const char *e = getenv(name);
+    k.set = e != nullptr;
+    snprintf(k.s, sizeof(k.s), "%s", e ? e : "");
+    return k;
+}
+#define OVO_KNOB_(T, read) ([&]() -> T { static T v_ = (read); if (ovo_knobs_dynamic()) v_ = (read); return v_; }())
+#define ovo_knob_set(name) OVO_KNOB_(bool, getenv(name) != nullptr)
+#define ovo_knob_int(name, dflt) OVO_KNOB_(int, ovo_env_int(name, dflt))
+#define ovo_knob_str(name) OVO_KNOB_(OvoKnobStr, ovo_env_str(name))
 
 static inline int ovo_grid(int64_t work_items, int block, int cap = 256 * 8) {
     int64_t g = (work_items + block - 1) / block;

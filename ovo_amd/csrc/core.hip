@@ -114,7 +114,7 @@ int ovo_profile_stop(double *ms, double *work, int64_t *launches, int n_kinds) {
     for (int i = 0; i < n_kinds; ++i) { ms[i] = 0; work[i] = 0; launches[i] = 0; }
     for (int i = 0; i < OVO_PROF_KINDS; ++i) g_last_bytes[i] = 0;
     OVO_HIP(hipDeviceSynchronize());
-    FILE *dump = getenv("OVO_PROF_DUMP") ? fopen(getenv("OVO_PROF_DUMP"), "a") : nullptr;   // diagnosis: one line per launch
+    FILE *dump = getenv("OVO_PROF_DUMP") ? fopen(getenv("OVO_PROF_DUMP"), "a") : nullptr;   // diagnosis: one line per launch (a file path read when profiling stops, not on a launch: no ovo_knob_*)
     for (const Rec &r : g_prof.recs) {
         float t = 0.f;
         if (hipEventElapsedTime(&t, r.a, r.b) != hipSuccess || r.kind >= n_kinds) continue;

@@ -359,8 +359,7 @@ inline void launch_resize_batch(const ResizeArgs &a, const ResizeBatch &b, int n
     dim3 grid((a.ow + 63) / 64, (a.oh + 3) / 4, nz);
     int bound = 0;
     for (int z = 0; z < nz; ++z) { const int t = resize_tap_bound(b.ch[z], b.cw[z], a.vh, a.vw); bound = t > bound ? t : bound; }
-    static const bool generic_once = getenv("OVO_RESIZE_GENERIC") != nullptr;              // measurement / tests
-    const bool generic = ovo_knobs_dynamic() ? getenv("OVO_RESIZE_GENERIC") != nullptr : generic_once;
+    const bool generic = ovo_knob_set("OVO_RESIZE_GENERIC");                               // measurement / tests
     if (!generic && a.hwc && a.src_u8 && a.C == 3 && a.aa == 1 && bound <= 3) k_resize_tri_hwc3<3><<<grid, 256, 0, s>>>(a, b, out);
     else if (!generic && a.hwc && a.src_u8 && a.C == 3 && a.aa == 1 && bound <= 6) k_resize_tri_hwc3<6><<<grid, 256, 0, s>>>(a, b, out);
     else k_resize_norm_batch<<<grid, 256, 0, s>>>(a, b, out);

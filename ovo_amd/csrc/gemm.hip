@@ -289,22 +289,14 @@ __global__ void __launch_bounds__(64 * NW) k_gemm(GemmArgs g) {
 
 template <int BM, int BN> struct Stages { static constexpr int value = (BM == 128 && BN == 128) || (BM == 64 && BN == 64) ? 4 : 3; };
 
-// environment knobs of the dispatcher (see ovo_knobs_dynamic)
+// environment knobs of the dispatcher (common.h: ovo_knob_*), read in one place for both of its instantiations
 struct GemmKnobs {
-    bool no_chunk, w4, no_ns2, no_stream, no_8p, no_tuned, has_tile;
-    char tile[16];
-    void read() {
-        no_chunk = getenv("OVO_GEMM_NO_CHUNK"); w4 = getenv("OVO_GEMM_W4"); no_ns2 = getenv("OVO_GEMM_NO_NS2");
-        no_stream = getenv("OVO_GEMM_NO_STREAM"); no_8p = getenv("OVO_GEMM_NO_8P"); no_tuned = getenv("OVO_GEMM_NO_TUNED");
-        const char *t = getenv("OVO_GEMM_TILE");
-        has_tile = t != nullptr;
-        snprintf(tile, sizeof(tile), "%s", t ? t : "");
-    }
+    bool w4, no_ns2, no_stream, no_8p, no_tuned;
+    OvoKnobStr tile;
 };
-static const GemmKnobs &gemm_knobs() {
-    static GemmKnobs k = [] { GemmKnobs x; x.read(); return x; }();
-    if (ovo_knobs_dynamic()) k.read();
-    return k;
+static GemmKnobs gemm_knobs() {
+    return {ovo_knob_set("OVO_GEMM_W4"), ovo_knob_set("OVO_GEMM_NO_NS2"), knob_gemm_no_stream(), ovo_knob_set("OVO_GEMM_NO_8P"), ovo_knob_set("OVO_GEMM_NO_TUNED"),
+            knob_gemm_tile()};
 }
 
 template <int BM, int BN, int BK, typename VT, int NW = 4, int NS = Stages<BM, BN>::value>
@@ -328,7 +320,7 @@ int launch(const GemmArgs &g0, hipStream_t s) {
     // Chunked order pays when the A panels outweigh the weights (M > N: per-XCD fills A/8 + W instead of A + W/8) or when
     // the n-tile count is not a multiple of 8 (round-robin then spreads every panel over every L2).
     g.tiles = nbm * g.nbn;
-    g.chunk = (g.M > g.N || g.nbn % 8 != 0) && !gemm_knobs().no_chunk ? (g.tiles + 7) / 8 : 0;
+    g.chunk = (g.M > g.N || g.nbn % 8 != 0) && !knob_gemm_no_chunk() ? (g.tiles + 7) / 8 : 0;
     const int grid = g.chunk > 0 ? g.chunk * 8 : g.tiles;
     k_gemm<BM, BN, BK, NS, VT, NW><<<grid, 64 * NW, lds, s>>>(g);
     if (prof) ovo_prof_end(s);
@@ -363,7 +355,7 @@ static int choose8p(int M, int N, int K, bool out_f32, bool add, bool *wins, boo
 
 template <typename VT>
 int dispatch(const GemmArgs &g, hipStream_t s) {
-    const GemmKnobs &kn = gemm_knobs();
+    const GemmKnobs kn = gemm_knobs();
     const bool k64 = g.K % 64 == 0;
     auto blocks = [&](int bm, int bn) { return (long long)((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn); };
     // Tile choice (tools/gemm_bench.py, MI355X): these GEMMs are a handful of workgroup "rounds" long, so round
@@ -401,7 +393,7 @@ int dispatch(const GemmArgs &g, hipStream_t s) {
     // the ring kernels above run ~650 TFLOP/s + 4 us at these sizes (tools/gemm_bench.py on MI355X, profiles/r02*_gemm_sweep.txt).
     // Tall short-K products are HBM streams: the weights-resident streaming kernel (gemm_stream.hip) runs them at 3+ TB/s, the tiled
     // kernels below at ~2 (tools/gemm_bench.py, profiles/r02c_gemm_stream.txt).
-    const char *force_tile = kn.has_tile ? kn.tile : nullptr;
+    const char *force_tile = kn.tile.set ? kn.tile.s : nullptr;
     if (!force_tile && !kn.no_tuned) {                               // measured choices first (gemm_tuned.h, tools/gemm_tune.py); family knobs still win
         const int f = gemm_flags(g);
         for (const TunedTile &e : kTunedTiles)
@@ -455,9 +447,19 @@ int dispatch(const GemmArgs &g, hipStream_t s) {
 }  // namespace
 
 struct RowLn { const float *g, *b; float eps; void *out; long long ld; };
-static int gemm_entry(const ovo_gemm_t *p, unsigned long long *best, int store, int n_valid, ovo_stream_t stream, const ovo_rope_t *rope = nullptr,
-                      const ovo_window_t *win = nullptr, long long add_rows = 0, const RowLn *rln = nullptr, const ovo_gemm_detail::FoldOut *fold_out = nullptr,
-                      const ovo_gemm_detail::FoldIn *fold_in = nullptr) {
+// what an entry point asks for on top of the plain product; each extern "C" wrapper names the fields it sets
+struct GemmOpts {
+    unsigned long long *best = nullptr;                          // fused argmax: its target, whether C is stored as well, the columns that may win
+    int store = 1, n_valid = 0;
+    const ovo_rope_t *rope = nullptr;                            // rotary embedding in the epilogue
+    const ovo_window_t *win = nullptr;                           // C / add rows in spatial order
+    long long add_rows = 0;                                      // periodic `add`
+    const RowLn *rln = nullptr;                                  // LayerNorm of the result rows
+    const ovo_gemm_detail::FoldOut *fold_out = nullptr;          // the LayerNorm fold's producer / consumer half
+    const ovo_gemm_detail::FoldIn *fold_in = nullptr;
+};
+static int gemm_entry(const ovo_gemm_t *p, ovo_stream_t stream, const GemmOpts &o = {}) {
+    const auto [best, store, n_valid, rope, win, add_rows, rln, fold_out, fold_in] = o;
     OVO_REQUIRE(p, "null descriptor");
     OVO_REQUIRE(p->M >= 0 && p->N > 0 && p->K > 0, "bad shape");
     if (p->M == 0) return OVO_OK;
@@ -470,16 +472,12 @@ static int gemm_entry(const ovo_gemm_t *p, unsigned long long *best, int store, 
     OVO_REQUIRE(p->ldc % 4 == 0 && ((uintptr_t)p->C & 15) == 0, "C rows must be 16-byte aligned");
     OVO_REQUIRE(!p->add || (p->ld_add % 4 == 0 && ((uintptr_t)p->add & 15) == 0), "add rows must be 16-byte aligned");
     OVO_REQUIRE(!p->bias || ((uintptr_t)p->bias & 15) == 0, "bias must be 16-byte aligned");
-    GemmArgs g;
+    GemmArgs g = {};                                             // every field rests at zero but the divisors below
     g.A = (const char *)p->A; g.lda = p->lda; g.W = (const char *)p->W; g.ldw = p->ldw; g.bias = p->bias;
     g.C = p->C; g.ldc = p->ldc; g.add = p->add; g.ld_add = p->ld_add;
-    g.M = p->M; g.N = p->N; g.K = p->K; g.out_dtype = p->out_dtype; g.act = p->act; g.alpha = p->alpha; g.nbn = 0;
-    g.best = best; g.store = store; g.n_valid = n_valid; g.add_rows = (int)add_rows; g.strip = 0;
-    g.rope_cos = g.rope_sin = nullptr; g.rope_T = 1; g.rope_hd = 4; g.rope_cols = 0; g.rope_t0 = 0;
-    g.ln_x = g.ln_g = g.ln_b = nullptr; g.ln_eps = 0.f; g.ln_d = 0; g.ln_mode = 0; g.pool_ww = 0; g.qpool_out = nullptr; g.qpool_cols = 0;
-    g.rln_g = g.rln_b = nullptr; g.rln_eps = 0.f; g.rln_out = nullptr; g.rln_ld = 0;
-    g.xb_out = nullptr; g.ld_xb = 0; g.stat_out = nullptr; g.stat_ld = 0; g.fold_stats = nullptr; g.fold_parts = 0; g.fold_D = 0; g.fold_cs = nullptr; g.fold_eps = 0.f;
-    g.dbg = 0; g.slab16 = 0; g.rope_lds = 0; g.stamps = nullptr; g.win_per = 0; g.win_ww = g.win_wh = g.win_nww = g.win_nwin = 1; g.win_H = g.win_W = 0;
+    g.M = p->M; g.N = p->N; g.K = p->K; g.out_dtype = p->out_dtype; g.act = p->act; g.alpha = p->alpha;
+    g.best = best; g.store = store; g.n_valid = n_valid; g.add_rows = (int)add_rows;
+    g.rope_T = 1; g.rope_hd = 4; g.win_ww = g.win_wh = g.win_nww = g.win_nwin = 1;
     if (win) {
         OVO_REQUIRE(win->B > 0 && win->H > 0 && win->W > 0 && win->wh > 0 && win->ww > 0, "bad window descriptor");
         const int nwh = (win->H + win->wh - 1) / win->wh, nww = (win->W + win->ww - 1) / win->ww;
@@ -503,7 +501,7 @@ static int gemm_entry(const ovo_gemm_t *p, unsigned long long *best, int store, 
     }
     if (fold_out || fold_in) {                                    // the LayerNorm fold: ping-pong kernel or nothing
         int bn = ovo_gemm_detail::gemm_fold_ok(p->M, p->N, p->K) ? choose8p(p->M, p->N, p->K, p->out_dtype == 0, p->add != nullptr, nullptr, true) : 0;
-        if (bn && ovo_knobs_dynamic() && getenv("OVO_FOLD_TILE")) bn = atoi(getenv("OVO_FOLD_TILE")) == 128 ? 128 : 256;      // tools/fold_bench.py: either tile width on the fold's launches
+        if (bn && ovo_knobs_dynamic() && ovo_knob_set("OVO_FOLD_TILE")) bn = ovo_knob_int("OVO_FOLD_TILE", 0) == 128 ? 128 : 256;      // tools/fold_bench.py: either tile width on the fold's launches; honoured in dynamic mode only
         if (!bn || p->in_dtype != 2 || p->alpha != 1.0f || win || add_rows || best) return OVO_E_UNSUPPORTED;
         if (fold_out) {
             if (p->out_dtype != 0 || !p->add || p->act != 0 || rope) return OVO_E_UNSUPPORTED;
@@ -556,9 +554,15 @@ bool ovo_gemm_detail::gemm_fold_ok(int M, int N, int K) {
     // both halves run on the ping-pong kernel: batched forwards only (M >= 2048 rows, the dispatcher's own bound), whole 64-deep K-tiles, whole 64-column wave tiles
     return M >= 2048 && K % 64 == 0 && K >= 64 && N % 64 == 0 && N >= 256;
 }
-int ovo_gemm_detail::gemm_fold_producer(const ovo_gemm_t *p, const FoldOut &o, ovo_stream_t stream) { return gemm_entry(p, nullptr, 1, 0, stream, nullptr, nullptr, 0, nullptr, &o); }
+int ovo_gemm_detail::gemm_fold_producer(const ovo_gemm_t *p, const FoldOut &fo, ovo_stream_t stream) {
+    GemmOpts o;
+    o.fold_out = &fo;
+    return gemm_entry(p, stream, o);
+}
 int ovo_gemm_detail::gemm_fold_consumer(const ovo_gemm_t *p, const ovo_rope_t *rope, const FoldIn &f, ovo_stream_t stream) {
-    return gemm_entry(p, nullptr, 1, 0, stream, rope, nullptr, 0, nullptr, nullptr, &f);
+    GemmOpts o;
+    o.rope = rope; o.fold_in = &f;
+    return gemm_entry(p, stream, o);
 }
 
 extern "C" int ovo_gemm_fold_out(const ovo_gemm_t *p, void *xb, int64_t ld_xb, float *stats, int64_t ld_stats, ovo_stream_t stream) {
@@ -574,26 +578,32 @@ extern "C" int ovo_gemm_fold_in(const ovo_gemm_t *p, const ovo_rope_t *rope, con
     return ovo_gemm_detail::gemm_fold_consumer(p, rope, f, stream);
 }
 
-extern "C" int ovo_gemm(const ovo_gemm_t *p, ovo_stream_t stream) { return gemm_entry(p, nullptr, 1, 0, stream); }
+extern "C" int ovo_gemm(const ovo_gemm_t *p, ovo_stream_t stream) { return gemm_entry(p, stream); }
 
 // ovo_gemm with the rotary embedding of PE's attention (ovo_rope_qk) applied to the f32 accumulators of columns [0, cols) before
 // the store: the QKV projection writes rotated q, k directly (one rounding instead of two, one launch less per block).
 extern "C" int ovo_gemm_rope(const ovo_gemm_t *p, const ovo_rope_t *rope, ovo_stream_t stream) {
     OVO_REQUIRE(rope, "null rope descriptor");
-    return gemm_entry(p, nullptr, 1, 0, stream, rope);
+    GemmOpts o;
+    o.rope = rope;
+    return gemm_entry(p, stream, o);
 }
 
 // ovo_gemm whose C / add rows are addressed in spatial order while the product rows arrive in window order (Hiera's attention
 // output projection): the un-windowing + residual add pass of the block happens in the epilogue.
 extern "C" int ovo_gemm_unwindow(const ovo_gemm_t *p, const ovo_window_t *win, ovo_stream_t stream) {
     OVO_REQUIRE(win, "null window descriptor");
-    return gemm_entry(p, nullptr, 1, 0, stream, nullptr, win);
+    GemmOpts o;
+    o.win = win;
+    return gemm_entry(p, stream, o);
 }
 
 int ovo_gemm_detail::gemm_unwindow_rowln(const ovo_gemm_t *p, const ovo_window_t *win, const float *ln_g, const float *ln_b, float eps, void *ln_out,
                                          long long ld_ln, ovo_stream_t stream) {
     const RowLn r = {ln_g, ln_b, eps, ln_out, ld_ln};
-    return gemm_entry(p, nullptr, 1, 0, stream, nullptr, win, 0, &r);
+    GemmOpts o;
+    o.win = win; o.rln = &r;
+    return gemm_entry(p, stream, o);
 }
 extern "C" int ovo_gemm_rowln(const ovo_gemm_t *p, const ovo_window_t *win, const float *ln_g, const float *ln_b, float eps, void *ln_out, int64_t ld_ln,
                               ovo_stream_t stream) {
@@ -604,7 +614,9 @@ extern "C" int ovo_gemm_rowln(const ovo_gemm_t *p, const ovo_window_t *win, cons
 // the SAM2 decoder: the projection of the positional code, so that k_proj(keys + pe) = keys . Wk^T + (pe . Wk^T)[pixel] needs no (keys + pe) tensor).
 extern "C" int ovo_gemm_periodic(const ovo_gemm_t *p, int64_t add_rows, ovo_stream_t stream) {
     OVO_REQUIRE(p && p->add && add_rows > 0 && add_rows < (1ll << 31), "periodic add needs add and 0 < add_rows < 2^31");
-    return gemm_entry(p, nullptr, 1, 0, stream, nullptr, nullptr, add_rows);
+    GemmOpts o;
+    o.add_rows = add_rows;
+    return gemm_entry(p, stream, o);
 }
 
 // C as ovo_gemm, plus a fused per-row first-max argmax over columns [0, n_valid): best u64 [M] must be ZERO on entry and holds, per
@@ -612,7 +624,9 @@ extern "C" int ovo_gemm_periodic(const ovo_gemm_t *p, int64_t add_rows, ovo_stre
 // (the 5 GB score matrix of a 1.25M x 1000 query is then never written).  Decode with ovo_decode_best.
 extern "C" int ovo_gemm_argmax(const ovo_gemm_t *p, uint64_t *best, int store_scores, int n_valid, ovo_stream_t stream) {
     OVO_REQUIRE(best && n_valid > 0 && p && n_valid <= p->N, "best must be non-null, 0 < n_valid <= N");
-    return gemm_entry(p, (unsigned long long *)best, store_scores != 0, n_valid, stream);
+    GemmOpts o;
+    o.best = (unsigned long long *)best; o.store = store_scores != 0; o.n_valid = n_valid;
+    return gemm_entry(p, stream, o);
 }
 
 namespace {

@@ -744,28 +744,16 @@ template <int BM, int BN, int WARPS_M, typename VT, bool STAGED, int MF = 16, bo
 int launch8p_(const GemmArgs &g0, hipStream_t s) {
     GemmArgs g = g0;
     g.dbg = 0; g.stamps = nullptr;
-#ifdef OVO_GEMM_DEBUG        // the stamp buffer's ADDRESS comes from the environment: never in a production build
-    g.dbg = (getenv("OVO_8P_DEBUG") ? atoi(getenv("OVO_8P_DEBUG")) : 0) | ((getenv("OVO_8P_DELAY") ? atoi(getenv("OVO_8P_DELAY")) : 0) << 8);
+#ifdef OVO_GEMM_DEBUG        // never in a production build; the stamp buffer's ADDRESS comes from the environment, afresh for every launch: not a knob (common.h)
+    g.dbg = ovo_knob_int("OVO_8P_DEBUG", 0) | (ovo_knob_int("OVO_8P_DELAY", 0) << 8);
     g.stamps = getenv("OVO_8P_STAMPS") ? (unsigned long long *)strtoull(getenv("OVO_8P_STAMPS"), nullptr, 0) : nullptr;
 #endif
-    static bool no_chunk = getenv("OVO_GEMM_NO_CHUNK") != nullptr;              // tuning knobs: read once (see ovo_knobs_dynamic)
-    static int strip_env = getenv("OVO_GEMM_STRIP") ? atoi(getenv("OVO_GEMM_STRIP")) : -1;
-    static int tail_wait = getenv("OVO_8P_TAILWAIT") ? atoi(getenv("OVO_8P_TAILWAIT")) : 0;
-    if (ovo_knobs_dynamic()) { no_chunk = getenv("OVO_GEMM_NO_CHUNK") != nullptr; strip_env = getenv("OVO_GEMM_STRIP") ? atoi(getenv("OVO_GEMM_STRIP")) : -1;
-                               tail_wait = getenv("OVO_8P_TAILWAIT") ? atoi(getenv("OVO_8P_TAILWAIT")) : 0; }
-    g.tail_wait = tail_wait;
-    static int no_slab16 = getenv("OVO_8P_NO_SLAB16") != nullptr;
-    if (ovo_knobs_dynamic()) no_slab16 = getenv("OVO_8P_NO_SLAB16") != nullptr;
-    g.slab16 = !no_slab16;
-    static int rope_lds_on = getenv("OVO_8P_ROPE_LDS") ? atoi(getenv("OVO_8P_ROPE_LDS")) : 1;      // (0: every wave loads its table rows itself)
-    if (ovo_knobs_dynamic()) rope_lds_on = getenv("OVO_8P_ROPE_LDS") ? atoi(getenv("OVO_8P_ROPE_LDS")) : 1;
-    g.rope_lds = rope_lds_on;
-    static int gelu_poly = getenv("OVO_GELU_POLY") != nullptr;
-    if (ovo_knobs_dynamic()) gelu_poly = getenv("OVO_GELU_POLY") != nullptr;
-    g.gelu_lut = !gelu_poly;
-    static int res_plain = getenv("OVO_8P_RES_PLAIN") ? atoi(getenv("OVO_8P_RES_PLAIN")) : 0;
-    if (ovo_knobs_dynamic()) res_plain = getenv("OVO_8P_RES_PLAIN") ? atoi(getenv("OVO_8P_RES_PLAIN")) : 0;
-    g.res_plain = res_plain;
+    const int strip_env = ovo_knob_int("OVO_GEMM_STRIP", -1);                   // tuning knobs (common.h: ovo_knob_*)
+    g.tail_wait = ovo_knob_int("OVO_8P_TAILWAIT", 0);
+    g.slab16 = !knob_8p_no_slab16();
+    g.rope_lds = ovo_knob_int("OVO_8P_ROPE_LDS", 1);                            // (0: every wave loads its table rows itself)
+    g.gelu_lut = !knob_gelu_poly();
+    g.res_plain = ovo_knob_int("OVO_8P_RES_PLAIN", 0);
     if (g.fold_stats || g.xb_out) {            // the LayerNorm fold lives in the staged epilogues the ViT's products take; anything else is refused, not approximated
         const bool cons_ok = !g.fold_stats || (STAGED && g.out_dtype != 0 && !g.add && !g.best && g.fold_cs && g.fold_parts >= 1 && g.fold_parts <= 16 && g.N % 64 == 0 && g.slab16 &&
                                                ((!g.rope_cos && (g.act == 0 || (g.act == 1 && g.gelu_lut))) || (g.rope_cos && g.act == 0 && g.rope_hd == 64 && g.rope_lds)));
@@ -791,7 +779,7 @@ int launch8p_(const GemmArgs &g0, hipStream_t s) {
     const bool prof = ovo_prof_enabled();
     if (prof) { ovo_prof_begin(BN == 256 ? 3 : 0, 2.0 * g.M * (double)g.N * g.K, s); ovo_prof_shape(g.M, g.N, g.K); ovo_prof_flags(gemm_flags(g)); ovo_prof_bytes(gemm_algorithmic_bytes(g)); }     // kinds 3 / 0: 256x256 / 256x128
     g.tiles = nbm * g.nbn;
-    g.chunk = (g.M > g.N || g.nbn % 8 != 0) && !no_chunk ? (g.tiles + 7) / 8 : 0;
+    g.chunk = (g.M > g.N || g.nbn % 8 != 0) && !knob_gemm_no_chunk() ? (g.tiles + 7) / 8 : 0;
     // tile order: measured to matter little (the K-loop is bound by the L2->LDS arrival rate, not by L2 misses); column strips of 8 n-tiles
     // gain ~5% on the widest products (N/BN >= 16: the per-XCD working set of a round drops under the 4 MB L2), nothing elsewhere
     g.strip = strip_env >= 0 ? strip_env : (g.nbn >= 16 ? 8 : 0);
@@ -805,20 +793,17 @@ int launch8p_(const GemmArgs &g0, hipStream_t s) {
 template <int BM, int BN, int WARPS_M, typename VT>
 int launch8p(const GemmArgs &g, hipStream_t s) {
     // OVO_8P_MFMA32 = 1: the 32 x 32 x 16 MFMA K-loop for the staged epilogues (bf16; measured against the 16 x 16 x 32 loop in profiles/r05*_gemm_mfma32.txt)
-    static int mf32 = getenv("OVO_8P_MFMA32") ? atoi(getenv("OVO_8P_MFMA32")) : OVO_8P_MFMA32_DEFAULT;
-    if (ovo_knobs_dynamic()) mf32 = getenv("OVO_8P_MFMA32") ? atoi(getenv("OVO_8P_MFMA32")) : OVO_8P_MFMA32_DEFAULT;
+    const int mf32 = ovo_knob_int("OVO_8P_MFMA32", OVO_8P_MFMA32_DEFAULT);
     // the fused argmax: straight from the accumulators -- unless the scores are stored too as plain 2-byte rows, which leave through the staged epilogue
-    static int best_staged = getenv("OVO_8P_BEST_STAGED") ? atoi(getenv("OVO_8P_BEST_STAGED")) : 1;
-    if (ovo_knobs_dynamic()) best_staged = getenv("OVO_8P_BEST_STAGED") ? atoi(getenv("OVO_8P_BEST_STAGED")) : 1;
-    if (g.best && !(best_staged && g.store && g.out_dtype != 0 && !g.add && !g.act && !g.rope_cos && g.win_per <= 0 && BN / (8 / WARPS_M) == 64 && !getenv("OVO_8P_NO_SLAB16")))
+    const int best_staged = ovo_knob_int("OVO_8P_BEST_STAGED", 1);
+    if (g.best && !(best_staged && g.store && g.out_dtype != 0 && !g.add && !g.act && !g.rope_cos && g.win_per <= 0 && BN / (8 / WARPS_M) == 64 && !knob_8p_no_slab16()))
         return launch8p_<BM, BN, WARPS_M, VT, false>(g, s);
     if (g.best) return launch8p_<BM, BN, WARPS_M, VT, true>(g, s);
     if constexpr (std::is_same<VT, bf16x8>::value) {
         if (mf32) return launch8p_<BM, BN, WARPS_M, VT, true, 32>(g, s);
     }
     // OVO_8P_MERGED: two barrier intervals per K-tile (the 256 x 256 tile's staged forms)
-    static int merged = getenv("OVO_8P_MERGED") ? atoi(getenv("OVO_8P_MERGED")) : OVO_8P_MERGED_DEFAULT;
-    if (ovo_knobs_dynamic()) merged = getenv("OVO_8P_MERGED") ? atoi(getenv("OVO_8P_MERGED")) : OVO_8P_MERGED_DEFAULT;
+    const int merged = ovo_knob_int("OVO_8P_MERGED", OVO_8P_MERGED_DEFAULT);
     if constexpr (BN == 256) {
         if (merged) return launch8p_<BM, BN, WARPS_M, VT, true, 16, true>(g, s);
     }

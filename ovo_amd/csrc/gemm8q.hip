@@ -379,8 +379,7 @@ int launch8q(const GemmArgs &g0, hipStream_t s) {
     GemmArgs &g = p.g;
     g.dbg = 0; g.stamps = nullptr;
 #ifdef OVO_GEMM_DEBUG
-    static const int dbg = getenv("OVO_8Q_DEBUG") ? atoi(getenv("OVO_8Q_DEBUG")) : 0;
-    g.dbg = dbg;
+    g.dbg = ovo_knob_int("OVO_8Q_DEBUG", 0);
 #endif
     g.nbn = (g.N + BN - 1) / BN;
     const int nbm = (g.M + BM - 1) / BM;

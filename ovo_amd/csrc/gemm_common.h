@@ -269,6 +269,13 @@ inline double gemm_algorithmic_bytes(const GemmArgs &g) {
            (g.fold_stats ? (double)g.M * g.fold_parts * 8.0 + g.N * 4.0 : 0.0);           // consumer: the partials of its rows (once per row block of tiles at least) + row sums
 }
 
+// knobs that several translation units read (common.h: ovo_knob_*): one accessor, so one cached value, for all of them
+inline bool knob_gemm_no_chunk() { return ovo_knob_set("OVO_GEMM_NO_CHUNK"); }       // tiles in plain order, no XCD chunks (gemm.hip, gemm8p.hip)
+inline bool knob_gemm_no_stream() { return ovo_knob_set("OVO_GEMM_NO_STREAM"); }     // no weights-resident streaming kernels (gemm.hip, gemm_stream.hip, mlp_stream.hip)
+inline OvoKnobStr knob_gemm_tile() { return ovo_knob_str("OVO_GEMM_TILE"); }         // forced tile "128x64", "256x256", "stream", ...; set = no fused streaming forms either
+inline bool knob_gelu_poly() { return ovo_knob_set("OVO_GELU_POLY"); }               // GELU as the packed polynomial, not the LDS table (gemm8p.hip, gemm_stream.hip, mlp_stream.hip)
+inline bool knob_8p_no_slab16() { return ovo_knob_set("OVO_8P_NO_SLAB16"); }         // gemm8p.hip: the f32 epilogue slab; also keeps the argmax out of the staged epilogue
+
 // launch of the 256-row ping-pong kernels (gemm8p.hip); bn in {128, 256}; returns OVO_E_UNSUPPORTED when the shape does not fit
 int gemm8p_launch(const GemmArgs &g, int bn, int in_dtype, hipStream_t s);
 

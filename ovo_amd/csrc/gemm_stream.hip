@@ -246,9 +246,7 @@ namespace ovo_gemm_detail {
 
 // Returns OVO_E_UNSUPPORTED when the shape has no instantiation (the caller then takes a tiled kernel).
 int gemm_stream_launch(const GemmArgs &g, int in_dtype, hipStream_t s) {
-    static int gelu_poly = getenv("OVO_GELU_POLY") != nullptr;
-    if (ovo_knobs_dynamic()) gelu_poly = getenv("OVO_GELU_POLY") != nullptr;
-    if (g.best || g.rope_cos || in_dtype != 2 || g.act > 1 || (g.act == 1 && gelu_poly)) return OVO_E_UNSUPPORTED;
+    if (g.best || g.rope_cos || in_dtype != 2 || g.act > 1 || (g.act == 1 && knob_gelu_poly())) return OVO_E_UNSUPPORTED;
     if (g.M < 16384 || ((uintptr_t)g.C & 15) != 0 || g.ldc % 4 != 0) return OVO_E_UNSUPPORTED;
     // column groups: the widest of 256 / 224 / 112 / 64 / 32 that divides N (hiera_b+'s 112-multiples, powers of two); 288 / 144 for
     // hiera_l's stage 1 (K = 192: 144 channels padded)
@@ -279,12 +277,7 @@ int gemm_stream_launch(const GemmArgs &g, int in_dtype, hipStream_t s) {
 // hiera.hip's entry: `p` as for ovo_gemm with A unused; A = LayerNorm (mode 1) / cast (mode 2) of x[source row, :d] (f32), source row of product
 // row m = its spatial token when `win` describes a window partition (padding rows = zeros), m itself without.  OVO_E_UNSUPPORTED: no
 // instantiation for the shape (the caller normalises / casts into a buffer and calls ovo_gemm).
-static bool stream_off() {                              // OVO_GEMM_NO_STREAM / OVO_GEMM_TILE / OVO_NO_LN_FOLD (see ovo_knobs_dynamic)
-    auto read = [] { return getenv("OVO_GEMM_NO_STREAM") || getenv("OVO_GEMM_TILE") || getenv("OVO_NO_LN_FOLD"); };
-    static bool off = read();
-    if (ovo_knobs_dynamic()) off = read();
-    return off;
-}
+static bool stream_off() { return knob_gemm_no_stream() || knob_gemm_tile().set || ovo_knob_set("OVO_NO_LN_FOLD"); }      // (common.h: ovo_knob_*)
 
 int gemm_f32a_stream(const ovo_gemm_t *p, const ovo_window_t *win, const float *x, int d, const float *gamma, const float *beta, float eps, int mode,
                      int pool2x2, ovo_stream_t stream, uint16_t *qpool_out, int qpool_cols) {

@@ -465,8 +465,7 @@ __device__ void dev_track_project(Blk b, const float *__restrict__ pts, const in
 // workgroups would take 48.7 us at 10 M -- the same-address atomics cost ~3 ns each).
 constexpr int TRACK_GRID_CAP_DEFAULT = 1024;
 static int track_grid_cap() {
-    static int cap = getenv("OVO_TRACK_GRID_CAP") ? atoi(getenv("OVO_TRACK_GRID_CAP")) : TRACK_GRID_CAP_DEFAULT;
-    if (ovo_knobs_dynamic()) cap = getenv("OVO_TRACK_GRID_CAP") ? atoi(getenv("OVO_TRACK_GRID_CAP")) : TRACK_GRID_CAP_DEFAULT;
+    const int cap = ovo_knob_int("OVO_TRACK_GRID_CAP", TRACK_GRID_CAP_DEFAULT);
     return cap > 0 ? cap : TRACK_GRID_CAP_DEFAULT;
 }
 #define TRACK_GRID_CAP track_grid_cap()

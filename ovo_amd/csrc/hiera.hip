@@ -495,8 +495,7 @@ int launch_patch_embed7(const float *img, int S, const void *w, int ldw, const f
 
 // E = 96 (hiera_t / s), 112 (b+), 144 (l); anything else (or a grid that does not tile by 8 x 32) keeps the im2col + GEMM form
 int patch_embed_direct(const float *img, int S, int E, const void *w, int ldw, const float *bias, const float *pos, float *out, int B, hipStream_t s) {
-    static const bool off_once = getenv("OVO_HIERA_PATCH_GEMM") != nullptr;               // measurement / tests: the im2col + GEMM form
-    if (ovo_knobs_dynamic() ? getenv("OVO_HIERA_PATCH_GEMM") != nullptr : off_once) return OVO_E_UNSUPPORTED;
+    if (ovo_knob_set("OVO_HIERA_PATCH_GEMM")) return OVO_E_UNSUPPORTED;                   // measurement / tests: the im2col + GEMM form
     if (S % 128 != 0 || ldw < 147) return OVO_E_UNSUPPORTED;
     switch (E) {
         case 96: return launch_patch_embed7<6>(img, S, w, ldw, bias, pos, out, B, s);
@@ -652,8 +651,7 @@ int ovo_hiera_forward(const ovo_hiera_config_t *cfg, const ovo_hiera_weights_t *
             // MLP below then skips its LayerNorm pass.  MEASURED AND LEFT OFF (tools/rowln_bench.py, profiles/r05c_rowln_bench.txt): 87 us against 64 (128 x 64
             // tiles) + 28 (LayerNorm pass) alone, but 25 us per block SLOWER inside the forward (15.97 vs 15.57 ms per 12 frames): one 512-thread workgroup
             // per CU with a two-stage ring of 72 KB K-tiles does not overlap its neighbours the way the small tiles and the copy-rate LayerNorm pass do.
-            static const bool rowln_once = getenv("OVO_HIERA_PROJ_LN") != nullptr;
-            const bool rowln = ovo_knobs_dynamic() ? getenv("OVO_HIERA_PROJ_LN") != nullptr : rowln_once;
+            const bool rowln = ovo_knob_set("OVO_HIERA_PROJ_LN");
             int rc = OVO_E_UNSUPPORTED;
             if (rowln && dout == 448 && kout == dout)
                 rc = ovo_gemm_detail::gemm_unwindow_rowln(&og, &ow, L.ln2_g, L.ln2_b, c.ln_eps, k.h, kout, stream);
@@ -670,7 +668,7 @@ int ovo_hiera_forward(const ovo_hiera_config_t *cfg, const ovo_hiera_weights_t *
         // chunk overwrites those lines before they are written back.  MEASURED AND LEFT OFF (bench.py, one box, 12-frame groups): one pass 409.4
         // frames/s, 96 MB chunks 404.0, 48 MB 398.2, 24 MB 387.1 -- the write stream of the FC1 chunks is not absorbed by the cache (the launches
         // stay write-bound) and every extra launch pair adds its ramp.  OVO_HIERA_MLP_CHUNK_MB = chunk size (default 0 = one pass over all rows).
-        static const long long chunk_mb = getenv("OVO_HIERA_MLP_CHUNK_MB") ? atoll(getenv("OVO_HIERA_MLP_CHUNK_MB")) : 0;
+        const long long chunk_mb = ovo_knob_int("OVO_HIERA_MLP_CHUNK_MB", 0);
         const long long hid_row = (long long)4 * dout * 2;
         long long chunk_rows = chunk_mb > 0 ? (chunk_mb << 20) / hid_row / 4096 * 4096 : 0;
         if (chunk_rows <= 0 || tok_out < 2 * chunk_rows || tok_out * hid_row <= (200ll << 20)) chunk_rows = tok_out;   // (a hidden block the cache holds anyway: one pass)

@@ -475,18 +475,14 @@ namespace ovo_gemm_detail {
 // the caller runs the two products.  Instantiations: Hiera hiera_b+ / hiera_s / hiera_t stage 1-2 widths (112, 224 | 96, 192) and hiera_l's 144, 288.
 int mlp_stream_launch(float *x, long long rows, int d, const float *ln_g, const float *ln_b, float eps, const void *w1, long long ldw1, const float *b1,
                       int hid, const void *w2, long long ldw2, const float *b2, hipStream_t s) {
-    auto read_off = [] { return getenv("OVO_NO_MLP_FUSE") != nullptr || getenv("OVO_GEMM_NO_STREAM") != nullptr || getenv("OVO_GEMM_TILE") != nullptr; };
-    static int off = read_off(), gelu_poly = getenv("OVO_GELU_POLY") != nullptr;                   // (see ovo_knobs_dynamic)
-    if (ovo_knobs_dynamic()) { off = read_off(); gelu_poly = getenv("OVO_GELU_POLY") != nullptr; }
-    if (off || gelu_poly || rows < 16384 || hid != 4 * d || !x || !ln_g || !ln_b || !w1 || !b1 || !w2 || !b2) return OVO_E_UNSUPPORTED;
+    const bool off = ovo_knob_set("OVO_NO_MLP_FUSE") || knob_gemm_no_stream() || knob_gemm_tile().set;      // (common.h: ovo_knob_*)
+    if (off || knob_gelu_poly() || rows < 16384 || hid != 4 * d || !x || !ln_g || !ln_b || !w1 || !b1 || !w2 || !b2) return OVO_E_UNSUPPORTED;
     if (ldw1 % 8 != 0 || ldw2 % 8 != 0 || (((uintptr_t)w1 | (uintptr_t)w2 | (uintptr_t)x) & 15) != 0) return OVO_E_UNSUPPORTED;
     MlpArgs g;
     g.x = x; g.rows = rows; g.ln_g = ln_g; g.ln_b = ln_b; g.eps = eps;
-    static int dbg_env = getenv("OVO_MLP_DBG") ? atoi(getenv("OVO_MLP_DBG")) : 0;                  // diagnosis (tools/mlp_stress.py)
-    if (ovo_knobs_dynamic()) dbg_env = getenv("OVO_MLP_DBG") ? atoi(getenv("OVO_MLP_DBG")) : 0;
-    g.dbg = dbg_env;
+    g.dbg = ovo_knob_int("OVO_MLP_DBG", 0);                                                        // diagnosis (tools/mlp_stress.py)
     g.dbg_out = nullptr;
-#ifdef OVO_GEMM_DEBUG        // the record buffer's ADDRESS comes from the environment: never in a production build
+#ifdef OVO_GEMM_DEBUG        // never in a production build; the record buffer's ADDRESS comes from the environment, afresh for every launch: not a knob (common.h)
     g.dbg_out = getenv("OVO_MLP_DBG_OUT") ? (unsigned *)strtoull(getenv("OVO_MLP_DBG_OUT"), nullptr, 0) : nullptr;
 #endif
     g.w1 = (const uint16_t *)w1; g.ldw1 = ldw1; g.b1 = b1; g.w2 = (const uint16_t *)w2; g.ldw2 = ldw2; g.b2 = b2;
@@ -494,8 +490,7 @@ int mlp_stream_launch(float *x, long long rows, int d, const float *ln_g, const 
     // GELU: the table in LDS (gemm_common.h: gelu_lut), as the two-launch path.  The packed polynomial (OVO_MLP_GELU_POLY=1) measured SLOWER here --
     // (786432, 112 -> 448): 408-444 us against 353-376 (profiles/r05a_mlp_stream_variants.txt): the kernel is bound by VALU issue beside the MFMAs,
     // and 9.5 packed instructions per value cost more of it than 7 plain ones + an LDS gather.  OVO_MLP_RB: variant number (measurement runs).
-    static int rb_env = getenv("OVO_MLP_RB") ? atoi(getenv("OVO_MLP_RB")) : 0, lut_env = getenv("OVO_MLP_GELU_POLY") == nullptr;
-    if (ovo_knobs_dynamic()) { rb_env = getenv("OVO_MLP_RB") ? atoi(getenv("OVO_MLP_RB")) : 0; lut_env = getenv("OVO_MLP_GELU_POLY") == nullptr; }
+    const int rb_env = ovo_knob_int("OVO_MLP_RB", 0), lut_env = !ovo_knob_set("OVO_MLP_GELU_POLY");
 #define GO(KK, DD, RB, RI, NTH, HCC, CODE)                                                                                             \
     if (d == DD && k1 == KK && (rb_env == 0 || rb_env == CODE))                                                                        \
         return lut_env ? launch_mlp<KK, DD, 4 * DD, RB, RI, NTH, false, HCC>(g, s) : launch_mlp<KK, DD, 4 * DD, RB, RI, NTH, true, HCC>(g, s);

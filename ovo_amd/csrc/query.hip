@@ -297,7 +297,7 @@ int launch_mfma(const void *F, int64_t n, int D, const float *T, int Q, const in
     const int64_t groups = (n + 15) / 16;
     int per_cu = (int)((160 * 1024) / lds);
     per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    if (const char *e = getenv("OVO_SIM_PER_CU")) { const int v = atoi(e); if (v >= 1 && v < per_cu) per_cu = v; }
+    if (const int v = ovo_knob_int("OVO_SIM_PER_CU", 0); v >= 1 && v < per_cu) per_cu = v;      // only ever lowers it
     int64_t grid = 256 * per_cu;
     if (grid * 4 > groups) grid = (groups + 3) / 4;
     k_similarity_mfma<DT><<<(int)(grid < 1 ? 1 : grid), 256, lds, s>>>(F, n, D, T, Q, cnt, siglip, se, bias, th, out_sim, cls, conf);
@@ -307,7 +307,7 @@ int launch_mfma(const void *F, int64_t n, int D, const float *T, int Q, const in
 template <int DT>
 int dispatch(const void *F, int64_t n, int D, const float *T, int Q, const int32_t *cnt, int siglip, float se, float bias, float th,
              float *out_sim, long long *cls, float *conf, hipStream_t s) {
-    if (D % 16 == 0 && (size_t)16 * D * sizeof(float) <= 160 * 1024 && !getenv("OVO_SIM_VALU"))
+    if (D % 16 == 0 && (size_t)16 * D * sizeof(float) <= 160 * 1024 && !ovo_knob_set("OVO_SIM_VALU"))
         return launch_mfma<DT>(F, n, D, T, Q, cnt, siglip, se, bias, th, out_sim, cls, conf, s);
     // smallest query chunk that covers Q in one pass (fewer wasted FMAs / LDS bytes), else 16-wide passes
     if (Q <= 4) return launch<DT, 4>(F, n, D, T, Q, cnt, siglip, se, bias, th, out_sim, cls, conf, s);

@@ -426,11 +426,7 @@ __global__ void __launch_bounds__(NTHREADS, NTHREADS == 512 ? 4 : 1) k_skinny_li
 }
 
 // GELU of the two upscaling kernels: the table in LDS (default) or the packed polynomial (OVO_SAM_GELU_POLY=1; measurement)
-int sam_gelu_lut() {
-    static int lut = getenv("OVO_SAM_GELU_POLY") == nullptr;
-    if (ovo_knobs_dynamic()) lut = getenv("OVO_SAM_GELU_POLY") == nullptr;
-    return lut;
-}
+int sam_gelu_lut() { return !ovo_knob_set("OVO_SAM_GELU_POLY"); }
 
 template <typename KernelT>
 int set_lds(KernelT k, size_t lds, const char *who) {

@@ -97,8 +97,7 @@ int ovo_vit_forward(const ovo_vit_config_t *cfg, const ovo_vit_weights_t *w, con
     // The LayerNorm fold: every layer carries folded weights, all four products of a block sit on the ping-pong kernel at this batch, and a row's partial
     // statistics fit the 16 slots (width <= 1024).  OVO_VIT_LNFOLD=0 keeps the LayerNorm kernels.
     namespace gd = ovo_gemm_detail;
-    static int fold_env = getenv("OVO_VIT_LNFOLD") ? atoi(getenv("OVO_VIT_LNFOLD")) : 1;
-    if (ovo_knobs_dynamic()) fold_env = getenv("OVO_VIT_LNFOLD") ? atoi(getenv("OVO_VIT_LNFOLD")) : 1;
+    const int fold_env = ovo_knob_int("OVO_VIT_LNFOLD", 1);
     const int parts = gd::gemm_fold_parts(D);
     bool fold = fold_env && c.layers > 0 && parts <= 16 && gd::gemm_fold_ok(M, D, D) && gd::gemm_fold_ok(M, D, c.mlp_dim) && gd::gemm_fold_ok(M, 3 * D, D) &&
                 gd::gemm_fold_ok(M, c.mlp_dim, D) && (c.act == 0 || c.act == 1) && (!c.use_rope || hd == 64);

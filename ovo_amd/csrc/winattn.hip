@@ -390,8 +390,7 @@ namespace ovo_gemm_detail {
 
 int win_attn_launch(const float *x, int B, int H, int W, int ws, int d, int d_out, int heads, int pool, const float *ln_g, const float *ln_b, float eps,
                     const void *qkv_w, long long ldw, const float *qkv_b, void *att, int ld_att, hipStream_t s) {
-    static const bool off_once = getenv("OVO_HIERA_NO_WINATTN") != nullptr;                // measurement / tests: the three-launch form
-    if (ovo_knobs_dynamic() ? getenv("OVO_HIERA_NO_WINATTN") != nullptr : off_once) return OVO_E_UNSUPPORTED;
+    if (ovo_knob_set("OVO_HIERA_NO_WINATTN")) return OVO_E_UNSUPPORTED;                    // measurement / tests: the three-launch form
     if ((((uintptr_t)x | (uintptr_t)qkv_w) & 15) != 0 || ((uintptr_t)att & 7) != 0 || ldw % 8 != 0 || ld_att < d_out || ld_att % 4 != 0) return OVO_E_UNSUPPORTED;
     if (d == c224::C2 && d_out == d && heads == 2 * NH && !pool && ws == 4 && H % 4 == 0 && W % 4 == 0 && ldw >= c224::C2) {     // stage 2: 4 x 4 windows
         const long long n_win = (long long)B * (H / 4) * (W / 4);

@@ -48,6 +48,23 @@ def test_product_never_imports_the_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, flags=re.M), f"{f} imports oracle"
 
 
+def test_knobs_are_read_through_the_one_helper():
+    """csrc/common.h implements the knob contract (read once per process, afresh per launch under OVO_KNOBS_DYNAMIC) in ovo_knob_*; nothing else in
+    csrc/ calls getenv but the exceptions common.h names: a file path read when profiling stops, and the buffer addresses of the OVO_GEMM_DEBUG builds."""
+    allowed = {("core.hip", "OVO_PROF_DUMP"), ("gemm8p.hip", "OVO_8P_STAMPS"), ("mlp_stream.hip", "OVO_MLP_DBG_OUT")}
+    csrc = os.path.join(ROOT, "ovo_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, f)).read()
+        if f == "common.h":
+            assert "ovo_knob_int" in text and "ovo_knob_set" in text and "ovo_knobs_dynamic" in text
+            continue
+        calls = len(re.findall(r"getenv\s*\(", text))
+        named = re.findall(r'getenv\s*\(\s*"(\w+)"\s*\)', text)
+        assert calls == len(named), f"{f}: getenv of something other than a literal name"
+        for name in named:
+            assert (f, name) in allowed, f"{f} reads {name} with getenv: use ovo_knob_* (csrc/common.h)"
+
+
 def test_cpu_tensors_are_rejected_loudly():
     import torch
     from ovo_amd import _lib

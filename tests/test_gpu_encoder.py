@@ -52,6 +52,52 @@ def test_gemm_vs_torch(m, n, k, dtype):
     torch.testing.assert_close(out, ref, atol=2e-4, rtol=2e-4)
 
 
+# a process of its own: one product, then OVO_GEMM_TILE=64x64 set in its own environment, then the product again; prints the kernel kinds the library's
+# profiler counted for each (csrc/common.h: 4..7 = the ring kernels' 128x128 / 128x64 / 64x128 / 64x64 tiles)
+_KNOB_CHILD = """
+import ctypes as C, os, sys
+sys.path.insert(0, sys.argv[1])
+import torch
+from ovo_amd import _lib as L
+lib = L.load()
+m, n, k = 1154, 3072, 1024
+a = torch.randn(m, k).to("cuda", torch.bfloat16)
+w = (torch.randn(n, k) * k ** -0.5).to("cuda", torch.bfloat16)
+out = torch.empty(m, n, device="cuda")
+def kinds():
+    g = L.Gemm()
+    g.A, g.lda, g.W, g.ldw, g.bias, g.C, g.ldc, g.add, g.ld_add = a.data_ptr(), k, w.data_ptr(), k, None, out.data_ptr(), n, None, 0
+    g.M, g.N, g.K, g.in_dtype, g.out_dtype, g.act, g.alpha = m, n, k, 2, 0, 0, 1.0
+    L.check(lib.ovo_profile_start())
+    L.check(lib.ovo_gemm(C.byref(g), L.stream()))
+    ms, work, cnt = (C.c_double * 9)(), (C.c_double * 9)(), (C.c_int64 * 9)()
+    L.check(lib.ovo_profile_stop(ms, work, cnt, 9))
+    return [i for i in range(9) for _ in range(cnt[i])]
+first = kinds()
+os.environ["OVO_GEMM_TILE"] = "64x64"
+print("KINDS", (first, kinds()))
+"""
+
+
+@pytest.mark.parametrize("dynamic", [False, True])
+def test_knobs_are_read_once_unless_dynamic(dynamic):
+    """The knob contract (csrc/common.h) seen from outside: a process WITHOUT OVO_KNOBS_DYNAMIC that changes OVO_GEMM_TILE after its first product keeps
+    the kernel it had; the same process with OVO_KNOBS_DYNAMIC=1 gets the forced 64 x 64 tile (profiler kind 7) on the second product."""
+    import ast
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if not k.startswith("OVO_")}
+    if dynamic:
+        env["OVO_KNOBS_DYNAMIC"] = "1"
+    r = subprocess.run([sys.executable, "-c", _KNOB_CHILD, ROOT], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    first, second = ast.literal_eval(r.stdout.split("KINDS", 1)[1].strip())
+    assert len(first) == 1 and first[0] != 7, first                 # one launch, and not the tile the knob will ask for
+    assert second == ([7] if dynamic else first)
+
+
 def test_gemm_epilogues_and_padding():
     g = torch.Generator().manual_seed(1)
     m, n, k = 577, 256, 128

@@ -103,42 +103,54 @@ def test_shared_identical_crops_do_not_change_results():
         assert (da is None and db is None) or torch.equal(torch.nan_to_num(da, nan=7.0), torch.nan_to_num(db, nan=7.0))
 
 
-@pytest.mark.parametrize("fused", [True, False])
-def test_incremental_dense_query_equals_full_requery(fused, monkeypatch):
-    """The resident dense class / confidence map, patched only for the rows a keyframe changed -- in one launch from the tracking pass's hit list
-    (`ovo_scatter_accum_query`, round 6) or as ovo_scatter_accum_touched -> ovo_similarity_rows --, against a full re-query of every row after
-    every keyframe: equal bit for bit, and the touched set is a small part of the map.  The hit list itself = the points with point_seg >= 0."""
+def _incremental_dense_run(fused: bool, monkeypatch):
+    """Five keyframes through the resident dense map in its one-launch (`fused`) or three-launch form; checks every keyframe against a full re-query and
+    the touched set against the matched points; returns the dense accumulators and counts after every keyframe."""
     from ovo_amd.pipeline import FramePipeline, synthetic_frames
     from ovo_amd.utils import clip_utils
-    if not fused:
+    if fused:                                                      # read when the pipeline is constructed: each construction gets its own setting
+        monkeypatch.delenv("OVO_NO_FUSED_SCATTER", raising=False)
+    else:
         monkeypatch.setenv("OVO_NO_FUSED_SCATTER", "1")
     pipe = FramePipeline(DEV, vit_card="tiny-pe", sam_card=None, n_map=60_000, n_text=7, scale=0.35, extra_capacity=200_000, track_th=40)
     assert pipe.incremental_query and (pipe.ovo.hit_shard is not None) == fused
     frames = synthetic_frames(5, DEV, scale=0.35, n_masks_grid=(3, 4), n_blobs=4)
     fractions, accs = [], []
     for f in frames:
+        parity = None if fused else pipe._touch_parity
         out = pipe.step(f)
         n = out["n_points"]
         _, cls, conf = clip_utils.similarity(pipe.acc[:n], pipe.texts, cnt=pipe.cnt[:n], want_sim=False, want_argmax=True)
         assert torch.equal(out["dense_cls"], cls) and torch.equal(out["dense_conf"], conf)
-        matched = torch.nonzero(pipe.ovo.last_point_seg >= 0).flatten()
+        seg = pipe.ovo.last_point_seg
+        matched = torch.nonzero(seg >= 0).flatten()
         if fused:
             hits = pipe.ovo.last_hits
             touched = int(hits[-4].item())
             assert torch.equal(torch.sort(hits[:touched].long()).values, matched)          # every matched point, once, in any order
-        else:
-            touched = int(pipe.n_touched[pipe._touch_parity ^ 1].item())
-            assert touched == matched.numel() or touched <= n                               # every matched point of a kept mask, once
+        else:                                                      # (a keyframe without descriptors launches no scatter and leaves the counters alone)
+            touched = int(pipe.n_touched[pipe._touch_parity ^ 1].item()) if pipe._touch_parity != parity else 0
+            kept = torch.tensor(pipe.ovo.last_mask_rows, device=seg.device) >= 0
+            assert touched <= matched.numel()
+            assert touched == int(kept[seg[matched].long()].sum().item())                  # every matched point of a kept mask, once
         fractions.append(touched / n)
         accs.append((pipe.acc[:n].clone(), pipe.cnt[:n].clone()))
     assert (out["dense_cls"] >= 0).any() and max(fractions) > 0 and max(fractions) < 0.6
     return accs
 
 
+@pytest.mark.parametrize("fused", [True, False])
+def test_incremental_dense_query_equals_full_requery(fused, monkeypatch):
+    """The resident dense class / confidence map, patched only for the rows a keyframe changed -- in one launch from the tracking pass's hit list
+    (`ovo_scatter_accum_query`, round 6) or as ovo_scatter_accum_touched -> ovo_similarity_rows --, against a full re-query of every row after
+    every keyframe: equal bit for bit, and the touched set is a small part of the map.  The hit list itself = the points with point_seg >= 0."""
+    _incremental_dense_run(fused, monkeypatch)
+
+
 def test_fused_scatter_query_accumulators_equal_the_three_launch_path(monkeypatch):
     """Same frames through both forms: the dense accumulators and counts are identical after every keyframe."""
-    a = test_incremental_dense_query_equals_full_requery(True, monkeypatch)
-    b = test_incremental_dense_query_equals_full_requery(False, monkeypatch)
+    a = _incremental_dense_run(True, monkeypatch)
+    b = _incremental_dense_run(False, monkeypatch)
     for (xa, ca), (xb, cb) in zip(a, b):
         assert torch.equal(xa, xb) and torch.equal(ca, cb)
     assert float(a[-1][0].abs().sum()) > 0
