@@ -236,7 +236,7 @@ int ovo_mask_area(const uint8_t *masks, int64_t pixels, const int32_t *rows, int
 /* C[M,N] = act(alpha * A[M,K] . W[N,K]^T + bias[N]) + add[M,N]      (nn.Linear layout: W is [out, in])
  *   in_dtype : 1 = f16, 2 = bf16 (A and W);  out_dtype: 0 = f32, 1 = f16, 2 = bf16
  *   act      : 0 none, 1 GELU (erf), 2 QuickGELU x*sigmoid(1.702x) (open_clip "-qg" cards), 3 ReLU, 4 sigmoid (SAM2 decoder),
- *              5 tanh-GELU (SigLIP towers)
+ *              5 tanh-GELU (SigLIP towers), 6 leaky ReLU (slope 0.01), 7 SiLU (ABI v14: the weights predictor's MLP, clips_merging.py:6-11)
  *   add      : optional f32 [M,N] (residual stream / position embedding); may alias C when out_dtype = 0
  *   K % 32 == 0, N % 4 == 0, lda/ldw multiples of 8 elements, 16-byte aligned bases. */
 typedef struct {
@@ -348,6 +348,24 @@ typedef struct {
     int32_t causal;                                   /* 1: key j is visible to query i only if j <= i (text towers); ABI v2 */
 } ovo_attention_t;
 int ovo_attention(const ovo_attention_t *a, ovo_stream_t stream);
+
+/* ---- the learned crop-merging weights predictor (ABI v14; reference: ovo/entities/clips_merging.py, selected by clip.embed_type "learned",
+ * clip_generator.py:19-31 and :154) ---- */
+/* ovo_gemm for FEW rows (clips_merging.py:13-24 `block_mlp`, applied at :48 to one row per mask: 3456 -> 13824 -> 4 x 13824 -> 3456 at base size):
+ * the product is one read of W, bound by HBM, so every byte of W is fetched once per 64-row block of A, by one wave, through LDS-DMA rings, and K is
+ * split over the waves of a workgroup whose partial sums are added in a FIXED order (bit-identical results from launch to launch).  M is padded to the
+ * MFMA's 16 rows inside the kernel; M > 64 runs as row blocks of 64 (W is then read once per block: hand large M to ovo_gemm).
+ * bf16 operands, out_dtype 0 / 2, act in {0, 3 ReLU, 4 sigmoid, 6 leaky ReLU, 7 SiLU}, K % 64 == 0, N % 16 == 0; anything else returns
+ * OVO_E_UNSUPPORTED with nothing launched (the caller runs ovo_gemm). */
+int ovo_gemm_fewrows(const ovo_gemm_t *g, ovo_stream_t stream);
+/* Self-attention over T <= 8 tokens (nn.TransformerEncoderLayer's self_attn inside clips_merging.py:29-36, run at :47 over the three clips of a mask:
+ * T = 3, head_dim 144 at base size -- ovo_attention stops at head_dim 128): qkv bf16 [B, T, 3, H, hd] (the packed in_proj product, as ovo_attention takes
+ * it) -> out bf16 [B, T, H hd] = softmax(q k^T scale) v per (batch, head); fp32 scores and softmax.  hd % 8 == 0, else OVO_E_UNSUPPORTED. */
+int ovo_attention_short(const void *qkv, int B, int T, int H, int hd, float scale, void *out, ovo_stream_t stream);
+/* The tail of WeightsPredictorMerger.forward (clips_merging.py:49-55) in one pass: softmax over the three clips of logits f32 [B, 3 D] read as [B, 3, D]
+ * (per channel; per_row = 0) or of logits [B, 3] (per_row = 1, the MLP's o_dim == 3), rows ld_logits apart; out f32 [B, D] =
+ * normalize(sum_k w_k clips[B, k, D]) with F.normalize's eps 1e-12. */
+int ovo_merge_clips(const float *logits, int64_t ld_logits, int per_row, const float *clips, int B, int D, float *out, ovo_stream_t stream);
 
 /* y = LayerNorm(x) * gamma + beta over the last dim (biased variance, eps inside the sqrt).
  * x f32 rows at x + r*x_stride; y rows at y + r*y_stride, out_dtype 0 = f32, 2 = bf16.  d % 4 == 0. */

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "lib", "libovo_hip.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 E_UNSUPPORTED = -3          # OVO_E_UNSUPPORTED: the entry point does not cover this shape; the caller takes its general path
 
 
@@ -188,6 +188,9 @@ _SIGNATURES = {
     "ovo_gemm_f32a": (_I32, [C.POINTER(Gemm), C.POINTER(Window), _P, C.c_int, _P, _P, C.c_float, C.c_int, C.c_int, _P]),
     "ovo_decode_best": (_I32, [_P, _I64, _F32, _P, _P, _P]),
     "ovo_attention": (_I32, [C.POINTER(Attention), _P]),
+    "ovo_gemm_fewrows": (_I32, [C.POINTER(Gemm), _P]),
+    "ovo_attention_short": (_I32, [_P, _I32, _I32, _I32, _I32, _F32, _P, _P]),
+    "ovo_merge_clips": (_I32, [_P, _I64, _I32, _P, _I32, _I32, _P, _P]),
     "ovo_layernorm": (_I32, [_P, _I64, _I64, _I32, _P, _P, _F32, _P, _I64, _I32, _P]),
     "ovo_vit_embed": (_I32, [_P, _P, _I32, _P, _I32, _I32, _I32, _P, _P, _F32, _P, _P]),
     "ovo_im2col": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P]),

@@ -175,6 +175,12 @@ __device__ __forceinline__ void act4(float *v, int act, const float2 *lut = null
             const float u = 1.5957691216057308f * fmaf(0.044715f * v[r] * v[r], v[r], v[r]);
             v[r] = v[r] / (1.0f + __expf(-u));
         }
+    } else if (act == 6) {                                       // leaky ReLU, slope 0.01 (the weights predictor's MLP, clips_merging.py:7)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.01f * v[r];
+    } else if (act == 7) {                                       // SiLU (clips_merging.py:9)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = v[r] / (1.0f + __expf(-v[r]));
     }
 }
 

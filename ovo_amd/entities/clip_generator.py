@@ -8,6 +8,8 @@ methods).  The image tower is `ovo_amd.encoders.vit.HipViT`; reg
 Offline limits, stated rather than hidden:
   * no checkpoints can be downloaded -> weights are loaded from `config["weights_path"]` (an open_clip-style
     `visual.*` state dict) when given, else seeded random weights of the same architecture;
+  * embed_type "learned": the weights predictor (clips_merging.py) is built from `config["weights_predictor_path"]/hparams.yaml`
+    and loads `model.pt` from there when it exists, else seeded random weights of that architecture;
   * the text tower + BPE tokenizer are a "next" row: `text_encoder` may be injected
     (callable: list[str] -> [n, D] tensor); the default is a deterministic hash embedding so that the
     query path (template ensembling, normalisation, similarity, argmax) runs end to end.
@@ -46,9 +48,16 @@ class CLIPGenerator:
         self.device = device
         self.embed_type = config.get("embed_type", "vanilla")
         self.mask_res = config.get("mask_res", 384)
+        self.clips_fusion_model = None
         if self.embed_type == "learned":
-            raise NotImplementedError("embed_type 'learned' needs the weights-predictor checkpoint (data/input/ReadMe.md:10), "
-                                      "which is not available offline; out of scope (SURVEY.md §2 row 17)")
+            # clip_generator.py:19-31: hparams.yaml + model.pt under weights_predictor_path; without model.pt: seeded random weights
+            import yaml
+            from .clips_merging import WeightsPredictorMerger
+            with open(os.path.join(config["weights_predictor_path"], "hparams.yaml"), "r") as f:
+                model_config = yaml.safe_load(f)
+            pt_path = os.path.join(config["weights_predictor_path"], "model.pt")
+            state = torch.load(pt_path, map_location="cpu") if os.path.exists(pt_path) else None
+            self.clips_fusion_model = WeightsPredictorMerger(model_config["model"], state, device=device, seed=config.get("seed", 0)).eval()
         self.w_masked = config.get("w_masked", 0.4418)
         self.w_global = config.get("w_global", 0.1)
         self.model_card = config.get("model_card", "SigLIP-384")
@@ -136,8 +145,12 @@ class CLIPGenerator:
         n = seg.shape[0]
         clip_g = norm(self.encode_image(img[None] / 255.0), p=2, dim=-1)
         both = norm(self.encode_image(torch.cat([seg[:, :3], seg[:, 3:]], dim=0)), p=2, dim=-1)
-        if return_all:
-            return torch.cat([clip_g.repeat(n, 1)[:, None], both[:n][:, None], both[n:][:, None]], dim=1)
+        if return_all or self.clips_fusion_model is not None:
+            triple = torch.cat([clip_g.repeat(n, 1)[:, None], both[:n][:, None], both[n:][:, None]], dim=1)
+            if return_all:
+                return triple
+            out = self.clips_fusion_model(triple)                                    # clip_generator.py:29, :154
+            return out.half() if self.config.get("use_half", False) else out         # :156-157 (the hand-weighted modes here return f32 as before)
         return clip_utils.fuse_clips(clip_g.repeat(n, 1), both[:n], both[n:], self.embed_type, self.w_masked, self.w_global)
 
     # ------------------------------------------------------------------ text side
