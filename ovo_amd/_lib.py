@@ -292,6 +292,50 @@ def dev(t: torch.Tensor, dtype: torch.dtype, name: str = "tensor") -> torch.Tens
     return t
 
 
+def gemm_desc(a: Optional[torch.Tensor], w: torch.Tensor, out: Optional[torch.Tensor], *, bias: Optional[torch.Tensor] = None,
+              add: Optional[torch.Tensor] = None, act: int = 0, alpha: float = 1.0, rows: Optional[int] = None, lda: Optional[int] = None,
+              a_off: int = 0, ldc: Optional[int] = None, c_off: int = 0, out_dtype: Optional[torch.dtype] = None) -> Gemm:
+    """ovo_gemm_t of out[M, N] = act(alpha * a[M, K] . w[N, K]^T + bias) + add with every field taken from the tensors: M from `a`, (N, K) from `w`, leading
+    dimensions from the row strides, dtype codes from the dtypes; `bias` / `add` None = NULL.  Shapes, dtypes and devices that do not fit raise here, before
+    anything crosses the ABI (not `is_cuda`: that is `dev()`'s and the library's business).  Overrides, in elements:
+      rows / lda / a_off   `a` read as `rows` rows, `lda` apart, from element `a_off` on (every T-th row of a matrix); a's own shape is then not checked
+      ldc / c_off          the result written `ldc` apart from element `c_off` of `out` on (a column block, spatial rows); out's own shape is then not checked
+      out=None, out_dtype  no C (ovo_gemm_argmax keeping only the winners);   a=None, rows   no A (ovo_gemm_f32a is handed f32 rows beside the descriptor)"""
+    if (a is None and rows is None) or (out is None and out_dtype is None):
+        raise OvoHipError("gemm_desc: a=None needs rows=, out=None needs out_dtype=")
+    (n, k), m, out_dtype = w.shape, (a.shape[0] if rows is None else rows), (out_dtype if out is None else out.dtype)
+    if w.dtype not in DTYPE_CODE or out_dtype not in DTYPE_CODE:
+        raise OvoHipError(f"gemm_desc: no dtype code for {w.dtype} -> {out_dtype}")
+    if a is not None and (a.dtype != w.dtype or (rows is None and lda is None and not a_off and a.shape[1] != k)):
+        raise OvoHipError(f"gemm_desc: a {tuple(a.shape)} {a.dtype} does not fit w {tuple(w.shape)} {w.dtype}")
+    if out is not None and ldc is None and not c_off and tuple(out.shape) != (m, n):
+        raise OvoHipError(f"gemm_desc: out is {tuple(out.shape)}, the product is {(m, n)}")
+    for t in (a, out, bias, add):
+        if t is not None and t.device != w.device:
+            raise OvoHipError(f"gemm_desc: operands on {t.device} and {w.device}")
+    lda, ldc = lda if lda is not None else (k if a is None else a.stride(0)), ldc if ldc is not None else (n if out is None else out.stride(0))
+    return Gemm(None if a is None else a.data_ptr() + a_off * a.element_size(), lda, w.data_ptr(), w.stride(0), None if bias is None else bias.data_ptr(),
+                None if out is None else out.data_ptr() + c_off * out.element_size(), ldc, None if add is None else add.data_ptr(),
+                0 if add is None else add.stride(0), m, n, k, DTYPE_CODE[w.dtype], DTYPE_CODE[out_dtype], act, alpha)
+
+
+def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, **kw) -> torch.Tensor:
+    """`ovo_gemm` on `gemm_desc(a, w, out, **kw)`; returns `out`."""
+    check(load().ovo_gemm(C.byref(gemm_desc(a, w, out, **kw)), stream()))
+    return out
+
+
+def attention_packed(qkv: torch.Tensor, out: torch.Tensor, B: int, H: int, Tq: int, Tk: int, hd: int, *, T: Optional[int] = None, scale: float,
+                     causal: int = 0) -> Attention:
+    """ovo_attention_t over a packed QKV projection: q | k | v at element offsets 0, D, 2 D (D = H hd, heads contiguous inside each) of the 3 D columns of
+    `qkv` [B, T, 3 D], the first Tq (queries) / Tk (keys) of a batch's T rows taking part; `out` [B, Tq, D].  The flat [B T, 3 D] form has to name T."""
+    T, D = (qkv.shape[1] if T is None and qkv.dim() > 2 else T), H * hd
+    if T is None or T < max(Tq, Tk) or qkv.numel() != B * T * 3 * D or out.numel() != B * Tq * D:
+        raise OvoHipError(f"attention_packed: qkv {tuple(qkv.shape)} / out {tuple(out.shape)} do not hold B {B}, T {T}, H {H}, Tq {Tq}, Tk {Tk}, hd {hd}")
+    base, es, sb = qkv.data_ptr(), qkv.element_size(), T * 3 * D
+    return Attention(base, base + D * es, base + 2 * D * es, out.data_ptr(), sb, hd, 3 * D, sb, hd, 3 * D, sb, hd, 3 * D, Tq * D, hd, D, B, H, Tq, Tk, hd, scale, causal)
+
+
 def gather_rows(src: torch.Tensor, rows) -> torch.Tensor:
     """src[rows] along dim 0 through `ovo_gather_rows` (torch's index_select picks size-dependent kernel variants whose
     first use lazily loads a code object: a 100+ ms stall in the middle of a sequence on ROCm)."""

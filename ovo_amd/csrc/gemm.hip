@@ -472,12 +472,8 @@ static int gemm_entry(const ovo_gemm_t *p, ovo_stream_t stream, const GemmOpts &
     OVO_REQUIRE(p->ldc % 4 == 0 && ((uintptr_t)p->C & 15) == 0, "C rows must be 16-byte aligned");
     OVO_REQUIRE(!p->add || (p->ld_add % 4 == 0 && ((uintptr_t)p->add & 15) == 0), "add rows must be 16-byte aligned");
     OVO_REQUIRE(!p->bias || ((uintptr_t)p->bias & 15) == 0, "bias must be 16-byte aligned");
-    GemmArgs g = {};                                             // every field rests at zero but the divisors below
-    g.A = (const char *)p->A; g.lda = p->lda; g.W = (const char *)p->W; g.ldw = p->ldw; g.bias = p->bias;
-    g.C = p->C; g.ldc = p->ldc; g.add = p->add; g.ld_add = p->ld_add;
-    g.M = p->M; g.N = p->N; g.K = p->K; g.out_dtype = p->out_dtype; g.act = p->act; g.alpha = p->alpha;
+    GemmArgs g = gemm_args_from(*p);
     g.best = best; g.store = store; g.n_valid = n_valid; g.add_rows = (int)add_rows;
-    g.rope_T = 1; g.rope_hd = 4; g.win_ww = g.win_wh = g.win_nww = g.win_nwin = 1;
     if (win) {
         OVO_REQUIRE(win->B > 0 && win->H > 0 && win->W > 0 && win->wh > 0 && win->ww > 0, "bad window descriptor");
         const int nwh = (win->H + win->wh - 1) / win->wh, nww = (win->W + win->ww - 1) / win->ww;

@@ -61,6 +61,16 @@ struct GemmArgs {
     unsigned long long *stamps;   // tools/ only (OVO_8P_STAMPS = address of u64[tiles][4]): s_memrealtime at start / K-loop / epilogue / end
 };
 
+// The plain product of a descriptor; every other field rests at zero but the divisors of the rope / window index arithmetic.
+inline GemmArgs gemm_args_from(const ovo_gemm_t &p) {
+    GemmArgs g = {};
+    g.A = (const char *)p.A; g.lda = p.lda; g.W = (const char *)p.W; g.ldw = p.ldw; g.bias = p.bias;
+    g.C = p.C; g.ldc = p.ldc; g.add = p.add; g.ld_add = p.ld_add;
+    g.M = p.M; g.N = p.N; g.K = p.K; g.out_dtype = p.out_dtype; g.act = p.act; g.alpha = p.alpha;
+    g.rope_T = 1; g.rope_hd = 4; g.win_ww = g.win_wh = g.win_nww = g.win_nwin = 1;
+    return g;
+}
+
 // ovo_gemm_unwindow: product row m is a token in window-major order (windows of wh x ww tiling an H x W grid that is padded up to
 // whole windows); its C / add row is the token's spatial index (b*H + y)*W + x, or -1 for a padding position (row dropped).
 __device__ __forceinline__ long long row_dest(const GemmArgs &g, int m) {

@@ -244,17 +244,21 @@ int launch_stream(const GemmArgs &g, hipStream_t s) {
 
 namespace ovo_gemm_detail {
 
+// Column groups: the widest of 256 / 224 / 112 / 64 / 32 that divides N (hiera_b+'s 112-multiples, powers of two; 0 = none does); 288 / 144 for hiera_l's stage 1 (K = 192: 144 channels padded)
+static int stream_group_width(int N, int K) {
+    int ng = 0;
+    for (int c : {256, 224, 112, 64, 32})
+        if (N % c == 0) { ng = c; break; }
+    if (K == 192 && N % 144 == 0 && N % 256 != 0) ng = N % 288 == 0 ? 288 : 144;
+    if (K == 128 && N == 336) ng = 336;                              // Hiera stage-1 QKV: one group (86 KB of weights), A read once
+    return ng;
+}
+
 // Returns OVO_E_UNSUPPORTED when the shape has no instantiation (the caller then takes a tiled kernel).
 int gemm_stream_launch(const GemmArgs &g, int in_dtype, hipStream_t s) {
     if (g.best || g.rope_cos || in_dtype != 2 || g.act > 1 || (g.act == 1 && knob_gelu_poly())) return OVO_E_UNSUPPORTED;
     if (g.M < 16384 || ((uintptr_t)g.C & 15) != 0 || g.ldc % 4 != 0) return OVO_E_UNSUPPORTED;
-    // column groups: the widest of 256 / 224 / 112 / 64 / 32 that divides N (hiera_b+'s 112-multiples, powers of two); 288 / 144 for
-    // hiera_l's stage 1 (K = 192: 144 channels padded)
-    int ng = 0;
-    for (int c : {256, 224, 112, 64, 32})
-        if (g.N % c == 0) { ng = c; break; }
-    if (g.K == 192 && g.N % 144 == 0 && g.N % 256 != 0) ng = g.N % 288 == 0 ? 288 : 144;
-    if (g.K == 128 && g.N == 336) ng = 336;                          // Hiera stage-1 QKV: one group (86 KB of weights), A read once
+    const int ng = stream_group_width(g.N, g.K);
     // measured (tools/gemm_bench.py, profiles/r02c_gemm_stream.txt): no gain over the tiled kernels with 6+ column groups (A re-read per group)
     // or for the narrow f32-residual product (524288, 112, 128), which both forms run at the HBM rate of its in-place C traffic
     if (g.N / (ng ? ng : 1) >= 6 || (g.K == 128 && g.N == 112 && g.out_dtype == 0)) return OVO_E_UNSUPPORTED;
@@ -286,12 +290,8 @@ int gemm_f32a_stream(const ovo_gemm_t *p, const ovo_window_t *win, const float *
         return OVO_E_UNSUPPORTED;
     if (p->ldw % 8 != 0 || ((uintptr_t)p->W & 15) != 0 || (p->bias && ((uintptr_t)p->bias & 15) != 0) || p->add || p->N % 4 != 0 || p->K % 32 != 0 || p->act > 1)
         return OVO_E_UNSUPPORTED;
-    GemmArgs g = {};
-    g.A = nullptr; g.lda = 0; g.W = (const char *)p->W; g.ldw = p->ldw; g.bias = p->bias;
-    g.C = p->C; g.ldc = p->ldc; g.add = nullptr; g.ld_add = 0;
-    g.M = p->M; g.N = p->N; g.K = p->K; g.out_dtype = p->out_dtype; g.act = p->act; g.alpha = p->alpha;
-    g.store = 1; g.rope_T = 1; g.rope_hd = 4;
-    g.win_per = 0; g.win_ww = g.win_wh = g.win_nww = g.win_nwin = 1;
+    GemmArgs g = gemm_args_from(*p);
+    g.A = nullptr; g.lda = 0; g.add = nullptr; g.ld_add = 0; g.store = 1;      // A is `x`; `add` was refused above
     if (win) {
         const int nwh = (win->H + win->wh - 1) / win->wh, nww = (win->W + win->ww - 1) / win->ww;
         if ((long long)win->B * nwh * nww * win->wh * win->ww != p->M) return OVO_E_UNSUPPORTED;
@@ -308,11 +308,7 @@ int gemm_f32a_stream(const ovo_gemm_t *p, const ovo_window_t *win, const float *
         if (!win || p->out_dtype != 2 || win->H % win->wh != 0 || win->W % win->ww != 0 || win->wh % 2 != 0 || (win->ww != 2 && win->ww != 4 && win->ww != 8) ||
             p->M % 16 != 0 || qpool_cols <= 0 || qpool_cols % 4 != 0 || ((uintptr_t)qpool_out & 7) != 0 || pool2x2)
             return OVO_E_UNSUPPORTED;
-        int ng = 0;                                                  // (the column-group width gemm_stream_launch will pick)
-        for (int c : {256, 224, 112, 64, 32})
-            if (p->N % c == 0) { ng = c; break; }
-        if (p->K == 192 && p->N % 144 == 0 && p->N % 256 != 0) ng = p->N % 288 == 0 ? 288 : 144;
-        if (p->K == 128 && p->N == 336) ng = 336;
+        const int ng = stream_group_width(p->N, p->K);
         if (!ng || qpool_cols % ng != 0) return OVO_E_UNSUPPORTED;
         g.qpool_out = qpool_out; g.qpool_cols = qpool_cols;
     }

@@ -264,10 +264,7 @@ extern "C" int ovo_gemm_fewrows(const ovo_gemm_t *p, ovo_stream_t stream) {
     if (p->in_dtype != 2 || (p->out_dtype != 0 && p->out_dtype != 2) || !act_ok || p->K % FEW_KC != 0 || p->N % 16 != 0 || p->lda < p->K || p->ldw < p->K ||
         (p->M + 63) / 64 > 65535)
         return OVO_E_UNSUPPORTED;
-    GemmArgs g = {};
-    g.A = (const char *)p->A; g.lda = p->lda; g.W = (const char *)p->W; g.ldw = p->ldw; g.bias = p->bias;
-    g.C = p->C; g.ldc = p->ldc; g.add = p->add; g.ld_add = p->ld_add;
-    g.M = p->M; g.N = p->N; g.K = p->K; g.out_dtype = p->out_dtype; g.act = p->act; g.alpha = p->alpha;
+    const GemmArgs g = gemm_args_from(*p);
     const int mt = p->M <= 16 ? 1 : p->M <= 32 ? 2 : 4;
     const int ntw = (p->N % 32 == 0 && p->N / 32 >= 256) ? 2 : 1;                 // narrow products keep 16-column groups: more workgroups
     // waves per workgroup (the K-split) and ring depth: the deepest ring that keeps two workgroups on a CU, or one workgroup of 8 waves when the grid

@@ -229,17 +229,9 @@ class HipSamDecoder:
               out: Optional[torch.Tensor] = None, rows: Optional[int] = None, lda: Optional[int] = None, ldc: Optional[int] = None,
               a_off: int = 0, c_off: int = 0, bias: bool = True, add_rows: int = 0) -> torch.Tensor:
         w = self.w[wname + ".w"]
-        m = a.shape[0] if rows is None else rows
-        n, k = w.shape
         if out is None:
-            out = torch.empty((m, n), dtype=out_dtype, device=a.device)
-        g = L.Gemm()
-        g.A, g.lda, g.W, g.ldw = a.data_ptr() + a_off * a.element_size(), (a.stride(0) if lda is None else lda), w.data_ptr(), k
-        g.bias = self.w[wname + ".b"].data_ptr() if bias else None
-        g.C, g.ldc = out.data_ptr() + c_off * out.element_size(), (out.stride(0) if ldc is None else ldc)
-        g.add, g.ld_add = (add.data_ptr(), add.stride(0)) if add is not None else (None, 0)
-        g.M, g.N, g.K = m, n, k
-        g.in_dtype, g.out_dtype, g.act, g.alpha = 2, L.DTYPE_CODE[out.dtype], act, 1.0
+            out = torch.empty((a.shape[0] if rows is None else rows, w.shape[0]), dtype=out_dtype, device=a.device)
+        g = L.gemm_desc(a, w, out, bias=self.w[wname + ".b"] if bias else None, add=add, act=act, rows=rows, lda=lda, a_off=a_off, ldc=ldc, c_off=c_off)
         if add_rows:                                              # add[m % add_rows]: a per-pixel constant shared by every prompt
             L.check(L.load().ovo_gemm_periodic(C.byref(g), add_rows, L.stream()))
         else:

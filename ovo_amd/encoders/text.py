@@ -118,18 +118,9 @@ class HipTextEncoder:
 
     def _gemm(self, a, wname, out_dtype, act=0, add=None, out=None, bias=True):
         w = self.w[wname + ".w"]
-        m, (n, k) = a.shape[0], w.shape
         if out is None:
-            out = torch.empty((m, n), dtype=out_dtype, device=a.device)
-        g = L.Gemm()
-        g.A, g.lda, g.W, g.ldw = a.data_ptr(), a.stride(0), w.data_ptr(), k
-        g.bias = self.w[wname + ".b"].data_ptr() if bias else None
-        g.C, g.ldc = out.data_ptr(), out.stride(0)
-        g.add, g.ld_add = (add.data_ptr(), add.stride(0)) if add is not None else (None, 0)
-        g.M, g.N, g.K = m, n, k
-        g.in_dtype, g.out_dtype, g.act, g.alpha = 2, L.DTYPE_CODE[out.dtype], act, 1.0
-        L.check(L.load().ovo_gemm(C.byref(g), L.stream()))
-        return out
+            out = torch.empty((a.shape[0], w.shape[0]), dtype=out_dtype, device=a.device)
+        return L.gemm(a, w, out, bias=self.w[wname + ".b"] if bias else None, add=add, act=act)
 
     @torch.no_grad()
     def encode_tokens(self, tokens: torch.Tensor) -> torch.Tensor:
@@ -156,13 +147,7 @@ class HipTextEncoder:
             p = f"transformer.resblocks.{i}."
             rows(p + "ln_1", y16=h16)
             qkv = self._gemm(h16, p + "qkv", bf)                                       # [R, 3w] = (q | k | v), heads contiguous inside each
-            a = L.Attention()
-            a.q, a.k, a.v, a.o = qkv.data_ptr(), qkv.data_ptr() + 2 * w, qkv.data_ptr() + 4 * w, att.data_ptr()
-            a.q_sb = a.k_sb = a.v_sb = t * 3 * w
-            a.q_sh = a.k_sh = a.v_sh = hd
-            a.q_st = a.k_st = a.v_st = 3 * w
-            a.o_sb, a.o_sh, a.o_st = t * w, hd, w
-            a.B, a.H, a.Tq, a.Tk, a.hd, a.scale, a.causal = b, H, t, t, hd, (0.0 if self.q_prescaled else hd ** -0.5), int(spec.causal)
+            a = L.attention_packed(qkv, att, b, H, t, t, hd, T=t, scale=(0.0 if self.q_prescaled else hd ** -0.5), causal=int(spec.causal))
             L.check(lib.ovo_attention(C.byref(a), L.stream()))
             self._gemm(att, p + "out", f32, add=x, out=x)
             rows(p + "ln_2", y16=h16)

@@ -81,23 +81,17 @@ class _Linear:
 def _gemm(a: torch.Tensor, lin: _Linear, out_dtype: torch.dtype, act: int = 0, add: Optional[torch.Tensor] = None, fewrows: bool = False,
           routes: Optional[Dict[str, int]] = None) -> torch.Tensor:
     """One linear layer; `routes` counts the entry that actually ran it (ovo_gemm_fewrows declines with OVO_E_UNSUPPORTED, nothing launched)."""
-    m = a.shape[0]
-    out = torch.empty(m, lin.n_pad, dtype=out_dtype, device=a.device)
-    g = L.Gemm()
-    g.A, g.lda, g.W, g.ldw, g.bias = a.data_ptr(), a.stride(0), lin.w.data_ptr(), lin.k, lin.b.data_ptr()
-    g.C, g.ldc = out.data_ptr(), lin.n_pad
-    g.add, g.ld_add = (add.data_ptr(), add.stride(0)) if add is not None else (None, 0)
-    g.M, g.N, g.K = m, lin.n_pad, lin.k
-    g.in_dtype, g.out_dtype, g.act, g.alpha = 2, L.DTYPE_CODE[out_dtype], act, 1.0
+    out = torch.empty(a.shape[0], lin.n_pad, dtype=out_dtype, device=a.device)
+    g = L.gemm_desc(a, lin.w, out, bias=lin.b, add=add, act=act)
     lib = L.load()
     if fewrows:
-        rc = lib.ovo_gemm_fewrows(g, L.stream())
+        rc = lib.ovo_gemm_fewrows(L.C.byref(g), L.stream())
         if rc != L.E_UNSUPPORTED:
             L.check(rc)
             if routes is not None:
                 routes["fewrows"] += 1
             return out
-    L.check(lib.ovo_gemm(g, L.stream()))
+    L.check(lib.ovo_gemm(L.C.byref(g), L.stream()))
     if routes is not None:
         routes["gemm"] += 1
     return out

@@ -25,18 +25,6 @@ from .. import _lib as L
 from ..encoders.vit import HipViT
 
 
-def _gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor) -> torch.Tensor:
-    """out f32[M, N] = a bf16[M, K] @ w bf16[N, K]^T + bias."""
-    g = L.Gemm()
-    g.A, g.lda, g.W, g.ldw = a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0)
-    g.bias = bias.data_ptr() if bias is not None else None
-    g.C, g.ldc, g.add, g.ld_add = out.data_ptr(), out.stride(0), None, 0
-    g.M, g.N, g.K = a.shape[0], w.shape[0], a.shape[1]
-    g.in_dtype, g.out_dtype, g.act, g.alpha = 2, 0, 0, 1.0
-    L.check(L.load().ovo_gemm(L.C.byref(g), L.stream()))
-    return out
-
-
 class PETextRegion(torch.nn.Module):
     def __init__(self, model: HipViT, model_card: str = "PE-Core-L14-336", preprocess=None,
                  resize_method: str = "multi_resolution", remove_global_patch: bool = True,
@@ -151,10 +139,10 @@ class PETextRegion(torch.nn.Module):
             x_t[:, :p * p] = tok[0, t0:].t().to(torch.bfloat16)
         if self.remove_global_patch and n > 0:
             weights, cnt = self._remove_global_patch(x_t, weights, cnt, nh * nw * p * p if self.resize_method == "multi_resolution" else p * p)
-        sums = _gemm(weights, x_t, None, torch.empty((n, d), dtype=torch.float32, device=tok.device))
+        sums = L.gemm(weights, x_t, torch.empty((n, d), dtype=torch.float32, device=tok.device))
         mean = torch.empty((n, d), dtype=torch.bfloat16, device=tok.device)
         L.check(lib.ovo_scale_rows_bf16(L.ptr(sums), L.ptr(cnt), n, d, L.ptr(mean), L.stream()))
-        out = _gemm(mean, self._fold_w, self._fold_b, torch.empty((n, self.out_dim), dtype=torch.float32, device=tok.device))
+        out = L.gemm(mean, self._fold_w, torch.empty((n, self.out_dim), dtype=torch.float32, device=tok.device), bias=self._fold_b)
         if not self.project_and_normalize:
             return out
         L.check(lib.ovo_l2_normalize_rows(L.ptr(out), n, self.out_dim, L.ptr(out), L.stream()))
@@ -169,10 +157,10 @@ class PETextRegion(torch.nn.Module):
         u_t = torch.empty_like(x_t)
         u = torch.empty((gpad, d), dtype=torch.bfloat16, device=x_t.device)
         L.check(lib.ovo_unit_tokens(L.ptr(x_t), d, g, gpad, L.ptr(u_t), L.ptr(u), L.stream()))
-        sums = _gemm(weights, u_t, None, torch.empty((n, d), dtype=torch.float32, device=x_t.device))
+        sums = L.gemm(weights, u_t, torch.empty((n, d), dtype=torch.float32, device=x_t.device))
         mean = torch.empty((n, d), dtype=torch.bfloat16, device=x_t.device)
         L.check(lib.ovo_scale_rows_bf16(L.ptr(sums), L.ptr(cnt), n, d, L.ptr(mean), L.stream()))
-        r_t = _gemm(mean, u, None, torch.empty((n, gpad), dtype=torch.float32, device=x_t.device))
+        r_t = L.gemm(mean, u, torch.empty((n, gpad), dtype=torch.float32, device=x_t.device))
         weights, cnt = weights.clone(), torch.empty_like(cnt)     # get_features_mask's result stays usable by the caller
         L.check(lib.ovo_global_patch_filter(L.ptr(r_t), L.ptr(weights), n, g, gpad, self.global_patch_threshold, L.ptr(cnt), L.stream()))
         return weights, cnt

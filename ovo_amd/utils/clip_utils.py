@@ -67,11 +67,7 @@ def _similarity_large(feats, txt, siglip, logit_scale, logit_bias, th, cls, conf
         raise L.OvoHipError(f"unsupported score dtype {sim_dtype}")
     sim = torch.empty((n, qp), dtype=sim_dtype, device=feats.device) if want_sim else None
     bias = torch.full((qp,), float(logit_bias), dtype=torch.float32, device=feats.device) if siglip else None
-    g = L.Gemm()
-    g.A, g.lda, g.W, g.ldw, g.bias = feats.data_ptr(), d, t16.data_ptr(), d, L.ptr(bias)
-    g.C, g.ldc, g.add, g.ld_add = L.ptr(sim), qp, None, 0
-    g.M, g.N, g.K = n, qp, d
-    g.in_dtype, g.out_dtype, g.act, g.alpha = _DTYPE_CODE[feats.dtype], _DTYPE_CODE[sim_dtype], (4 if siglip else 0), (math.exp(logit_scale) if siglip else 1.0)
+    g = L.gemm_desc(feats, t16, sim, bias=bias, out_dtype=sim_dtype, act=(4 if siglip else 0), alpha=(math.exp(logit_scale) if siglip else 1.0))
     if cls is not None:
         best = torch.zeros(n, dtype=torch.int64, device=feats.device)         # u64 (score, ~column) keys
         L.check(lib.ovo_gemm_argmax(L.C.byref(g), L.ptr(best), int(want_sim), q, L.stream()))

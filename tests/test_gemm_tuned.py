@@ -53,10 +53,7 @@ def test_tuned_choice_equals_cost_model_choice(monkeypatch):
             else:
                 monkeypatch.setenv("OVO_GEMM_NO_TUNED", "1")
             out = res.clone() if (res is not None and f32) else torch.zeros(m, n, dtype=torch.float32 if f32 else torch.bfloat16, device="cuda")
-            g = L.Gemm()
-            g.A, g.lda, g.W, g.ldw, g.bias, g.C, g.ldc = a.data_ptr(), k, w.data_ptr(), k, bias.data_ptr(), out.data_ptr(), n
-            g.add, g.ld_add = (out.data_ptr() if f32 else res.data_ptr(), n) if res is not None else (None, 0)
-            g.M, g.N, g.K, g.in_dtype, g.out_dtype, g.act, g.alpha = m, n, k, 2, 0 if f32 else 2, (f & 12) >> 2, 1.0
+            g = L.gemm_desc(a, w, out, bias=bias, add=None if res is None else (out if f32 else res), act=(f & 12) >> 2)
             if f & 16:
                 rope = L.Rope(); rope.cos, rope.sin, rope.T, rope.hd, rope.cols, rope.t0 = cs.data_ptr(), sn.data_ptr(), T, hd, 2 * n // 3, 1
                 L.check(lib.ovo_gemm_rope(C.byref(g), C.byref(rope), L.stream()))

@@ -22,13 +22,7 @@ ACT_NAME = {0: None, 3: "relu", 4: "sigmoid", 6: "leaky_relu", 7: "silu"}
 def _few(a, w, bias, act=0, out_dtype=torch.float32, add=None, entry="ovo_gemm_fewrows"):
     from ovo_amd import _lib as L
     out = torch.empty(a.shape[0], w.shape[0], dtype=out_dtype, device=DEV)
-    g = L.Gemm()
-    g.A, g.lda, g.W, g.ldw, g.bias = a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr()
-    g.C, g.ldc = out.data_ptr(), out.stride(0)
-    g.add, g.ld_add = (add.data_ptr(), add.stride(0)) if add is not None else (None, 0)
-    g.M, g.N, g.K = a.shape[0], w.shape[0], a.shape[1]
-    g.in_dtype, g.out_dtype, g.act, g.alpha = 2, L.DTYPE_CODE[out_dtype], act, 1.0
-    L.check(getattr(L.load(), entry)(C.byref(g), L.stream()))
+    L.check(getattr(L.load(), entry)(C.byref(L.gemm_desc(a, w, out, bias=bias, add=add, act=act)), L.stream()))
     return out
 
 
@@ -62,10 +56,9 @@ def test_gemm_fewrows_row_blocks_and_unsupported():
     # ovo_gemm takes the two activations as well (the route above the crossover and with OVO_MERGER_NO_FEWROWS)
     for act, name in ((6, "leaky_relu"), (7, "silu")):
         torch.testing.assert_close(_few(a, w, bias, act, entry="ovo_gemm"), ACTS[name](a.double() @ w.double().T + bias.double()).float(), atol=3e-4, rtol=3e-4)
-    g = L.Gemm()
     out = torch.full((4, 96), 7.0, device=DEV)
-    g.A, g.lda, g.W, g.ldw, g.bias, g.C, g.ldc, g.add, g.ld_add = a.data_ptr(), 256, w.data_ptr(), 256, None, out.data_ptr(), 96, None, 0
-    g.M, g.N, g.K, g.in_dtype, g.out_dtype, g.act, g.alpha = 4, 96, 224, 2, 0, 0, 1.0                 # K % 64 != 0
+    g = L.gemm_desc(a, w, out, rows=4)
+    g.K = 224                                                                                          # K % 64 != 0
     assert L.load().ovo_gemm_fewrows(C.byref(g), L.stream()) == L.E_UNSUPPORTED
     g.K, g.act = 256, 1                                                                                # GELU is not one of its activations
     assert L.load().ovo_gemm_fewrows(C.byref(g), L.stream()) == L.E_UNSUPPORTED
@@ -89,15 +82,8 @@ def test_attention_short(b, t, h, hd):
     L.check(L.load().ovo_attention_short(L.ptr(qkv), b, t, h, hd, scale, L.ptr(out), L.stream()))
     torch.testing.assert_close(out.float(), _att_ref(qkv, scale), atol=2e-2, rtol=1.6e-2)              # one bf16 rounding of O(1) values
     if hd == 64:                                                                                       # the MFMA attention on the same packed tensor
-        a = L.Attention()
         o2 = torch.empty_like(out)
-        d = h * hd
-        a.q, a.k, a.v, a.o = qkv.data_ptr(), qkv.data_ptr() + 2 * d, qkv.data_ptr() + 4 * d, o2.data_ptr()
-        a.q_sb = a.k_sb = a.v_sb = t * 3 * d
-        a.q_sh = a.k_sh = a.v_sh = a.o_sh = hd
-        a.q_st = a.k_st = a.v_st = 3 * d
-        a.o_sb, a.o_st = t * d, d
-        a.B, a.H, a.Tq, a.Tk, a.hd, a.scale, a.causal = b, h, t, t, hd, scale, 0
+        a = L.attention_packed(qkv, o2, b, h, t, t, hd, scale=scale)
         L.check(L.load().ovo_attention(C.byref(a), L.stream()))
         torch.testing.assert_close(out.float(), o2.float(), atol=4e-2, rtol=3.2e-2)                    # two roundings vs one
 

@@ -24,18 +24,7 @@ DEV = "cuda"
 
 def _gemm(a, w, bias=None, add=None, act=0, alpha=1.0, out_dtype=torch.float32):
     from ovo_amd import _lib as L
-    m, k = a.shape
-    n = w.shape[0]
-    out = torch.empty((m, n), dtype=out_dtype, device=DEV)
-    g = L.Gemm()
-    g.A, g.lda, g.W, g.ldw = a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0)
-    g.bias = bias.data_ptr() if bias is not None else None
-    g.C, g.ldc = out.data_ptr(), out.stride(0)
-    g.add, g.ld_add = (add.data_ptr(), add.stride(0)) if add is not None else (None, 0)
-    g.M, g.N, g.K = m, n, k
-    g.in_dtype, g.out_dtype, g.act, g.alpha = L.DTYPE_CODE[a.dtype], L.DTYPE_CODE[out_dtype], act, alpha
-    L.check(L.load().ovo_gemm(C.byref(g), L.stream()))
-    return out
+    return L.gemm(a, w, torch.empty((a.shape[0], w.shape[0]), dtype=out_dtype, device=DEV), bias=bias, add=add, act=act, alpha=alpha)
 
 
 @pytest.mark.parametrize("m,n,k", [(1154, 3072, 1024), (1154, 1024, 4096), (1154, 1024, 1024), (64, 64, 32), (1, 4, 32),
@@ -65,11 +54,8 @@ a = torch.randn(m, k).to("cuda", torch.bfloat16)
 w = (torch.randn(n, k) * k ** -0.5).to("cuda", torch.bfloat16)
 out = torch.empty(m, n, device="cuda")
 def kinds():
-    g = L.Gemm()
-    g.A, g.lda, g.W, g.ldw, g.bias, g.C, g.ldc, g.add, g.ld_add = a.data_ptr(), k, w.data_ptr(), k, None, out.data_ptr(), n, None, 0
-    g.M, g.N, g.K, g.in_dtype, g.out_dtype, g.act, g.alpha = m, n, k, 2, 0, 0, 1.0
     L.check(lib.ovo_profile_start())
-    L.check(lib.ovo_gemm(C.byref(g), L.stream()))
+    L.check(lib.ovo_gemm(C.byref(L.gemm_desc(a, w, out)), L.stream()))
     ms, work, cnt = (C.c_double * 9)(), (C.c_double * 9)(), (C.c_int64 * 9)()
     L.check(lib.ovo_profile_stop(ms, work, cnt, 9))
     return [i for i in range(9) for _ in range(cnt[i])]
@@ -111,11 +97,7 @@ def test_gemm_epilogues_and_padding():
     torch.testing.assert_close(_gemm(a, w, bias, add=add, alpha=0.5), 0.5 * z + bias + add, atol=3e-4, rtol=3e-4)
     x = add.clone()                                          # in-place residual: C aliases add
     from ovo_amd import _lib as L
-    gg = L.Gemm()
-    gg.A, gg.lda, gg.W, gg.ldw, gg.bias = a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr()
-    gg.C, gg.ldc, gg.add, gg.ld_add = x.data_ptr(), n, x.data_ptr(), n
-    gg.M, gg.N, gg.K, gg.in_dtype, gg.out_dtype, gg.act, gg.alpha = m, n, k, 2, 0, 0, 1.0
-    L.check(L.load().ovo_gemm(C.byref(gg), L.stream()))
+    L.gemm(a, w, x, bias=bias, add=x)
     torch.testing.assert_close(x, add + z + bias, atol=3e-4, rtol=3e-4)
     ob = _gemm(a, w, bias, out_dtype=torch.bfloat16)         # bf16 store = RNE of the fp32 result
     assert torch.equal(ob, _gemm(a, w, bias).to(torch.bfloat16))
@@ -149,11 +131,7 @@ def test_gemm_pingpong_kernel_vs_ring_kernel_and_torch(monkeypatch, tile, m, n, 
     assert (lut - out).abs().max() < 4e-5                                    # two approximations of erf-GELU, each within 1e-5 of it
     x = add.clone()                                                          # in-place residual: C aliases add
     from ovo_amd import _lib as L
-    gg = L.Gemm()
-    gg.A, gg.lda, gg.W, gg.ldw, gg.bias = a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr()
-    gg.C, gg.ldc, gg.add, gg.ld_add = x.data_ptr(), n, x.data_ptr(), n
-    gg.M, gg.N, gg.K, gg.in_dtype, gg.out_dtype, gg.act, gg.alpha = m, n, k, L.DTYPE_CODE[dtype], 0, 0, 1.0
-    L.check(L.load().ovo_gemm(C.byref(gg), L.stream()))
+    L.gemm(a, w, x, bias=bias, add=x)
     torch.testing.assert_close(x, add + a.float() @ w.float().T + bias, atol=3e-4, rtol=3e-4)
 
 
@@ -176,11 +154,7 @@ def test_gemm_pingpong_mfma32_loop_vs_mfma16_loop_and_torch(monkeypatch, tile, m
         out = {"f32_gelu_add": _gemm(a, w, bias, add=add, act=1), "bf16": _gemm(a, w, bias, out_dtype=dtype),
                "bf16_gelu": _gemm(a, w, bias, act=1, out_dtype=dtype), "bf16_qgelu_alpha": _gemm(a, w, bias, act=2, alpha=0.75, out_dtype=dtype)}
         x = add.clone()
-        gg = L.Gemm()
-        gg.A, gg.lda, gg.W, gg.ldw, gg.bias = a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr()
-        gg.C, gg.ldc, gg.add, gg.ld_add = x.data_ptr(), n, x.data_ptr(), n
-        gg.M, gg.N, gg.K, gg.in_dtype, gg.out_dtype, gg.act, gg.alpha = m, n, k, 2, 0, 0, 1.0
-        L.check(L.load().ovo_gemm(C.byref(gg), L.stream()))
+        L.gemm(a, w, x, bias=bias, add=x)
         out["f32_inplace"] = x
         return out
     monkeypatch.setenv("OVO_8P_MFMA32", "0")
@@ -214,11 +188,7 @@ def test_gemm_pingpong_merged_intervals_bit_identical(monkeypatch, m, n, k):
         out = {"f32_gelu_add": _gemm(a, w, bias, add=add, act=1), "bf16": _gemm(a, w, bias, out_dtype=dtype),
                "bf16_gelu": _gemm(a, w, bias, act=1, out_dtype=dtype), "f32": _gemm(a, w, bias)}
         x = add.clone()
-        gg = L.Gemm()
-        gg.A, gg.lda, gg.W, gg.ldw, gg.bias = a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr()
-        gg.C, gg.ldc, gg.add, gg.ld_add = x.data_ptr(), n, x.data_ptr(), n
-        gg.M, gg.N, gg.K, gg.in_dtype, gg.out_dtype, gg.act, gg.alpha = m, n, k, 2, 0, 0, 1.0
-        L.check(L.load().ovo_gemm(C.byref(gg), L.stream()))
+        L.gemm(a, w, x, bias=bias, add=x)
         out["f32_inplace"] = x
         return out
     monkeypatch.setenv("OVO_8P_MERGED", "0")
@@ -247,9 +217,7 @@ def test_gemm_rope_epilogue_mfma32_loop(monkeypatch, b, t, heads, hd):
     for mf in ("0", "1"):
         monkeypatch.setenv("OVO_8P_MFMA32", mf)
         out = torch.empty(m, 3 * d, dtype=torch.bfloat16, device=DEV)
-        gg = L.Gemm()
-        gg.A, gg.lda, gg.W, gg.ldw, gg.bias, gg.C, gg.ldc = a.data_ptr(), d, w.data_ptr(), d, bias.data_ptr(), out.data_ptr(), 3 * d
-        gg.M, gg.N, gg.K, gg.in_dtype, gg.out_dtype, gg.act, gg.alpha = m, 3 * d, d, 2, 2, 0, 1.0
+        gg = L.gemm_desc(a, w, out, bias=bias)
         rp = L.Rope(cos.data_ptr(), sin.data_ptr(), t, hd, 2 * d, 1)
         L.check(L.load().ovo_gemm_rope(C.byref(gg), C.byref(rp), L.stream()))
         outs.append(out.float())
@@ -321,11 +289,7 @@ def test_gemm_stream_kernel_vs_tiled_kernel_and_torch(monkeypatch, m, n, k):
     assert (out - tiled).abs().max() < 4e-5                        # table GELU against the polynomial on the same pre-activation bits
     x = add.clone()                                                # in-place residual: C aliases add
     from ovo_amd import _lib as L
-    gg = L.Gemm()
-    gg.A, gg.lda, gg.W, gg.ldw, gg.bias = a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr()
-    gg.C, gg.ldc, gg.add, gg.ld_add = x.data_ptr(), n, x.data_ptr(), n
-    gg.M, gg.N, gg.K, gg.in_dtype, gg.out_dtype, gg.act, gg.alpha = m, n, k, 2, 0, 0, 1.0
-    L.check(L.load().ovo_gemm(C.byref(gg), L.stream()))
+    L.gemm(a, w, x, bias=bias, add=x)
     torch.testing.assert_close(x, add + a.float() @ w.float().T + bias, atol=3e-4, rtol=3e-4)
 
 
@@ -348,11 +312,7 @@ def test_gemm_stream_kernel_unwindow_rows(monkeypatch):
             monkeypatch.delenv("OVO_GEMM_NO_STREAM")
             monkeypatch.setenv("OVO_GEMM_TILE", "stream")
         x = res.clone()
-        gg, win = L.Gemm(), L.Window()
-        gg.A, gg.lda, gg.W, gg.ldw, gg.bias = a.data_ptr(), k, w.data_ptr(), k, bias.data_ptr()
-        gg.C, gg.ldc, gg.add, gg.ld_add = x.data_ptr(), n, x.data_ptr(), n
-        gg.M, gg.N, gg.K, gg.in_dtype, gg.out_dtype, gg.act, gg.alpha = M, n, k, 2, 0, 0, 1.0
-        win.B, win.H, win.W, win.wh, win.ww = B, H, W, wh, ww
+        gg, win = L.gemm_desc(a, w, x, bias=bias, add=x, ldc=n), L.Window(B, H, W, wh, ww)      # (x holds the spatial rows, fewer than M)
         L.check(L.load().ovo_gemm_unwindow(C.byref(gg), C.byref(win), L.stream()))
         outs.append(x)
     assert torch.equal(outs[0], outs[1])
@@ -377,9 +337,7 @@ def test_gemm_unwindow_epilogue_vs_torch(B, H, W, wh, ww, n, k):
     for inplace in (False, True):
         add = res.clone()
         out = add if inplace else torch.full((B * H * W, n), float("nan"), device=DEV)
-        gg = L.Gemm()
-        gg.A, gg.lda, gg.W, gg.ldw, gg.bias, gg.C, gg.ldc, gg.add, gg.ld_add = a.data_ptr(), k, w.data_ptr(), k, bias.data_ptr(), out.data_ptr(), n, add.data_ptr(), n
-        gg.M, gg.N, gg.K, gg.in_dtype, gg.out_dtype, gg.act, gg.alpha = m, n, k, 2, 0, 0, 1.0
+        gg = L.gemm_desc(a, w, out, bias=bias, add=add, ldc=n)      # (out holds the spatial rows, fewer than m)
         win = L.Window(B, H, W, wh, ww)
         L.check(L.load().ovo_gemm_unwindow(C.byref(gg), C.byref(win), L.stream()))
         torch.testing.assert_close(out, ref, atol=3e-4, rtol=3e-4)
@@ -404,9 +362,7 @@ def test_gemm_rope_epilogue_vs_rope_kernel_and_torch(b, t, heads, hd):
     ang = ang.repeat_interleave(2, dim=1)
     cos, sin = ang.cos().contiguous().to(DEV), ang.sin().contiguous().to(DEV)
     out = torch.empty(m, 3 * d, dtype=torch.bfloat16, device=DEV)
-    gg = L.Gemm()
-    gg.A, gg.lda, gg.W, gg.ldw, gg.bias, gg.C, gg.ldc = a.data_ptr(), d, w.data_ptr(), d, bias.data_ptr(), out.data_ptr(), 3 * d
-    gg.M, gg.N, gg.K, gg.in_dtype, gg.out_dtype, gg.act, gg.alpha = m, 3 * d, d, 2, 2, 0, 1.0
+    gg = L.gemm_desc(a, w, out, bias=bias)
     rp = L.Rope(cos.data_ptr(), sin.data_ptr(), t, hd, 2 * d, 1)
     L.check(L.load().ovo_gemm_rope(C.byref(gg), C.byref(rp), L.stream()))
     z = (a.float() @ w.float().T + bias).reshape(b, t, 3, heads, hd)
@@ -437,14 +393,7 @@ def test_attention_vs_torch(B, H, Tq, Tk, hd):
     qkv = torch.randn(B, T, 3, H, hd, generator=g).to(DEV, torch.bfloat16)          # packed like the QKV GEMM output
     qkv[:, :, 0] *= 2.0                                                              # peaked softmax rows
     out = torch.zeros(B, Tq, D, dtype=torch.bfloat16, device=DEV)
-    a = L.Attention()
-    base, esz = qkv.data_ptr(), 2
-    a.q, a.k, a.v, a.o = base, base + D * esz, base + 2 * D * esz, out.data_ptr()
-    a.q_sb = a.k_sb = a.v_sb = T * 3 * D
-    a.q_sh = a.k_sh = a.v_sh = hd
-    a.q_st = a.k_st = a.v_st = 3 * D
-    a.o_sb, a.o_sh, a.o_st = Tq * D, hd, D
-    a.B, a.H, a.Tq, a.Tk, a.hd, a.scale = B, H, Tq, Tk, hd, hd ** -0.5
+    a = L.attention_packed(qkv, out, B, H, Tq, Tk, hd, scale=hd ** -0.5)
     L.check(L.load().ovo_attention(C.byref(a), L.stream()))
     q, k, v = (qkv[:, :n, i].float().permute(0, 2, 1, 3) for i, n in ((0, Tq), (1, Tk), (2, Tk)))
     ref = torch.softmax(q @ k.transpose(-1, -2) * hd ** -0.5, dim=-1) @ v
@@ -473,14 +422,7 @@ def test_attention_prescaled_queries(B, H, Tq, Tk, hd):
     for name, t, scale in (("prescaled", pre, 0.0), ("in_kernel", raw, hd ** -0.5)):
         qkv = t.to(DEV, torch.bfloat16)
         out = torch.zeros(B, Tq, D, dtype=torch.bfloat16, device=DEV)
-        a = L.Attention()
-        base = qkv.data_ptr()
-        a.q, a.k, a.v, a.o = base, base + D * 2, base + 4 * D, out.data_ptr()
-        a.q_sb = a.k_sb = a.v_sb = T * 3 * D
-        a.q_sh = a.k_sh = a.v_sh = hd
-        a.q_st = a.k_st = a.v_st = 3 * D
-        a.o_sb, a.o_sh, a.o_st = Tq * D, hd, D
-        a.B, a.H, a.Tq, a.Tk, a.hd, a.scale = B, H, Tq, Tk, hd, scale
+        a = L.attention_packed(qkv, out, B, H, Tq, Tk, hd, scale=scale)
         L.check(L.load().ovo_attention(C.byref(a), L.stream()))
         q, k, v = (qkv[:, :n, i].float().permute(0, 2, 1, 3) for i, n in ((0, Tq), (1, Tk), (2, Tk)))
         f = math.log(2.0) if scale == 0.0 else scale
@@ -513,16 +455,8 @@ def test_attention_rescale_path(B, H, Tq, Tk, hd):
 
 def _attention_call(qkv, B, H, Tq, Tk, hd, causal=0):
     from ovo_amd import _lib as L
-    D, T = H * hd, qkv.shape[1]
-    out = torch.zeros(B, Tq, D, dtype=torch.bfloat16, device=DEV)
-    a = L.Attention()
-    base = qkv.data_ptr()
-    a.q, a.k, a.v, a.o = base, base + D * 2, base + 2 * D * 2, out.data_ptr()
-    a.q_sb = a.k_sb = a.v_sb = T * 3 * D
-    a.q_sh = a.k_sh = a.v_sh = hd
-    a.q_st = a.k_st = a.v_st = 3 * D
-    a.o_sb, a.o_sh, a.o_st = Tq * D, hd, D
-    a.B, a.H, a.Tq, a.Tk, a.hd, a.scale, a.causal = B, H, Tq, Tk, hd, hd ** -0.5, causal
+    out = torch.zeros(B, Tq, H * hd, dtype=torch.bfloat16, device=DEV)
+    a = L.attention_packed(qkv, out, B, H, Tq, Tk, hd, scale=hd ** -0.5, causal=causal)
     L.check(L.load().ovo_attention(C.byref(a), L.stream()))
     torch.cuda.synchronize()
     return out
@@ -602,9 +536,7 @@ def test_gemm_with_layernorm_in_the_operand_load(M, N, K, d, win, mode, act, out
         grid[src.to(DEV)] = ref
         ref = torch.nn.functional.max_pool2d(grid.reshape(B, H, W, N).permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1).reshape(-1, N).contiguous()
     got = torch.empty(ref.shape[0], N, dtype=out, device=DEV)
-    q = L.Gemm()
-    q.A, q.lda, q.W, q.ldw, q.bias, q.C, q.ldc, q.add, q.ld_add = None, K, w.data_ptr(), K, bias.data_ptr(), got.data_ptr(), N, None, 0
-    q.M, q.N, q.K, q.in_dtype, q.out_dtype, q.act, q.alpha = M, N, K, 2, 0 if out == torch.float32 else 2, act, 1.0
+    q = L.gemm_desc(None, w, got, bias=bias, act=act, rows=M, ldc=N)      # (pooled: got holds a quarter of the M rows)
     wd = None
     if win is not None:
         wd = L.Window(); wd.B, wd.H, wd.W, wd.wh, wd.ww = win
@@ -653,16 +585,11 @@ def test_fused_mlp_stream_vs_two_products_and_torch(rows, d, k1):
     # (a) two launches
     xa = x0.clone()
     h = torch.empty(rows, hid, dtype=torch.bfloat16, device=DEV)
-    q = L.Gemm()
-    q.A, q.lda, q.W, q.ldw, q.bias, q.C, q.ldc, q.add, q.ld_add = None, k1, w1.data_ptr(), k1, b1.data_ptr(), h.data_ptr(), hid, None, 0
-    q.M, q.N, q.K, q.in_dtype, q.out_dtype, q.act, q.alpha = rows, hid, k1, 2, 2, 1, 1.0
+    q = L.gemm_desc(None, w1, h, bias=b1, act=1, rows=rows)
     rc = lib.ovo_gemm_f32a(C.byref(q), None, xa.data_ptr(), d, gamma.data_ptr(), beta.data_ptr(), 1e-6, 1, 0, L.stream())
     two = rc == 0
     if two:
-        q2 = L.Gemm()
-        q2.A, q2.lda, q2.W, q2.ldw, q2.bias, q2.C, q2.ldc, q2.add, q2.ld_add = h.data_ptr(), hid, w2.data_ptr(), hid, b2.data_ptr(), xa.data_ptr(), d, xa.data_ptr(), d
-        q2.M, q2.N, q2.K, q2.in_dtype, q2.out_dtype, q2.act, q2.alpha = rows, d, hid, 2, 0, 0, 1.0
-        L.check(lib.ovo_gemm(C.byref(q2), L.stream()))
+        L.gemm(h, w2, xa, bias=b2, add=xa)
     # fused
     xf = torch.cat([x0, torch.full((64, d), 7.0, device=DEV)])            # guard rows behind the end: must stay untouched
     L.check(lib.ovo_mlp_f32(xf.data_ptr(), rows, d, gamma.data_ptr(), beta.data_ptr(), 1e-6, w1.data_ptr(), k1, b1.data_ptr(), hid,
@@ -893,10 +820,7 @@ def test_gemm_fold_pieces_vs_torch(m, d, n, act):
     xb = torch.empty(m, d, dtype=torch.bfloat16, device=DEV)
     parts = d // 64
     stats = torch.full((parts, m, 2), float("nan"), device=DEV)
-    g = L.Gemm()
-    g.A, g.lda, g.W, g.ldw, g.bias = a.data_ptr(), d, wo.data_ptr(), d, bo.data_ptr()
-    g.C, g.ldc, g.add, g.ld_add = x.data_ptr(), d, res.data_ptr(), d
-    g.M, g.N, g.K, g.in_dtype, g.out_dtype, g.act, g.alpha = m, d, d, 2, 0, 0, 1.0
+    g = L.gemm_desc(a, wo, x, bias=bo, add=res)
     L.check(lib.ovo_gemm_fold_out(C.byref(g), L.ptr(xb), d, L.ptr(stats), m, L.stream()))
     assert torch.equal(x, ref_x)
     assert torch.equal(xb, ref_x.to(torch.bfloat16))
@@ -912,9 +836,7 @@ def test_gemm_fold_pieces_vs_torch(m, d, n, act):
     if act == 1:
         ref = torch.nn.functional.gelu(ref)
     out = torch.empty(m, n, dtype=torch.bfloat16, device=DEV)
-    g.A, g.lda, g.W, g.ldw, g.bias = xb.data_ptr(), d, wf_d.data_ptr(), d, bf_d.data_ptr()
-    g.C, g.ldc, g.add, g.ld_add = out.data_ptr(), n, None, 0
-    g.M, g.N, g.K, g.out_dtype, g.act = m, n, d, 2, act
+    g = L.gemm_desc(xb, wf_d, out, bias=bf_d, act=act)
     L.check(lib.ovo_gemm_fold_in(C.byref(g), None, L.ptr(stats), m, parts, d, L.ptr(cs_d), 1e-5, L.stream()))
     got = out.float().cpu()
     scale = ref.abs().max().item()

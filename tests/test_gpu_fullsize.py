@@ -136,7 +136,6 @@ def test_streaming_gemm_full_size_equals_tiled(monkeypatch, m, n, k, act):
     """The Hiera stage-1 / stage-2 products at the bench's size (8 frames x 65 536 / 16 384 tokens): the weights-resident streaming kernel
     and the tiled kernels accumulate every output element in the same k-order, so the full-size outputs are bit-identical (with GELU: equal up to an ulp of bf16 on < 2 % of the elements -- table vs polynomial); a sampled set
     of rows is also checked against the fp32 product of the same rounded operands."""
-    import ctypes as C
     from ovo_amd import _lib as L
     g = torch.Generator().manual_seed(m % 1000 + n + k)
     a = torch.randn(m, k, generator=g).to(torch.bfloat16).to(DEV)
@@ -150,11 +149,7 @@ def test_streaming_gemm_full_size_equals_tiled(monkeypatch, m, n, k, act):
             monkeypatch.delenv("OVO_GEMM_NO_STREAM")
             monkeypatch.setenv("OVO_GEMM_TILE", "stream")
         out = torch.empty((m, n), dtype=torch.bfloat16, device=DEV)
-        gg = L.Gemm()
-        gg.A, gg.lda, gg.W, gg.ldw, gg.bias, gg.C, gg.ldc, gg.add, gg.ld_add = a.data_ptr(), k, w.data_ptr(), k, bias.data_ptr(), out.data_ptr(), n, None, 0
-        gg.M, gg.N, gg.K, gg.in_dtype, gg.out_dtype, gg.act, gg.alpha = m, n, k, 2, 2, act, 1.0
-        L.check(L.load().ovo_gemm(C.byref(gg), L.stream()))
-        outs.append(out)
+        outs.append(L.gemm(a, w, out, bias=bias, act=act))
     if act:       # GELU: the streaming kernel's LDS table against the tiled kernel's own form on the same pre-activation bits -- the bf16 outputs differ
         # by an ulp where a rounding boundary falls between two 1e-5-accurate approximations, nowhere by more
         d = (outs[0].float() - outs[1].float()).abs()

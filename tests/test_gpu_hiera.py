@@ -286,9 +286,7 @@ def test_projection_with_rowwise_layernorm_vs_torch(windowed):
     ln_g, ln_b = 1.0 + 0.2 * torch.randn(N, generator=g), 0.1 * torch.randn(N, generator=g)
     d_A, d_W, d_bias, d_x, d_g, d_b = (t.to(DEV) for t in (A, W, bias, x.clone(), ln_g, ln_b))
     h = torch.full((B * H * H, N), 7.0, dtype=torch.bfloat16, device=DEV)
-    q = L.Gemm()
-    q.A, q.lda, q.W, q.ldw, q.bias, q.C, q.ldc, q.add, q.ld_add = d_A.data_ptr(), K, d_W.data_ptr(), K, d_bias.data_ptr(), d_x.data_ptr(), N, d_x.data_ptr(), N
-    q.M, q.N, q.K, q.in_dtype, q.out_dtype, q.act, q.alpha = M, N, K, 2, 0, 0, 1.0
+    q = L.gemm_desc(d_A, d_W, d_x, bias=d_bias, add=d_x, ldc=N)      # (windowed: d_x holds the spatial rows, fewer than M)
     win = L.Window(B, H, H, ws, ws) if windowed else None
     L.check(lib.ovo_gemm_rowln(C.byref(q), C.byref(win) if windowed else None, L.ptr(d_g), L.ptr(d_b), 1e-6, L.ptr(h), N, L.stream()))
     prod = A.float() @ W.float().T + bias

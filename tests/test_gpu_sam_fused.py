@@ -86,12 +86,9 @@ def test_skinny_linear_vs_torch_and_periodic_gemm(N, K):
     torch.testing.assert_close(out[:, off:off + N].float(), ref, atol=0.03, rtol=0.01)           # bf16 output
     assert torch.all(out[:, :off] == 7.0) and torch.all(out[:, off + N:] == 7.0)                 # neighbours untouched
     # the tiled-GEMM form of the same product (ovo_gemm_periodic): equal up to the summation order of the f32 accumulation
-    gm = L.Gemm()
     out2 = torch.empty((M, N), dtype=torch.bfloat16, device=DEV)
     addc = add[:, off:off + N].contiguous()
-    gm.A, gm.lda, gm.W, gm.ldw, gm.bias, gm.C, gm.ldc, gm.add, gm.ld_add = A.data_ptr(), K, W.data_ptr(), K, bias.data_ptr(), out2.data_ptr(), N, addc.data_ptr(), N
-    gm.M, gm.N, gm.K, gm.in_dtype, gm.out_dtype, gm.act, gm.alpha = M, N, K, 2, 2, 0, 1.0
-    L.check(lib.ovo_gemm_periodic(C.byref(gm), S, L.stream()))
+    L.check(lib.ovo_gemm_periodic(C.byref(L.gemm_desc(A, W, out2, bias=bias, add=addc)), S, L.stream()))
     torch.testing.assert_close(out2.float(), out[:, off:off + N].float(), atol=0.02, rtol=0.01)
     torch.testing.assert_close(out2.float(), ref, atol=0.03, rtol=0.01)
 
@@ -112,11 +109,7 @@ def test_up1_ln_vs_torch_and_unfused(C1, K, s, P):
     ref = _gelu(torch.nn.functional.layer_norm(prod + bias + feat, (C1,), gamma, beta, 1e-6))
     torch.testing.assert_close(out.float(), ref, atol=0.03, rtol=0.01)
     # the unfused chain rounds the product to bf16 before the row pass; the results agree to bf16 resolution
-    gm = L.Gemm()
-    g1 = torch.empty((M, 4 * C1), dtype=torch.bfloat16, device=DEV)
-    gm.A, gm.lda, gm.W, gm.ldw, gm.bias, gm.C, gm.ldc, gm.add, gm.ld_add = A.data_ptr(), K, W.data_ptr(), K, None, g1.data_ptr(), 4 * C1, None, 0
-    gm.M, gm.N, gm.K, gm.in_dtype, gm.out_dtype, gm.act, gm.alpha = M, 4 * C1, K, 2, 2, 0, 1.0
-    L.check(lib.ovo_gemm(C.byref(gm), L.stream()))
+    g1 = L.gemm(A, W, torch.empty((M, 4 * C1), dtype=torch.bfloat16, device=DEV))
     out2 = torch.empty_like(out)
     L.check(lib.ovo_sam_upscale_ln(L.ptr(g1), L.ptr(bias), L.ptr(feat), L.ptr(gamma), L.ptr(beta), 1e-6, P, s, C1, L.ptr(out2), L.stream()))
     torch.testing.assert_close(out2.float(), out.float(), atol=0.05, rtol=0.02)
@@ -139,11 +132,7 @@ def test_up2_masks_vs_torch_and_unfused(C2, K, s2, P, n_mask, first):
     up = _gelu(prod + bias + feat)
     ref = torch.einsum("pyxc,pmc->pmyx", up, hyper[:, first:])
     torch.testing.assert_close(out, ref, atol=2e-3 * C2 ** 0.5, rtol=1e-3)
-    gm = L.Gemm()
-    g2 = torch.empty((M, 4 * C2), dtype=torch.bfloat16, device=DEV)
-    gm.A, gm.lda, gm.W, gm.ldw, gm.bias, gm.C, gm.ldc, gm.add, gm.ld_add = A.data_ptr(), K, W.data_ptr(), K, None, g2.data_ptr(), 4 * C2, None, 0
-    gm.M, gm.N, gm.K, gm.in_dtype, gm.out_dtype, gm.act, gm.alpha = M, 4 * C2, K, 2, 2, 0, 1.0
-    L.check(lib.ovo_gemm(C.byref(gm), L.stream()))
+    g2 = L.gemm(A, W, torch.empty((M, 4 * C2), dtype=torch.bfloat16, device=DEV))
     out2 = torch.empty_like(out)
     L.check(lib.ovo_sam_upscale_masks(L.ptr(g2), L.ptr(bias), L.ptr(feat), L.ptr(hyper), n_mask, first, P, s2, C2, L.ptr(out2), L.stream()))
     torch.testing.assert_close(out2, out, atol=0.05 * C2 ** 0.5, rtol=0.02)                       # the unfused chain rounds the product to bf16
@@ -168,16 +157,11 @@ def test_t2i_attention_vs_torch_and_flash_kernel(H, T, S, P, shared, fusedcols):
     qq = q.float().reshape(P, T, H, 16).permute(0, 2, 1, 3)
     ref = (torch.softmax(qq @ kk.transpose(-1, -2) * 0.25, dim=-1) @ vv).permute(0, 2, 1, 3).reshape(P, T, ci)
     torch.testing.assert_close(o.float(), ref, atol=0.02, rtol=0.02)
-    # the generic flash kernel on the same strided operands
-    a = L.Attention()
+    # the generic flash kernel on the same strided operands (the decoder's own strided descriptor: scale = 16 ** -0.5 = 0.25)
+    from ovo_amd.encoders.sam_decoder import HipSamDecoder
     o2 = torch.empty_like(o)
-    a.q, a.k, a.v, a.o = q.data_ptr(), kv.data_ptr() + 2 * k_off, kv.data_ptr() + 2 * v_off, o2.data_ptr()
-    a.q_sb, a.q_sh, a.q_st = T * ci, 16, ci
-    a.k_sb, a.k_sh, a.k_st = (0 if shared else S * ld), 16, ld
-    a.v_sb, a.v_sh, a.v_st = (0 if shared else S * ld), 16, ld
-    a.o_sb, a.o_sh, a.o_st = T * ci, 16, ci
-    a.B, a.H, a.Tq, a.Tk, a.hd, a.scale = P, H, T, S, 16, 0.25
-    L.check(lib.ovo_attention(C.byref(a), L.stream()))
+    qs, ks = (T * ci, 16, ci), ((0 if shared else S * ld), 16, ld)
+    HipSamDecoder._attn((q, 0), (kv, k_off), (kv, v_off), (o2, 0), P, H, T, S, 16, qs, ks, ks, qs)
     torch.testing.assert_close(o.float(), o2.float(), atol=0.02, rtol=0.02)
 
 

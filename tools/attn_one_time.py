@@ -10,11 +10,7 @@ dev = torch.device("cuda", 0); lib = L.load()
 D = H * hd; T = max(Tq, Tk)
 qkv = torch.randn(B, T, 3, H, hd, device=dev).to(torch.bfloat16)
 out = torch.zeros(B, Tq, D, dtype=torch.bfloat16, device=dev)
-a = L.Attention(); base = qkv.data_ptr()
-a.q, a.k, a.v, a.o = base, base + D * 2, base + 4 * D, out.data_ptr()
-a.q_sb = a.k_sb = a.v_sb = T * 3 * D; a.q_sh = a.k_sh = a.v_sh = hd; a.q_st = a.k_st = a.v_st = 3 * D
-a.o_sb, a.o_sh, a.o_st = Tq * D, hd, D
-a.B, a.H, a.Tq, a.Tk, a.hd, a.scale = B, H, Tq, Tk, hd, hd ** -0.5
+a = L.attention_packed(qkv, out, B, H, Tq, Tk, hd, scale=hd ** -0.5)
 for _ in range(3): L.check(lib.ovo_attention(C.byref(a), L.stream()))
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 torch.cuda.synchronize(); e0.record()

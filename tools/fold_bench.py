@@ -42,13 +42,7 @@ rope = L.Rope(cos.data_ptr(), sin.data_ptr(), T, HD, 2 * D, 1)
 
 
 def desc(a, w, bias, out, add=None, act=0):
-    g = L.Gemm()
-    g.A, g.lda, g.W, g.ldw, g.bias = a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), bias.data_ptr()
-    g.C, g.ldc = out.data_ptr(), out.stride(0)
-    g.add, g.ld_add = (add.data_ptr(), add.stride(0)) if add is not None else (None, 0)
-    g.M, g.N, g.K = a.shape[0], w.shape[0], a.shape[1]
-    g.in_dtype, g.out_dtype, g.act, g.alpha = 2, L.DTYPE_CODE[out.dtype], act, 1.0
-    return g
+    return L.gemm_desc(a, w, out, bias=bias, add=add, act=act)
 
 
 def ln():

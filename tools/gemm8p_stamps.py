@@ -17,10 +17,8 @@ out = torch.empty(m, n, dtype=torch.float32 if f32 else torch.bfloat16, device=d
 bias = torch.randn(n, device=dev)
 tiles = -(-m // bm) * -(-n // bn)
 st = torch.zeros(tiles + 8, 4, dtype=torch.int64, device=dev)
-g = L.Gemm(); g.A, g.lda, g.W, g.ldw, g.bias, g.C, g.ldc, g.add, g.ld_add = a.data_ptr(), k, w.data_ptr(), k, None, out.data_ptr(), n, None, 0
-g.M, g.N, g.K, g.in_dtype, g.out_dtype, g.act, g.alpha = m, n, k, 2, 0 if f32 else 2, int(os.environ.get('ACT', '0')), 1.0
-if os.environ.get('BIAS'): g.bias = bias.data_ptr()
-if os.environ.get('ADD'): g.add, g.ld_add = out.data_ptr(), n      # in-place residual
+g = L.gemm_desc(a, w, out, bias=bias if os.environ.get('BIAS') else None, add=out if os.environ.get('ADD') else None,      # ADD: in-place residual
+                act=int(os.environ.get('ACT', '0')))
 for _ in range(5): L.check(lib.ovo_gemm(C.byref(g), L.stream()))
 torch.cuda.synchronize()
 os.environ["OVO_8P_STAMPS"] = hex(st.data_ptr())

@@ -10,14 +10,10 @@ ROT = int(os.environ.get('ROTATE', '1'))   # > 1: cycle through that many weight
 PAD = int(os.environ.get('PAD', '0'))      # extra elements per row of A and W (row stride K + PAD): breaks power-of-two strides
 def run(m, n, k, iters=int(os.environ.get('ITERS', '100'))):
     a = torch.randn(m, k + PAD, device=dev).to(torch.bfloat16); ws = [(torch.randn(n, k + PAD, device=dev) * k ** -0.5).to(torch.bfloat16) for _ in range(ROT)]; w = ws[0]
-    odt = {'bf16': (torch.bfloat16, 2), 'f32': (torch.float32, 0)}[os.environ.get('OUT', 'bf16')]
-    out = torch.empty(m, n, dtype=odt[0], device=dev)
-    g = L.Gemm(); g.A, g.lda, g.W, g.ldw, g.bias, g.C, g.ldc, g.add, g.ld_add = a.data_ptr(), k + PAD, w.data_ptr(), k + PAD, None, out.data_ptr(), n, None, 0
-    g.M, g.N, g.K, g.in_dtype, g.out_dtype, g.act, g.alpha = m, n, k, 2, odt[1], int(os.environ.get('ACT', '0')), 1.0
-    if os.environ.get('BIAS'):
-        bias = torch.randn(n, device=dev) + float(os.environ.get('BIAS_SHIFT', '0')); g.bias = bias.data_ptr()      # BIAS_SHIFT=100: every GELU table lookup hits the last entry (no LDS bank conflicts)
-    if os.environ.get('ADD'):
-        add = out if os.environ.get('INPLACE') else torch.randn(m, n, device=dev); g.add, g.ld_add = add.data_ptr(), n
+    out = torch.empty(m, n, dtype={'bf16': torch.bfloat16, 'f32': torch.float32}[os.environ.get('OUT', 'bf16')], device=dev)
+    bias = torch.randn(n, device=dev) + float(os.environ.get('BIAS_SHIFT', '0')) if os.environ.get('BIAS') else None      # BIAS_SHIFT=100: every GELU table lookup hits the last entry (no LDS bank conflicts)
+    add = (out if os.environ.get('INPLACE') else torch.randn(m, n, device=dev)) if os.environ.get('ADD') else None
+    g = L.gemm_desc(a[:, :k], w[:, :k], out, bias=bias, add=add, act=int(os.environ.get('ACT', '0')))
     call = lambda: lib.ovo_gemm(C.byref(g), L.stream())
     if os.environ.get('ROPE'):          # PE's QKV projection: rotary embedding of the q and k columns in the epilogue (T = 577, head_dim 64)
         T, hd = 577, 64

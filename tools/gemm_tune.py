@@ -55,12 +55,9 @@ def make_call(m, n, k, flags):
     f32 = bool(flags & F_F32)
     out = torch.zeros(m, n, dtype=torch.float32 if f32 else torch.bfloat16, device=dev)
     bias = torch.randn(n, device=dev)
-    g = L.Gemm(); g.A, g.lda, g.W, g.ldw, g.bias, g.C, g.ldc, g.add, g.ld_add = a.data_ptr(), k, ws[0].data_ptr(), k, bias.data_ptr(), out.data_ptr(), n, None, 0
-    g.M, g.N, g.K, g.in_dtype, g.out_dtype, g.act, g.alpha = m, n, k, 2, 0 if f32 else 2, (flags & F_ACT) >> 2, 1.0
-    keep = [a, ws, out, bias]
-    if flags & F_ADD:
-        add = out if f32 else torch.zeros(m, n, device=dev)        # the encoders' residual products update the f32 stream in place
-        g.add, g.ld_add = add.data_ptr(), n; keep.append(add)
+    add = (out if f32 else torch.zeros(m, n, device=dev)) if flags & F_ADD else None        # the encoders' residual products update the f32 stream in place
+    g = L.gemm_desc(a, ws[0], out, bias=bias, add=add, act=(flags & F_ACT) >> 2)
+    keep = [a, ws, out, bias, add]
     if flags & F_ROPE:
         T, hd = 577, 64
         cs, sn = torch.rand(T, hd, device=dev), torch.rand(T, hd, device=dev)

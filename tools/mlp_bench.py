@@ -28,12 +28,7 @@ def run(rows, d, k1, iters=20):
         L.check(lib.ovo_mlp_f32(x.data_ptr(), rows, d, gamma.data_ptr(), beta.data_ptr(), 1e-6, w1.data_ptr(), k1, b1.data_ptr(), hid, w2.data_ptr(), hid,
                                 b2.data_ptr(), L.stream()))
 
-    q = L.Gemm()
-    q.A, q.lda, q.W, q.ldw, q.bias, q.C, q.ldc, q.add, q.ld_add = None, k1, w1.data_ptr(), k1, b1.data_ptr(), h.data_ptr(), hid, None, 0
-    q.M, q.N, q.K, q.in_dtype, q.out_dtype, q.act, q.alpha = rows, hid, k1, 2, 2, 1, 1.0
-    q2 = L.Gemm()
-    q2.A, q2.lda, q2.W, q2.ldw, q2.bias, q2.C, q2.ldc, q2.add, q2.ld_add = h.data_ptr(), hid, w2.data_ptr(), hid, b2.data_ptr(), x.data_ptr(), d, x.data_ptr(), d
-    q2.M, q2.N, q2.K, q2.in_dtype, q2.out_dtype, q2.act, q2.alpha = rows, d, hid, 2, 0, 0, 1.0
+    q, q2 = L.gemm_desc(None, w1, h, bias=b1, act=1, rows=rows), L.gemm_desc(h, w2, x, bias=b2, add=x)
 
     def two():
         L.check(lib.ovo_gemm_f32a(C.byref(q), None, x.data_ptr(), d, gamma.data_ptr(), beta.data_ptr(), 1e-6, 1, 0, L.stream()))

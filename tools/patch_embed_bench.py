@@ -25,11 +25,7 @@ def direct():
 def two_pass():
     L.check(lib.ovo_im2col(L.ptr(img), B, 3, S, S, 7, 4, 3, L.ptr(col), 192, L.stream()))
     for b in range(B):
-        q = L.Gemm()
-        q.A, q.lda, q.W, q.ldw, q.bias = col[b * T0:].data_ptr(), 192, w.data_ptr(), 192, bias.data_ptr()
-        q.C, q.ldc, q.add, q.ld_add = out_b[b].data_ptr(), E, pos.data_ptr(), E
-        q.M, q.N, q.K, q.in_dtype, q.out_dtype, q.act, q.alpha = T0, E, 192, 2, 0, 0, 1.0
-        L.check(lib.ovo_gemm(L.C.byref(q), L.stream()))
+        L.gemm(col[b * T0:(b + 1) * T0], w, out_b[b], bias=bias, add=pos)
 
 def timed(fn, reps=20):
     for _ in range(3): fn()

@@ -14,9 +14,7 @@ A = torch.randn(M, K, device=dev).to(torch.bfloat16); W = (torch.randn(N, K, dev
 bias, x = torch.zeros(N, device=dev), torch.randn(B * H * H, N, device=dev)
 g, b = torch.ones(N, device=dev), torch.zeros(N, device=dev)
 h = torch.empty(B * H * H, N, dtype=torch.bfloat16, device=dev)
-q = L.Gemm()
-q.A, q.lda, q.W, q.ldw, q.bias, q.C, q.ldc, q.add, q.ld_add = A.data_ptr(), K, W.data_ptr(), K, bias.data_ptr(), x.data_ptr(), N, x.data_ptr(), N
-q.M, q.N, q.K, q.in_dtype, q.out_dtype, q.act, q.alpha = M, N, K, 2, 0, 0, 1.0
+q = L.gemm_desc(A, W, x, bias=bias, add=x, ldc=N)      # (x holds the spatial rows, fewer than M)
 win = L.Window(B, H, H, ws, ws)
 def timed(fn, reps=30):
     for _ in range(5): fn()
