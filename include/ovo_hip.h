@@ -625,7 +625,8 @@ int ovo_amg_binarize(const float *logits, const int32_t *sel, int n_sel, int h, 
 int ovo_paint_segmap(const uint8_t *masks, int n, int64_t pixels, int32_t *seg, ovo_stream_t stream);
 
 /* =============================================================================================
- * f3: loop-closure semantic update (ovo.py:366-424 update_map, instance_utils.py:5-35 same_instance / fuse_instances).
+ * f3: loop closure.  The semantic update (ovo.py:366-424 update_map, instance_utils.py:5-35 same_instance / fuse_instances) and, below it, the
+ * map update of the SLAM back end that precedes it (orbslam.py:68-115 WrapperORBSLAM.update_map): ovo_map_reanchor.
  * ============================================================================================= */
 
 /* One pass over the map: cnt i32 [n_slots] points per instance id, sums f64 [n_slots, 3] of their coordinates
@@ -640,6 +641,26 @@ int ovo_near_fraction(const float *pts_by_instance, const int64_t *offsets, cons
 
 /* ins[i] = table[ins[i]] for ids in [0, n_slots): all `points_ins_ids[points_ins_ids == id2] = id1` of the merges in one pass. */
 int ovo_remap_instances(int32_t *ins, int64_t n, const int32_t *table, int n_slots, ovo_stream_t stream);
+
+/* The geometric half (ABI v15; WrapperORBSLAM.update_map, orbslam.py:68-115): after the tracker has corrected its keyframe poses, the whole point map is
+ * moved OUT OF PLACE in one launch.  The source map is xyz f32[n_src,3], ids i32[n_src], ins i32[n_src], rgb u8[n_src,3] (rgb NULL: no colours, as in
+ * ovo_map_step_t; rgb_out is then not touched).  A table of K segments IN OUTPUT ORDER (the tracker's keyframe order, not the storage order), HOST arrays:
+ *   seg_src i64[K]      first source row of segment k
+ *   seg_dst i64[K + 1]  exclusive prefix sum of the segment lengths: seg_dst[0] = 0, seg_dst[K] = rows written
+ *   seg_T   f32[K, 12]  the top three rows of the segment's 4 x 4 transform (updated c2w . inverse(old c2w)), row-major
+ * Output rows [seg_dst[k], seg_dst[k+1]) = source rows seg_src[k] .. with ids, ins and rgb copied bit for bit and xyz' = T[:, :3] . p + T[:, 3] in f32.
+ * Segments may be empty, in any order relative to storage, and may repeat source rows; source rows that no segment covers are dropped (keyframes the
+ * tracker pruned).  Rows of the outputs past seg_dst[K] are not touched.  One row's result depends on that source row and its table entry alone: no
+ * atomics, bit-identical from run to run.
+ * The WHOLE table is checked before anything is queued -- seg_src[k] >= 0, seg_src[k] + length <= n_src, seg_dst non-decreasing from 0,
+ * seg_dst[K] <= cap_out (the rows the output buffers hold), no output buffer or workspace overlapping a source buffer or each other -- a violation
+ * returns OVO_E_ARG with nothing launched: the kernel never sees an unchecked table.  K == 0 or seg_dst[K] == 0 is a successful no-op.
+ * ws: device scratch of ovo_map_reanchor_workspace_bytes(K) bytes (8-byte aligned) that the table is staged into; the host arrays are read before the
+ * call returns when they are pageable -- a pinned table has to stay unchanged until the stream has passed the call. */
+size_t ovo_map_reanchor_workspace_bytes(int K);
+int ovo_map_reanchor(const float *xyz, const int32_t *ids, const int32_t *ins, const uint8_t *rgb, int64_t n_src, float *xyz_out, int32_t *ids_out,
+                     int32_t *ins_out, uint8_t *rgb_out, int64_t cap_out, const int64_t *seg_src_host, const int64_t *seg_dst_host,
+                     const float *seg_T_host, int K, void *ws, size_t ws_bytes, ovo_stream_t stream);
 
 
 /* =============================================================================================

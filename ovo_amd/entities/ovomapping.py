@@ -8,8 +8,8 @@ What is different, on purpose:
     imageio / OpenCV and are out of scope; anything indexable that returns the reference's frame tuple
     `(frame_id, image HxWx3 u8, depth HxW f32, c2w 4x4[, full-resolution image])` and carries `intrinsics`, `height`, `width`
     (+ `dataset_config`, `crop_edge` when colour and depth resolutions differ) works;
-  * only the `vanilla` back end exists here (Gaussian-SLAM / ORB-SLAM2 wrappers: out of scope) and there is no Open3D
-    visualiser process (`vis.stream` must be false);
+  * the `vanilla` back end, and the `orbslam*` wrapper around an INJECTED tracker (`tracker=`, `ok_state=`: slam/orbslam.py; the ORB-SLAM
+    binding itself and Gaussian-SLAM are out of scope); there is no Open3D visualiser process (`vis.stream` must be false);
   * no autocast context: the kernels choose their own arithmetic (bf16 MFMA operands, fp32 accumulation);
   * when a frame is segmented, the mask-independent half of the next segmented frame's feature extraction is not started
     early here (a dataset may be a live camera); `ovo_amd.pipeline.FramePipeline` is the throughput-oriented driver that does.
@@ -31,12 +31,15 @@ from .logger import Logger
 from .ovo import OVO
 
 
-def get_slam_backbone(config: Dict[str, Any], dataset, cam_intrinsics: torch.Tensor) -> VanillaMapper:
-    """Reference: ovomapping.py:18-27."""
+def get_slam_backbone(config: Dict[str, Any], dataset, cam_intrinsics: torch.Tensor, tracker=None, ok_state=None) -> VanillaMapper:
+    """Reference: ovomapping.py:18-27.  `tracker` / `ok_state`: the injected tracker of the "orbslam*" back ends (slam/orbslam.py)."""
     backbone = config["slam"].get("slam_module", "vanilla")
+    if backbone.startswith("orbslam") and tracker is not None:
+        from ..slam.orbslam import WrapperORBSLAM
+        return WrapperORBSLAM(config, cam_intrinsics, world_ref=torch.from_numpy(dataset[0][3]), tracker=tracker, ok_state=ok_state)      # :23-25
     if backbone != "vanilla":
-        raise NotImplementedError(f"slam_module {backbone!r}: only the ground-truth-pose 'vanilla' mapper is built here "
-                                  "(Gaussian-SLAM and ORB-SLAM2 wrappers are out of scope, SURVEY.md §2)")
+        raise NotImplementedError(f"slam_module {backbone!r}: only the ground-truth-pose 'vanilla' mapper is built here, and the 'orbslam*' "
+                                  "wrapper around an injected tracker= (Gaussian-SLAM and the ORB-SLAM binding itself are out of scope, SURVEY.md §2)")
     return VanillaMapper(config, cam_intrinsics)
 
 
@@ -46,7 +49,7 @@ def _sync() -> None:
 
 
 class OVOSemMap:
-    def __init__(self, config: Dict[str, Any], output_path: str, dataset=None, ovo: Optional[OVO] = None) -> None:
+    def __init__(self, config: Dict[str, Any], output_path: str, dataset=None, ovo: Optional[OVO] = None, tracker=None, ok_state=None) -> None:
         self._setup_output_path(output_path)
         io_utils.save_dict_to_yaml(config, "config.yaml", directory=self.output_path)
         config["output_path"] = str(self.output_path)
@@ -75,7 +78,7 @@ class OVOSemMap:
         sam = config["semantic"].get("sam", {})
         if (sam.get("precomputed", False) or sam.get("precompute", False)) and self.ovo.mask_generator is not None:
             self.ovo.mask_generator.precompute(self.dataset, self.segment_every)
-        self.slam_backbone = get_slam_backbone(config, self.dataset, cam_intrinsics)
+        self.slam_backbone = get_slam_backbone(config, self.dataset, cam_intrinsics, tracker=tracker, ok_state=ok_state)
 
         self.first_frame = 0
         if config.get("restore_map", False):
