@@ -105,7 +105,7 @@ def test_fuse_views_golden_and_bank():
     rows = _t(d["clips"][0])
     bank = DescriptorBank(rows.shape[1], DEV, rows=2, slots=1)      # tiny capacities: exercise growth
     r = bank.append(rows)
-    for mode, key, kfkey in (("avg_pooling", "avg", None), ("l1_medoid", "l1", None), ("cossim_medoid", "cos", "cos_kf")):
+    for mode, key, kfkey in (("avg_pooling", "avg", None), ("l1_medoid", "l1", "l1_kf"), ("cossim_medoid", "cos", "cos_kf")):
         kf = bank.fuse([(7, r), (9, r[:1])], mode)
         np.testing.assert_allclose(bank.feature(7).reshape(-1).cpu().numpy(), d[key], atol=1e-6, rtol=0)
         assert bank.feature(7).shape == (1, rows.shape[1]) and bank.feature(9).shape == (rows.shape[1],)
