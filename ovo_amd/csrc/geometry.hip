@@ -79,6 +79,24 @@ __host__ CompactWs carve(void *ws, int64_t n) {
     return c;
 }
 
+// The workspace of a tracking step (ovo_track_step_t.ws); a step clears hist .. tickets first (zero_bytes), the decisions rewrite dst / res:
+//   i32 hist[n x cols] | i32 stats[4 n] | one word if n x cols is odd | u64 counters[CNT_SLOTS x CNT_STRIDE] | u32 tickets[2 + n] | i32 dst[n] | i32 res[8 + 6 n]
+constexpr int CNT_SLOTS = 32, CNT_STRIDE = 16;                     // counter slots of a tracking step; u64 words between two slots (128 bytes)
+struct TrackOffs { size_t stats, pad, counters, tickets, dst, res, end; };      // in 4-byte words from the start
+struct TrackWs { int32_t *hist, *stats; unsigned long long *counters; unsigned int *tickets; int32_t *dst, *res; size_t zero_bytes; };
+
+__host__ TrackOffs track_offsets(int n_masks, int hist_cols) {
+    const size_t n = (size_t)n_masks, stats = n * hist_cols, pad = stats & 1;                       // (the counters are 8-byte aligned)
+    const size_t counters = stats + 4 * n + pad, tickets = counters + 2 * CNT_SLOTS * CNT_STRIDE, dst = tickets + 2 + n, res = dst + n;
+    return TrackOffs{stats, pad, counters, tickets, dst, res, res + 8 + 6 * n};
+}
+
+__host__ TrackWs carve_track(void *ws, int n_masks, int hist_cols) {
+    const TrackOffs o = track_offsets(n_masks, hist_cols);
+    int32_t *w = (int32_t *)ws;
+    return TrackWs{w, w + o.stats, (unsigned long long *)(w + o.counters), (unsigned int *)(w + o.tickets), w + o.dst, w + o.res, o.dst * sizeof(int32_t)};
+}
+
 // (B) as three small launches (a single workgroup walking 156k words took 330 us of a 370 us frustum cull at 10 M points):
 //   k_scan_sums   one workgroup per SCAN_CHUNK words: total popcount of its chunk            -> sums[b]
 //   k_scan_bases  one workgroup: exclusive scan of the (few hundred) chunk totals, in place    -> sums[b] = base of chunk b, *total
@@ -344,8 +362,6 @@ __device__ __forceinline__ void hits_flush(const HitSink &sink, const int32_t *h
     }
     hcount = 0;
 }
-
-constexpr int CNT_SLOTS = 32, CNT_STRIDE = 16;                     // counter slots of a tracking step; u64 words between two slots (128 bytes)
 
 // The chain of one batch of survivors (lane < count active): project, depth-test, colour-frame remap, seg lookup, vote.
 __device__ __forceinline__ void track_batch(const WaveQueue &q, int head, int count, const ovo_camera_t &cam, const float *__restrict__ depth,
@@ -1309,19 +1325,78 @@ int ovo_map_explained(const float *pts, int64_t n, const ovo_camera_t *cam, cons
     return OVO_OK;
 }
 
+// ---- what the map / tracking entry points below share on the host: grid size, kernel arguments, argument checks ----------------------
+// the frame's sub-sampled grid, every ds-th pixel of h x w (vanilla_mapper.py:67-68): the length of a row, the number of pixels
+static int sub_w(int w, int ds) { return (w + ds - 1) / ds; }
+static int64_t sub_pixels(int h, int w, int ds) { return (int64_t)sub_w(h, ds) * sub_w(w, ds); }
+
+static BackprojArgs backproj_args(const float *K9, const float *c2w16, int h, int w, int ds, int erode) {
+    BackprojArgs b;
+    for (int i = 0; i < 9; ++i) b.K[i] = K9[i];
+    for (int i = 0; i < 16; ++i) b.c2w[i] = c2w16[i];
+    b.h = h; b.w = w; b.ds = ds; b.ws_w = sub_w(w, ds); b.erode = erode;
+    return b;
+}
+
+// total: the scan's total, or NULL where the emit kernel rebuilds it (k_kf_emit)
+static MapCommit map_commit(const ovo_map_step_t *a, const long long *total) {
+    return MapCommit{(long long *)a->map.state, total, (volatile long long *)a->result_host, a->seq, a->map.cap, a->map.n >= 0 ? a->map.n : -1, a->map.next_id};
+}
+
+static Decide decide_args(const ovo_track_step_t *t, const TrackWs &w) {
+    return Decide{w.res, w.dst, t->next_ins, t->next_ins_host, t->track_th, t->n_masks};
+}
+
+// n_host: the map's exact size where the host knows it at this point of the stream, else -1 (read the device state)
+static Publish publish_args(const ovo_track_step_t *t, const TrackWs &w, long long n_host) {
+    return Publish{w.res, (volatile int32_t *)t->result_host, w.counters, CNT_SLOTS, (const long long *)t->map.state, n_host, w.tickets + 1, t->seq, 8 + 6 * t->n_masks};
+}
+
+// OVO_REQUIRE in a check that several entry points share: the message names the one that was called (`who`)
+#define STEP_REQUIRE(cond, msg) do { if (!(cond)) { ovo_set_error("%s: %s", who, msg); return OVO_E_ARG; } } while (0)
+#define STEP_CHECK(call) do { const int rc__ = (call); if (rc__ != OVO_OK) return rc__; } while (0)
+
+// every argument check of a map step (ovo_map_step_t); n_sub: the pixels of its sub-sampled grid
+static int check_map_step(const ovo_map_step_t *a, int64_t &n_sub, const char *who) {
+    STEP_REQUIRE(a && a->depth && a->map.xyz && a->map.ids && a->map.ins && a->map.state && a->explained && a->ws, "null argument");
+    STEP_REQUIRE(a->h > 0 && a->w > 0 && a->ds >= 1 && a->n_upper >= 0, "bad shape");
+    n_sub = sub_pixels(a->h, a->w, a->ds);
+    STEP_REQUIRE(a->ws_bytes >= ovo_compact_workspace_bytes(n_sub) + 8, "workspace too small");
+    STEP_REQUIRE(a->map.cap >= a->n_upper + n_sub, "map capacity below n_upper + one frame of points");
+    STEP_REQUIRE(a->map.n < 0 || a->map.n <= a->n_upper, "n_upper below the known point count");
+    return OVO_OK;
+}
+
+// every argument check of a tracking step (ovo_track_step_t); sink: its hit list (ovo_track_step_t.hits; ABI 11)
+static int check_track_step(const ovo_track_step_t *t, HitSink &sink, const char *who) {
+    STEP_REQUIRE(t && t->depth && t->seg_map && t->point_seg && t->ws && t->map.state && t->next_ins, "null argument");
+    STEP_REQUIRE(t->n_upper == 0 || (t->map.xyz && t->map.ins), "null map");
+    STEP_REQUIRE(t->n_masks > 0 && t->n_masks <= 8192 && t->hist_cols >= 1, "bad mask / histogram shape");
+    STEP_REQUIRE(t->ws_bytes >= ovo_track_workspace_bytes(t->n_masks, t->hist_cols), "workspace too small");
+    STEP_REQUIRE(!t->masks || (t->pixels > 0 && t->pixels % 16 == 0 && ((uintptr_t)t->masks & 15) == 0), "masks: pixels must be a multiple of 16");
+    STEP_REQUIRE(t->map.n < 0 || t->map.n <= t->n_upper, "n_upper below the known point count");
+    STEP_REQUIRE(!t->filter_depth || t->depth_scratch, "depth_scratch needed for the depth filter");
+    sink = HitSink{nullptr, nullptr, 0, 1, 0};
+    if (!t->hits) return OVO_OK;
+    const int count = t->hit_shard_count < 1 ? 1 : t->hit_shard_count, block = t->hit_shard_block;
+    STEP_REQUIRE(t->n_hits, "hits without n_hits");
+    STEP_REQUIRE(t->hit_shard_rank >= 0 && t->hit_shard_rank < count, "bad hit shard rank");
+    STEP_REQUIRE(count == 1 || (block > 0 && (block & (block - 1)) == 0), "hit_shard_block must be a power of two");
+    int block_log2 = 0;
+    while (count > 1 && (1 << block_log2) < block) ++block_log2;
+    sink = HitSink{t->hits, t->n_hits, t->hit_shard_rank, count, block_log2};
+    return OVO_OK;
+}
+
 int ovo_map_backproject(const float *depth, const uint8_t *rgb, const uint8_t *explained, int h, int w, int erode,
                         int ds, const float *K9_host, const float *c2w16_host, int64_t base, int32_t first_id,
                         float *xyz, int32_t *ids, int32_t *ins, uint8_t *out_rgb, int64_t *out_count, void *ws,
                         size_t ws_bytes, ovo_stream_t stream) {
     OVO_REQUIRE(depth && K9_host && c2w16_host && xyz && ids && ins && out_count && ws, "null argument");
     OVO_REQUIRE(h > 0 && w > 0 && ds >= 1 && base >= 0, "bad shape");
-    BackprojArgs a;
-    for (int i = 0; i < 9; ++i) a.K[i] = K9_host[i];
-    for (int i = 0; i < 16; ++i) a.c2w[i] = c2w16_host[i];
-    a.h = h; a.w = w; a.ds = ds; a.erode = erode;
-    a.ws_w = (w + ds - 1) / ds;
-    const int64_t n_sub = (int64_t)((h + ds - 1) / ds) * a.ws_w;
+    const int64_t n_sub = sub_pixels(h, w, ds);
     OVO_REQUIRE(ws_bytes >= ovo_compact_workspace_bytes(n_sub), "workspace too small");
+    const BackprojArgs a = backproj_args(K9_host, c2w16_host, h, w, ds, erode);
     hipStream_t s = (hipStream_t)stream;
     CompactWs c = carve(ws, n_sub);
     const int g = ovo_grid(n_sub, 256);
@@ -1334,20 +1409,15 @@ int ovo_map_backproject(const float *depth, const uint8_t *rgb, const uint8_t *e
 }
 
 
-// ---- the keyframe chain without host round trips (ovo_map_step, ovo_track_step) ------------------------------------------------
+// ---- the keyframe chain without host round trips (ovo_map_step, ovo_track_step): validate, carve, fill, launch ------------------------
 size_t ovo_track_workspace_bytes(int n_masks, int hist_cols) {
-    // hist | stats[4 n] | counters (CNT_SLOTS x 128 bytes) | tickets (2 + n x u32) | dst[n] | result block [8 + 6 n]
-    return ((size_t)n_masks * hist_cols + 4 * (size_t)n_masks + 2 * CNT_SLOTS * CNT_STRIDE + 2 + n_masks + n_masks + 8 + 6 * (size_t)n_masks + 4) * sizeof(int32_t);
+    const TrackOffs o = track_offsets(n_masks, hist_cols);
+    return (o.end - o.pad + 4) * sizeof(int32_t);      // sized without the alignment word, plus 4 spare words that cover it
 }
 
 int ovo_map_step(const ovo_map_step_t *a, ovo_stream_t stream) {
-    OVO_REQUIRE(a && a->depth && a->map.xyz && a->map.ids && a->map.ins && a->map.state && a->explained && a->ws, "null argument");
-    OVO_REQUIRE(a->h > 0 && a->w > 0 && a->ds >= 1 && a->n_upper >= 0, "bad shape");
-    const int64_t ws_w = (a->w + a->ds - 1) / a->ds;
-    const int64_t n_sub = (int64_t)((a->h + a->ds - 1) / a->ds) * ws_w;
-    OVO_REQUIRE(a->ws_bytes >= ovo_compact_workspace_bytes(n_sub) + 8, "workspace too small");
-    OVO_REQUIRE(a->map.cap >= a->n_upper + n_sub, "map capacity below n_upper + one frame of points");
-    OVO_REQUIRE(a->map.n < 0 || a->map.n <= a->n_upper, "n_upper below the known point count");
+    int64_t n_sub;
+    STEP_CHECK(check_map_step(a, n_sub, __func__));
     hipStream_t s = (hipStream_t)stream;
     const bool known = a->map.n >= 0;
     const bool maybe_nonempty = known ? a->map.next_id > 0 : true;
@@ -1359,69 +1429,32 @@ int ovo_map_step(const ovo_map_step_t *a, ovo_stream_t stream) {
             k_map_explained<<<ovo_grid(a->n_upper, 256), 256, 0, s>>>(a->map.xyz, 0, a->cam, a->depth, a->explained,
                                                                       (const long long *)a->map.state);
     }
-    BackprojArgs b;
-    for (int i = 0; i < 9; ++i) b.K[i] = a->K[i];
-    for (int i = 0; i < 16; ++i) b.c2w[i] = a->c2w[i];
-    b.h = a->h; b.w = a->w; b.ds = a->ds; b.ws_w = (int)ws_w;
-    b.erode = a->erode && maybe_nonempty;
+    const BackprojArgs b = backproj_args(a->K, a->c2w, a->h, a->w, a->ds, a->erode && maybe_nonempty);
     long long *total = (long long *)a->ws;
     CompactWs c = carve((char *)a->ws + 8, n_sub);
     const int g = ovo_grid(n_sub, 256);
     k_backproj_flag<<<g, 256, 0, s>>>(a->depth, maybe_nonempty ? a->explained : nullptr, b, n_sub, c.words,
                                       known ? nullptr : (const long long *)a->map.state);
     scan_words(c.words, c.offs, c.sums, c.n_words, total, s);
-    MapCommit mc;
-    mc.state = (long long *)a->map.state; mc.total = total; mc.result = (volatile long long *)a->result_host; mc.seq = a->seq;
-    mc.cap = a->map.cap; mc.n_host = known ? a->map.n : -1; mc.id_host = a->map.next_id;
     k_backproj_emit<<<g, 256, 0, s>>>(a->depth, a->rgb, b, n_sub, c.words, c.offs, 0, 0, a->map.xyz, a->map.ids, a->map.ins,
-                                      a->map.rgb, mc);
+                                      a->map.rgb, map_commit(a, total));
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }
 
-// the hit list of a tracking step (ovo_track_step_t.hits; ABI 11), validated
-static int make_sink(const ovo_track_step_t *t, HitSink &sink) {
-    sink = HitSink{nullptr, nullptr, 0, 1, 0};
-    if (!t->hits) return OVO_OK;
-    OVO_REQUIRE(t->n_hits, "hits without n_hits");
-    const int count = t->hit_shard_count < 1 ? 1 : t->hit_shard_count;
-    OVO_REQUIRE(t->hit_shard_rank >= 0 && t->hit_shard_rank < count, "bad hit shard rank");
-    int block_log2 = 0;
-    if (count > 1) {
-        OVO_REQUIRE(t->hit_shard_block > 0 && (t->hit_shard_block & (t->hit_shard_block - 1)) == 0, "hit_shard_block must be a power of two");
-        while ((1 << block_log2) < t->hit_shard_block) ++block_log2;
-    }
-    sink = HitSink{t->hits, t->n_hits, t->hit_shard_rank, count, block_log2};
-    return OVO_OK;
-}
-
 int ovo_track_step(const ovo_track_step_t *a, ovo_stream_t stream) {
-    OVO_REQUIRE(a && a->depth && a->seg_map && a->point_seg && a->ws && a->map.state && a->next_ins, "null argument");
-    OVO_REQUIRE(a->n_upper == 0 || (a->map.xyz && a->map.ins), "null map");
-    OVO_REQUIRE(a->n_masks > 0 && a->n_masks <= 8192 && a->hist_cols >= 1, "bad mask / histogram shape");
-    OVO_REQUIRE(a->ws_bytes >= ovo_track_workspace_bytes(a->n_masks, a->hist_cols), "workspace too small");
-    OVO_REQUIRE(!a->masks || (a->pixels > 0 && a->pixels % 16 == 0 && ((uintptr_t)a->masks & 15) == 0), "masks: pixels must be a multiple of 16");
-    OVO_REQUIRE(a->map.n < 0 || a->map.n <= a->n_upper, "n_upper below the known point count");
+    HitSink sink;
+    STEP_CHECK(check_track_step(a, sink, __func__));
     hipStream_t s = (hipStream_t)stream;
     const int nm = a->n_masks;
-    int32_t *hist = (int32_t *)a->ws;
-    int32_t *stats = hist + (size_t)nm * a->hist_cols;
-    unsigned long long *counters = (unsigned long long *)(stats + 4 * (size_t)nm + ((((size_t)nm * a->hist_cols) & 1) ? 1 : 0));   // 8-byte aligned
-    unsigned int *tickets = (unsigned int *)(counters + CNT_SLOTS * CNT_STRIDE);
-    int32_t *dst = (int32_t *)(tickets + 2 + nm);
-    int32_t *res = dst + nm;
-    const size_t zero_bytes = (size_t)((char *)dst - (char *)hist);
-    OVO_HIP(hipMemsetAsync(hist, 0, zero_bytes, s));
-    HitSink sink;
-    { const int rc = make_sink(a, sink); if (rc != OVO_OK) return rc; }
+    const TrackWs w = carve_track(a->ws, nm, a->hist_cols);
+    OVO_HIP(hipMemsetAsync(w.hist, 0, w.zero_bytes, s));
     if (sink.hits) OVO_HIP(hipMemsetAsync(sink.n_hits, 0, sizeof(int32_t), s));
     const bool known = a->map.n >= 0;
     const long long *n_dev = known ? nullptr : (const long long *)a->map.state;
     const float *depth = a->depth;
     if (a->filter_depth) {
-        OVO_REQUIRE(a->depth_scratch, "depth_scratch needed for the depth filter");
-        const int rc = ovo_depth_filter(a->depth, a->cam.h, a->cam.w, 7, 2.5f, 0.05f, a->depth_scratch, stream);
-        if (rc != OVO_OK) return rc;
+        STEP_CHECK(ovo_depth_filter(a->depth, a->cam.h, a->cam.w, 7, 2.5f, 0.05f, a->depth_scratch, stream));
         depth = a->depth_scratch;
     }
     const int64_t n_grid = known ? a->map.n : a->n_upper;
@@ -1429,22 +1462,17 @@ int ovo_track_step(const ovo_track_step_t *a, ovo_stream_t stream) {
         const bool prof = ovo_prof_enabled();
         if (prof) ovo_prof_begin(2, 14.0 * (double)n_grid, s);
         k_track_project<<<ovo_grid(n_grid, 256, TRACK_GRID_CAP), 256, 0, s>>>(a->map.xyz, a->map.ins, known ? a->map.n : 0, a->cam, depth, a->seg_map, a->seg_h,
-                                                           a->seg_w, a->ratio, a->point_seg, hist, nm, a->hist_cols, counters, CNT_SLOTS, n_dev, sink);
+                                                           a->seg_w, a->ratio, a->point_seg, w.hist, nm, a->hist_cols, w.counters, CNT_SLOTS, n_dev, sink);
         if (prof) ovo_prof_end(s);
     }
     const int64_t seg_pixels = (int64_t)a->seg_h * a->seg_w;
-    k_seg_area<<<ovo_grid(seg_pixels, 256, 256), 256, nm * sizeof(int), s>>>(a->seg_map, seg_pixels, nm, stats);
-    Decide d;
-    d.res = res; d.dst = dst; d.next_ins = a->next_ins; d.next_host = a->next_ins_host; d.track_th = a->track_th; d.n_masks = nm;
-    k_vote_decide<<<nm, 256, 0, s>>>(hist, a->hist_cols, stats, tickets, d);
+    k_seg_area<<<ovo_grid(seg_pixels, 256, 256), 256, nm * sizeof(int), s>>>(a->seg_map, seg_pixels, nm, w.stats);
+    k_vote_decide<<<nm, 256, 0, s>>>(w.hist, a->hist_cols, w.stats, w.tickets, decide_args(a, w));
     if (n_grid > 0)
-        k_assign_res<<<ovo_grid(n_grid, 256, 256), 256, 0, s>>>(a->map.ins, a->point_seg, known ? a->map.n : 0, res, nm, n_dev);
-    Publish pb;
-    pb.res = res; pb.host = (volatile int32_t *)a->result_host; pb.counters = counters; pb.cnt_slots = CNT_SLOTS; pb.n_dev = (const long long *)a->map.state;
-    pb.n_host = known ? a->map.n : -1; pb.ticket = tickets + 1; pb.seq = a->seq; pb.n_ints = 8 + 6 * nm;
+        k_assign_res<<<ovo_grid(n_grid, 256, 256), 256, 0, s>>>(a->map.ins, a->point_seg, known ? a->map.n : 0, w.res, nm, n_dev);
     const long long px16 = a->masks ? a->pixels / 16 : 0;
     dim3 grid(a->masks ? ovo_grid(px16, 256, 8) : 1, nm);              // (few, fat workgroups: see k_kf_finish's launch)
-    k_fuse_publish<<<grid, 256, 0, s>>>((uint4 *)a->masks, px16, nm, dst, res, pb);
+    k_fuse_publish<<<grid, 256, 0, s>>>((uint4 *)a->masks, px16, nm, w.dst, w.res, publish_args(a, w, known ? a->map.n : -1));
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }
@@ -1479,16 +1507,12 @@ int ovo_round_chain(ovo_round_chain_t *ctx, const ovo_map_step_t *maps, const ov
         c.xyz = mr.xyz; c.ids = mr.ids; c.ins = mr.ins; c.rgb_out = mr.rgb; c.cap = mr.cap; c.state = (long long *)mr.state;
         c.n_host = mr.n; c.id_host = mr.next_id;
         if (c.do_map) {
-            OVO_REQUIRE(a->map.ids && a->explained && a->ws && a->h > 0 && a->w > 0 && a->ds >= 1, "bad map step");
-            const int64_t ws_w = (a->w + a->ds - 1) / a->ds;
-            c.n_sub = (int64_t)((a->h + a->ds - 1) / a->ds) * ws_w;
+            int64_t n_sub;
+            STEP_CHECK(check_map_step(a, n_sub, __func__));
+            c.n_sub = n_sub;
             if (((c.n_sub + 63) >> 6) > SCAN_CHUNK) { ovo_set_error("ovo_round_chain: frame too large for the one-workgroup scan"); return OVO_E_UNSUPPORTED; }
-            OVO_REQUIRE(a->ws_bytes >= ovo_compact_workspace_bytes(c.n_sub) + 8, "workspace too small");
-            OVO_REQUIRE(a->map.cap >= a->n_upper + c.n_sub, "map capacity below n_upper + one frame of points");
             c.depth = a->depth; c.rgb = a->rgb; c.cam_map = a->cam;
-            for (int i = 0; i < 9; ++i) c.bp.K[i] = a->K[i];
-            for (int i = 0; i < 16; ++i) c.bp.c2w[i] = a->c2w[i];
-            c.bp.h = a->h; c.bp.w = a->w; c.bp.ds = a->ds; c.bp.ws_w = (int)ws_w; c.bp.erode = a->erode;
+            c.bp = backproj_args(a->K, a->c2w, a->h, a->w, a->ds, a->erode);
             c.erode = a->erode;
             c.explained = a->explained;
             c.total = (long long *)a->ws;
@@ -1499,23 +1523,16 @@ int ovo_round_chain(ovo_round_chain_t *ctx, const ovo_map_step_t *maps, const ov
         if (c.do_track) {
             if (t->n_masks > CHAIN_MAX_MASKS) { ovo_set_error("ovo_round_chain: more than %d masks", CHAIN_MAX_MASKS); return OVO_E_UNSUPPORTED; }
             if (t->hits) { ovo_set_error("ovo_round_chain: no hit list in the one-launch form"); return OVO_E_UNSUPPORTED; }
-            OVO_REQUIRE(t->depth && t->seg_map && t->point_seg && t->ws && t->next_ins && t->hist_cols >= 1, "bad track step");
-            OVO_REQUIRE(t->ws_bytes >= ovo_track_workspace_bytes(t->n_masks, t->hist_cols), "workspace too small");
-            OVO_REQUIRE(!t->masks || (t->pixels > 0 && t->pixels % 16 == 0 && ((uintptr_t)t->masks & 15) == 0), "masks: pixels must be a multiple of 16");
+            HitSink none;
+            STEP_CHECK(check_track_step(t, none, __func__));
             const int nm = t->n_masks;
             if (!c.do_map) c.cam_map = t->cam;
             c.depth_t = t->depth;
             c.filter = t->filter_depth; c.depth_f = t->depth_scratch; c.filter_th = 0.05f;
-            OVO_REQUIRE(!c.filter || c.depth_f, "depth_scratch needed for the depth filter");
             c.cam = t->cam; c.ratio = t->ratio; c.seg_map = t->seg_map; c.seg_h = t->seg_h; c.seg_w = t->seg_w;
             c.masks = (uint4 *)t->masks; c.n_masks = nm; c.px16 = t->masks ? t->pixels / 16 : 0; c.point_seg = t->point_seg;
-            c.hist = (int32_t *)t->ws;
-            c.stats = c.hist + (size_t)nm * t->hist_cols;
-            c.counters = (unsigned long long *)(c.stats + 4 * (size_t)nm + ((((size_t)nm * t->hist_cols) & 1) ? 1 : 0));
-            unsigned int *tickets = (unsigned int *)(c.counters + CNT_SLOTS * CNT_STRIDE);
-            c.dst = (int32_t *)(tickets + 2 + nm);
-            c.res = c.dst + nm;
-            c.zero_bytes = (long long)((char *)c.dst - (char *)c.hist);
+            const TrackWs w = carve_track(t->ws, nm, t->hist_cols);          // (no tickets: grid barriers order the passes)
+            c.hist = w.hist; c.stats = w.stats; c.counters = w.counters; c.dst = w.dst; c.res = w.res; c.zero_bytes = (long long)w.zero_bytes;
             c.hist_cols = t->hist_cols; c.track_th = t->track_th;
             c.next_ins = t->next_ins; c.next_host = t->next_ins_host;
             c.result = (volatile int32_t *)t->result_host; c.seq = t->seq;
@@ -1537,33 +1554,22 @@ int ovo_round_chain(ovo_round_chain_t *ctx, const ovo_map_step_t *maps, const ov
 
 int ovo_keyframe_step(const ovo_map_step_t *a, const ovo_track_step_t *t, ovo_stream_t stream) {
     OVO_REQUIRE(a && t && a->depth && t->depth && t->n_masks > 0, "both halves are needed (use ovo_map_step / ovo_track_step for one)");
-    const int64_t ws_w = (a->w + a->ds - 1) / a->ds;
-    const int64_t n_sub = (int64_t)((a->h + a->ds - 1) / a->ds) * ws_w;
+    int64_t n_sub;
+    HitSink sink;
+    STEP_CHECK(check_map_step(a, n_sub, __func__));
+    STEP_CHECK(check_track_step(t, sink, __func__));
     if (((n_sub + 63) >> 6) > SCAN_CHUNK || t->n_masks > CHAIN_MAX_MASKS_V || ((size_t)a->h * a->w) % 16 != 0) {      // shapes the merged launches do not cover
-        const int rc = ovo_map_step(a, stream);
-        return rc != OVO_OK ? rc : ovo_track_step(t, stream);
+        STEP_CHECK(ovo_map_step(a, stream));
+        return ovo_track_step(t, stream);
     }
-    OVO_REQUIRE(a->map.xyz && a->map.ids && a->map.ins && a->map.state && a->explained && a->ws && t->seg_map && t->point_seg && t->ws && t->next_ins, "null argument");
-    OVO_REQUIRE(a->h > 0 && a->w > 0 && a->ds >= 1 && a->n_upper >= 0 && t->hist_cols >= 1, "bad shape");
-    OVO_REQUIRE(a->ws_bytes >= ovo_compact_workspace_bytes(n_sub) + 8 && t->ws_bytes >= ovo_track_workspace_bytes(t->n_masks, t->hist_cols), "workspace too small");
-    OVO_REQUIRE(a->map.cap >= a->n_upper + n_sub, "map capacity below n_upper + one frame of points");
-    OVO_REQUIRE(!t->masks || (t->pixels > 0 && t->pixels % 16 == 0 && ((uintptr_t)t->masks & 15) == 0), "masks: pixels must be a multiple of 16");
-    OVO_REQUIRE(!t->filter_depth || t->depth_scratch, "depth_scratch needed for the depth filter");
     OVO_REQUIRE(((uintptr_t)a->explained & 15) == 0 && ((uintptr_t)t->ws & 15) == 0, "misaligned scratch");
     hipStream_t s = (hipStream_t)stream;
     const int nm = t->n_masks;
-    int32_t *hist = (int32_t *)t->ws;
-    int32_t *stats = hist + (size_t)nm * t->hist_cols;
-    unsigned long long *counters = (unsigned long long *)(stats + 4 * (size_t)nm + ((((size_t)nm * t->hist_cols) & 1) ? 1 : 0));
-    unsigned int *tickets = (unsigned int *)(counters + CNT_SLOTS * CNT_STRIDE);
-    int32_t *dst = (int32_t *)(tickets + 2 + nm);
-    int32_t *res = dst + nm;
-    const size_t zero_bytes = ((size_t)((char *)dst - (char *)hist) + 15) & ~(size_t)15;        // (dst / res are rewritten by the decisions anyway)
+    const TrackWs w = carve_track(t->ws, nm, t->hist_cols);
+    const size_t zero_bytes = (w.zero_bytes + 15) & ~(size_t)15;        // k_kf_zero clears 16 bytes at a time (dst / res are rewritten by the decisions anyway)
     // ---- 1: zero
     KfZero z;
-    HitSink sink;
-    { const int rc = make_sink(t, sink); if (rc != OVO_OK) return rc; }
-    z.a = (uint4 *)a->explained; z.a16 = (long long)((size_t)a->h * a->w / 16); z.b = (uint4 *)hist; z.b16 = (long long)(zero_bytes / 16); z.c = sink.n_hits;
+    z.a = (uint4 *)a->explained; z.a16 = (long long)((size_t)a->h * a->w / 16); z.b = (uint4 *)w.hist; z.b16 = (long long)(zero_bytes / 16); z.c = sink.n_hits;
     k_kf_zero<<<64, 256, 0, s>>>(z);
     // ---- 2: the three independent first passes
     const bool known = a->map.n >= 0;
@@ -1577,34 +1583,25 @@ int ovo_keyframe_step(const ovo_map_step_t *a, const ovo_track_step_t *t, ovo_st
     p1.xyz = a->map.xyz; p1.n_host = known ? a->map.n : -1; p1.state = (const long long *)a->map.state; p1.cam_map = a->cam; p1.depth_map = a->depth;
     p1.explained = a->explained;
     p1.depth_t = t->depth; p1.fh = t->cam.h; p1.fw = t->cam.w; p1.filter_th = 0.05f; p1.depth_f = t->depth_scratch;
-    p1.seg_map = t->seg_map; p1.seg_pixels = seg_pixels; p1.n_masks = nm; p1.stats = stats;
+    p1.seg_map = t->seg_map; p1.seg_pixels = seg_pixels; p1.n_masks = nm; p1.stats = w.stats;
     k_kf_phase1<<<p1.g_expl + p1.g_filt + p1.g_area, 256, 0, s>>>(p1, make_blur_taps(7, 2.5f));
     // ---- 3, 4: erode + subsample -> ordered append, state commit
-    BackprojArgs b;
-    for (int i = 0; i < 9; ++i) b.K[i] = a->K[i];
-    for (int i = 0; i < 16; ++i) b.c2w[i] = a->c2w[i];
-    b.h = a->h; b.w = a->w; b.ds = a->ds; b.ws_w = (int)ws_w;
-    b.erode = a->erode && maybe_nonempty;
+    const BackprojArgs b = backproj_args(a->K, a->c2w, a->h, a->w, a->ds, a->erode && maybe_nonempty);
     CompactWs c = carve((char *)a->ws + 8, n_sub);
     const int g = ovo_grid(n_sub, 256);
     k_backproj_flag<<<g, 256, 0, s>>>(a->depth, maybe_nonempty ? a->explained : nullptr, b, n_sub, c.words, known ? nullptr : (const long long *)a->map.state);
-    MapCommit mc;
-    mc.state = (long long *)a->map.state; mc.total = nullptr; mc.result = (volatile long long *)a->result_host; mc.seq = a->seq;
-    mc.cap = a->map.cap; mc.n_host = known ? a->map.n : -1; mc.id_host = a->map.next_id;
     // (every workgroup rebuilds the scan and ends on the commit ticket: 128 of them emit a 640 x 480 frame in 9 us, 1200 in 11.5)
-    k_kf_emit<<<g < 128 ? g : 128, 256, 0, s>>>(a->depth, a->rgb, b, n_sub, c.words, a->map.xyz, a->map.ids, a->map.ins, a->map.rgb, mc);
+    k_kf_emit<<<g < 128 ? g : 128, 256, 0, s>>>(a->depth, a->rgb, b, n_sub, c.words, a->map.xyz, a->map.ids, a->map.ins, a->map.rgb, map_commit(a, nullptr));
     // ---- 5: the tracking pass (the map's size after the append is device-resident in any case)
     const float *depth = t->filter_depth ? t->depth_scratch : t->depth;
     const int64_t n_grid = a->n_upper + n_sub;
     const bool prof = ovo_prof_enabled();
     if (prof) ovo_prof_begin(2, 14.0 * (double)n_grid, s);
-    k_track_project<<<ovo_grid(n_grid, 256, TRACK_GRID_CAP), 256, 0, s>>>(t->map.xyz, t->map.ins, 0, t->cam, depth, t->seg_map, t->seg_h, t->seg_w, t->ratio, t->point_seg, hist, nm,
-                                                       t->hist_cols, counters, CNT_SLOTS, (const long long *)t->map.state, sink);
+    k_track_project<<<ovo_grid(n_grid, 256, TRACK_GRID_CAP), 256, 0, s>>>(t->map.xyz, t->map.ins, 0, t->cam, depth, t->seg_map, t->seg_h, t->seg_w, t->ratio, t->point_seg, w.hist, nm,
+                                                       t->hist_cols, w.counters, CNT_SLOTS, (const long long *)t->map.state, sink);
     if (prof) ovo_prof_end(s);
     // ---- 6: vote statistics + decisions
-    Decide d;
-    d.res = res; d.dst = dst; d.next_ins = t->next_ins; d.next_host = t->next_ins_host; d.track_th = t->track_th; d.n_masks = nm;
-    k_vote_decide<<<nm, 256, 0, s>>>(hist, t->hist_cols, stats, tickets, d);
+    k_vote_decide<<<nm, 256, 0, s>>>(w.hist, t->hist_cols, w.stats, w.tickets, decide_args(t, w));
     // ---- 7: assignment | mask fusion, publish
     KfFinish f;
     // few, fat workgroups: every one of them pays a fixed chain of dependent loads (map size, targets / dst), a fence and its ticket, and beyond the
@@ -1612,11 +1609,8 @@ int ovo_keyframe_step(const ovo_map_step_t *a, const ovo_track_step_t *t, ovo_st
     // 21.8, 128 + 32 x 4 22.9, 4096 + 32 x 32 118 (rocprofv3 over tools/round_profile.py with NOSAM=1)
     f.g_assign = ovo_grid(n_grid, 256, 256); f.gx = t->masks ? ovo_grid(t->pixels / 16, 256, 8) : 1;
     f.ins = t->map.ins; f.point_seg = t->point_seg; f.n_host = -1; f.n_dev = (const long long *)t->map.state;
-    f.masks = (uint4 *)t->masks; f.px16 = t->masks ? t->pixels / 16 : 0; f.n_masks = nm; f.dst = dst; f.res = res;
-    Publish pb;
-    pb.res = res; pb.host = (volatile int32_t *)t->result_host; pb.counters = counters; pb.cnt_slots = CNT_SLOTS; pb.n_dev = (const long long *)t->map.state; pb.n_host = -1;
-    pb.ticket = tickets + 1; pb.seq = t->seq; pb.n_ints = 8 + 6 * nm;
-    k_kf_finish<<<f.g_assign + (t->masks ? f.gx * nm : 0), 256, 0, s>>>(f, pb);
+    f.masks = (uint4 *)t->masks; f.px16 = t->masks ? t->pixels / 16 : 0; f.n_masks = nm; f.dst = w.dst; f.res = w.res;
+    k_kf_finish<<<f.g_assign + (t->masks ? f.gx * nm : 0), 256, 0, s>>>(f, publish_args(t, w, -1));
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }

@@ -246,6 +246,89 @@ def test_many_masks_per_keyframe_device_vs_host_decisions(mode):
     assert max(n_masks) > 64, n_masks
 
 
+def _small_keyframe(call):
+    """One keyframe of 30 x 36 depth pixels (1080: not a multiple of 16, so `ovo_keyframe_step` hands it to the single steps) at ds = 1 over a map of 356
+    points in front of the camera, those of the top ten rows on the depth surface; 3 masks (a 1 x 3 grid seg map), no binary masks.  The two steps are filled
+    the way `VanillaMapper.map_launch(defer=True)` and `OVO.track_launch(defer=True)` fill them and handed to `call`; returns every output."""
+    from ovo_amd import _lib as L
+    from ovo_amd.utils import geometry_utils as G
+    lib = L.load()
+    h, w, n_masks, next_ins = 30, 36, 3, 3
+    K = np.array([[30, 0, 17.5], [0, 30, 14.5], [0, 0, 1]], np.float32)
+    v, u = np.mgrid[:h, :w]
+    depth = (2.0 + 0.02 * u + 0.03 * v).astype(np.float32)
+    depth[4:7, 5:9] = 0                                                          # a hole
+    old = ((u + v) % 3 == 0) & (depth > 0)
+    n0, n_sub = int(old.sum()), h * w
+    z = depth[old] + np.where(v[old] < 10, 0.0, 0.3).astype(np.float32)
+    pts = np.stack([(u[old] - K[0, 2]) / K[0, 0] * z, (v[old] - K[1, 2]) / K[1, 1] * z, z], 1).astype(np.float32)
+    cap = n0 + n_sub
+    xyz, ids, ins = torch.zeros((cap, 3), device=DEV), torch.full((cap,), -1, dtype=torch.int32, device=DEV), torch.full((cap,), -1, dtype=torch.int32, device=DEV)
+    rgb_out = torch.zeros((cap, 3), dtype=torch.uint8, device=DEV)
+    xyz[:n0], ids[:n0] = _t(pts), torch.arange(n0, dtype=torch.int32, device=DEV)
+    ins[:n0] = _t(np.where(np.arange(n0) % 4 == 0, -1, np.arange(n0) % next_ins).astype(np.int32))
+    state = torch.tensor([n0, n0, 0, 0], dtype=torch.int64, device=DEV)          # {n, next point id, flags, ticket}
+    d_depth, d_rgb = _t(depth), _t(np.random.default_rng(2).integers(0, 256, (h, w, 3), dtype=np.uint8))
+    pose, K_host = torch.eye(4), torch.from_numpy(K)
+    near, far = G.depth_range(depth)
+    map_ring, track_ring = L.PinnedRing(4, np.int64, 4), L.PinnedRing(8 + 6 * n_masks, np.int32, 4)
+    # the map step: the host knows the map's size exactly (nothing is in flight)
+    a = L.MapStep()
+    a.map = L.MapRef(xyz.data_ptr(), ids.data_ptr(), ins.data_ptr(), rgb_out.data_ptr(), cap, state.data_ptr(), n0, n0)
+    a.depth, a.rgb, a.h, a.w = d_depth.data_ptr(), d_rgb.data_ptr(), h, w
+    a.cam = G.frame_camera(near, far, h, w, pose, K_host, 0.03)
+    a.K = (L.C.c_float * 9)(*K.reshape(-1).tolist())
+    a.c2w[:] = pose.reshape(-1).tolist()
+    a.ds, a.erode, a.n_upper = 1, 1, n0
+    explained = torch.empty(h * w, dtype=torch.uint8, device=DEV)
+    map_ws = torch.empty(lib.ovo_compact_workspace_bytes(n_sub) + 8, dtype=torch.uint8, device=DEV)
+    a.explained, a.ws, a.ws_bytes = explained.data_ptr(), map_ws.data_ptr(), map_ws.numel()
+    a.seq, a.result_host = map_ring.next()
+    # the tracking step behind it: the map's size is read on the device
+    t = L.TrackStep()
+    t.map = L.MapRef(xyz.data_ptr(), ids.data_ptr(), ins.data_ptr(), rgb_out.data_ptr(), cap, state.data_ptr(), -1, -1)
+    t.n_upper = n0 + n_sub
+    t.cam = G.frame_camera(near, far, h, w, pose, K_host, 0.05)
+    scratch = torch.empty(h * w, dtype=torch.float32, device=DEV)
+    t.depth, t.filter_depth, t.depth_scratch = d_depth.data_ptr(), 1, scratch.data_ptr()
+    seg = _t((u // 12).astype(np.int32))
+    t.seg_map, t.seg_h, t.seg_w = seg.data_ptr(), h, w
+    t.masks, t.n_masks, t.pixels = None, n_masks, 0
+    t.ratio = L.Ratio(0, 1.0, 1.0, 0)
+    t.hist_cols, t.track_th = next_ins + 1, 5
+    point_seg = torch.full((n0 + n_sub,), -7, dtype=torch.int16, device=DEV)
+    t.point_seg = point_seg.data_ptr()
+    track_ws = torch.empty(lib.ovo_track_workspace_bytes(n_masks, t.hist_cols), dtype=torch.uint8, device=DEV)
+    t.ws, t.ws_bytes = track_ws.data_ptr(), track_ws.numel()
+    d_next = torch.tensor([next_ins], dtype=torch.int32, device=DEV)
+    t.next_ins, t.next_ins_host = d_next.data_ptr(), next_ins
+    t.seq, t.result_host = track_ring.next()
+    call(lib, a, t)
+    torch.cuda.synchronize()
+    return {"xyz": xyz.cpu(), "ids": ids.cpu(), "ins": ins.cpu(), "rgb": rgb_out.cpu(), "point_seg": point_seg.cpu(), "state": state.cpu(),
+            "next_ins": d_next.cpu(), "map_result": torch.from_numpy(map_ring.wait(a.seq).copy()), "track_result": torch.from_numpy(track_ring.wait(t.seq).copy())}
+
+
+def test_keyframe_step_on_a_shape_it_hands_on_equals_the_two_single_steps():
+    """`ovo_keyframe_step` on a frame whose pixel count is no multiple of 16 validates both halves and then runs `ovo_map_step` + `ovo_track_step`: every
+    output -- points, ids, instances, colours, the points' masks, the map state, both result blocks -- equals the two calls on fresh copies, bit for bit."""
+    from ovo_amd import _lib as L
+
+    def single(lib, a, t):
+        L.check(lib.ovo_map_step(L.C.byref(a), L.stream()))
+        L.check(lib.ovo_track_step(L.C.byref(t), L.stream()))
+
+    one = _small_keyframe(lambda lib, a, t: L.check(lib.ovo_keyframe_step(L.C.byref(a), L.C.byref(t), L.stream())))
+    two = _small_keyframe(single)
+    for k in one:
+        assert torch.equal(one[k], two[k]), k
+    seq, appended, n_after, next_id = two["map_result"].tolist()
+    assert seq == 1 and 100 < appended < 1080 and n_after == 356 + appended == next_id == int(two["state"][0])     # the surface points explain their pixels
+    res = two["track_result"]
+    assert int(res[0]) == 1 and int(res[8::6].sum()) > 150 and (res[12::6] >= 0).all()       # every mask matched points and got an instance
+    assert (two["ins"][356:n_after] >= 0).sum() > 100                                            # ... which the new points received
+
+
 # ------------------------------------------------------------------ oracle at full size
 def _scene(n_points, scale=1.0, t=2, seed=5):
     from ovo_amd import synthetic as syn
