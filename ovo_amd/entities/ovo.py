@@ -18,7 +18,7 @@ keys.  What changed underneath:
 """
 from __future__ import annotations
 
-import os
+import contextlib
 import time
 from collections import deque
 from typing import Any, Dict, List, Optional, Tuple
@@ -28,9 +28,9 @@ import torch
 
 from .. import _lib as L
 from ..utils import geometry_utils as G
-from ..utils.streams import side_stream
 from .descriptor_bank import DescriptorBank, KeyframeView
 from .instance3d import Instance3D
+from .token_lookahead import TokenLookahead
 
 
 def _timed(slot: str):
@@ -50,11 +50,6 @@ def _timed(slot: str):
 
 
 class OVO:
-    _vit_stream = None      # side stream + pending result of prefetch_image_features()
-    _prefetched = None
-    _tokens_free = None     # recorded on the main stream after the pooling that last read the ViT workspace
-    _batch_slots = None     # prefetch_image_features_batch: two token buffers (double-buffered batches)
-
     def __init__(self, config: Dict[str, Any], logger=None, scene_name: Optional[str] = None,
                  cam_intrinsics: Optional[torch.Tensor] = None, eval: bool = False, device="cuda",
                  clip_generator=None, mask_generator=None) -> None:
@@ -88,7 +83,7 @@ class OVO:
         self.bank = DescriptorBank(self.clip_generator.clip_dim, device)
         self.keyframes = {"ins_descriptors": dict(), "frame_id": list(), "ins_maps": list()}
         self.keyframes_queue = deque([])
-        self._prefetched_batch: Dict[int, tuple] = {}
+        self.lookahead: Optional[TokenLookahead] = None   # ViT tokens computed ahead of `_extract_clip` (made by the first prefetch call)
         self._planned_kfs: set = set()                # keyframes whose descriptors are planned (rows decided) but not stored yet
         self.objects: Dict[int, Instance3D] = dict()
         self._time_cache: List[float] = []
@@ -206,9 +201,8 @@ class OVO:
         on the CURRENT stream so far (its inputs and buffers are allocated here), and `track_finish` makes the current stream wait for it.
         `defer`: do not launch; the `ovo_track_step_t` is left in the record (`pend["step"]`) for the caller's `ovo_round_chain`, who also
         sets `pend["done"]`."""
-        image, depth_in, ratio = frame_data
         lib = L.load()
-        h, w = depth_in.shape
+        h, w = frame_data[1].shape
         if self._track_ring is None:
             self._track_ring = L.PinnedRing(8 + 6 * self.MAX_RESULT_MASKS, np.int32, getattr(self, "_track_ring_slots", 32))
         a = L.TrackStep()
@@ -231,24 +225,16 @@ class OVO:
             self._next_ins_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         if len(self._track_pending) >= self._track_ring.slots - 1:
             raise L.OvoHipError("too many keyframes queued without track_finish")
-        depth = G.to_device(depth_in, torch.float32, dev)
-        pose = self._pose_host(c2w)
-        near, far = G.depth_range(depth_in)                       # frustum uses the raw depth (:209)
-        a.cam = G.frame_camera(near, far, h, w, pose, self._K_host, self.config["match_distance_th"])
+        depth, a.cam, a.ratio, seg_map, a.hist_cols = self._track_inputs(frame_data, c2w, seg_map, dev)
         a.depth = depth.data_ptr()
-        if self.config.get("depth_filter", False):
+        if self.config.get("depth_filter", False):                # filtered in the chain, into a scratch image
             scratch = getattr(self, "_depth_scratch", None)
             if scratch is None or scratch.numel() < h * w or scratch.device != depth.device:
                 scratch = self._depth_scratch = torch.empty(h * w, dtype=torch.float32, device=dev)
             a.filter_depth, a.depth_scratch = 1, scratch.data_ptr()
-        seg_map = L.dev(seg_map, torch.int32, "seg_map")
         n_masks = int(binary_maps.shape[0])
         a.seg_map, a.seg_h, a.seg_w = seg_map.data_ptr(), seg_map.shape[0], seg_map.shape[1]
         a.masks, a.n_masks, a.pixels = binary_maps.data_ptr(), n_masks, binary_maps[0].numel()
-        a.ratio = L.Ratio(1, float(ratio[0]), float(ratio[1]), int(ratio[2])) if len(ratio) > 0 else L.Ratio(0, 1.0, 1.0, 0)
-        queued_masks = sum(p["n_masks"] for p in self._track_pending)
-        # votes table columns: [unassigned | instance 0 .. max id]; ids the queued keyframes may still allocate are covered
-        a.hist_cols = max(self.next_ins_id + queued_masks, max(self.objects) + 1 if self.objects else 0) + 1
         a.track_th = int(self.config["track_th"])
         point_seg = torch.empty((max(int(a.n_upper), 1) + 0xfffff) & ~0xfffff, dtype=torch.int16, device=dev)    # 1 Mi-point steps: the allocator re-uses blocks
         a.point_seg = point_seg.data_ptr()
@@ -306,40 +292,9 @@ class OVO:
         kf_id, n_masks = self.kf_id, pend["n_masks"]
         n, n_matched, next_after = int(res[1]), int(res[3]), int(res[4])
         table = res[8:8 + 6 * n_masks].reshape(n_masks, 6).tolist()
-        track_th = self.config["track_th"]
-        objects = self.objects
-        matched_info: Dict[int, List[Tuple[int, int]]] = {}
-        for m, (n_pts, n_assigned, mode_id, area, target, _) in enumerate(table):
-            if n_pts <= track_th:
-                continue
-            if n_assigned > track_th:
-                objects[mode_id].observe(kf_id, area)
-                hits = matched_info.get(mode_id)
-                if hits is None:
-                    matched_info[mode_id] = [(m, area)]
-                else:
-                    hits.append((m, area))
-            elif n_pts - n_assigned > track_th:
-                new_id = self.next_ins_id
-                self.next_ins_id += 1
-                if target != new_id:
-                    raise L.OvoHipError(f"instance ids diverged between host and device ({target} vs {new_id})")
-                objects[new_id] = Instance3D(new_id, kf_id=kf_id, points_ids=[], mask_area=area, bank=self.bank)
-                matched_info[new_id] = [(m, area)]
-        if next_after != self.next_ins_id:
-            raise L.OvoHipError(f"next instance id diverged between host and device ({next_after} vs {self.next_ins_id})")
+        matched_info, _ = self._walk_masks(table, kf_id, next_after)
         binary_maps = pend["binary_maps"]                       # fused in place by the chain (ovo.py:303)
-        matched_ins_ids, keep_rows = [], []
-        mask_rows = [-1] * n_masks
-        for ins_id, hits in matched_info.items():
-            first = hits[0][0]
-            if len(hits) > 1 and self.n_top_views > 0:           # fused areas feed the top-k view heap (:305-309)
-                self.objects[ins_id].add_top_kf(kf_id, int(table[first][5]))
-            if self.n_top_views <= 0 or self.objects[ins_id].is_top_kf(kf_id):
-                for m, _ in hits:
-                    mask_rows[m] = len(matched_ins_ids)
-                matched_ins_ids.append(ins_id)
-                keep_rows.append(first)
+        matched_ins_ids, keep_rows, mask_rows = self._keep_rows(matched_info, kf_id, n_masks, lambda first: table[first][5])
         kept = L.gather_rows(binary_maps, keep_rows) if want_maps else None
         slam = pend["slam"]
         updated = pend["ins"] if slam is None else slam._ins[:n]
@@ -347,33 +302,80 @@ class OVO:
         self.last_hits = pend["hits"]
         return matched_ins_ids, kept, n_matched, updated
 
+    def _track_inputs(self, frame_data, c2w, seg_map: torch.Tensor, dev):
+        """What tracking one keyframe needs of the frame, on either decision path: (depth f32[h, w] on `dev`, camera struct, Ratio, seg map
+        i32 on the device, columns of the vote table).  The pose goes through the host for the frustum set-up (a CPU tensor costs nothing, a
+        device tensor one 64-byte D2H)."""
+        _, depth_in, ratio = frame_data
+        h, w = depth_in.shape
+        depth = G.to_device(depth_in, torch.float32, dev)
+        near, far = G.depth_range(depth_in)                       # frustum uses the raw depth (:209)
+        cam = G.frame_camera(near, far, h, w, G._cpu32(c2w).contiguous(), self._K_host, self.config["match_distance_th"])
+        r = L.Ratio(1, float(ratio[0]), float(ratio[1]), int(ratio[2])) if len(ratio) > 0 else L.Ratio(0, 1.0, 1.0, 0)
+        # votes table columns: [unassigned | instance 0 .. max id]; ids the queued keyframes may still allocate are covered (restore_dict leaves
+        # next_ins_id at 0 like the reference: hence the instances' own maximum)
+        queued_masks = sum(p["n_masks"] for p in self._track_pending)
+        hist_cols = max(self.next_ins_id + queued_masks, max(self.objects) + 1 if self.objects else 0) + 1
+        return depth, cam, r, L.dev(seg_map, torch.int32, "seg_map"), hist_cols
+
+    def _walk_masks(self, table, kf_id: int, device_next: Optional[int] = None):
+        """The decisions of ovo.py:255-280 on the per-mask table, in mask order: rows (points, assigned points, their mode instance, mask
+        area) from `ovo_vote_stats`, or with the device's own decision behind them (target id of a NEW instance, fused area) from
+        `ovo_track_step` -- the ids allocated here must then be the device's, and `device_next` its next free id.
+        Returns ({instance: [(mask, area), ...]}, instance per mask or -1)."""
+        track_th = self.config["track_th"]
+        objects = self.objects
+        matched_info: Dict[int, List[Tuple[int, int]]] = {}
+        target = [-1] * len(table)
+        for m, (n_pts, n_assigned, mode_id, area, *device) in enumerate(table):
+            if n_pts <= track_th:
+                continue
+            if n_assigned > track_th:
+                target[m] = mode_id
+                objects[mode_id].observe(kf_id, area)
+                matched_info.setdefault(mode_id, []).append((m, area))
+            elif n_pts - n_assigned > track_th:
+                target[m] = new_id = self.next_ins_id
+                self.next_ins_id += 1
+                if device and device[0] != new_id:
+                    raise L.OvoHipError(f"instance ids diverged between host and device ({device[0]} vs {new_id})")
+                objects[new_id] = Instance3D(new_id, kf_id=kf_id, points_ids=[], mask_area=area, bank=self.bank)
+                matched_info[new_id] = [(m, area)]
+        if device_next is not None and device_next != self.next_ins_id:
+            raise L.OvoHipError(f"next instance id diverged between host and device ({device_next} vs {self.next_ins_id})")
+        return matched_info, target
+
+    def _keep_rows(self, matched_info, kf_id: int, n_masks: int, fused_area):
+        """The bookkeeping of ovo.py:299-322 once the masks of one instance are fused into its first mask: `fused_area(first mask)` feeds the
+        top-k view heap (:305-309), and an instance keeps a row only while this keyframe is among its top views.  Returns (matched instance
+        ids, the mask row each keeps, per ORIGINAL mask index the kept row it contributes to or -1 -- for the dense accumulator)."""
+        matched_ins_ids, keep_rows = [], []
+        mask_rows = [-1] * n_masks
+        for ins_id, hits in matched_info.items():
+            first = hits[0][0]
+            if len(hits) > 1 and self.n_top_views > 0:
+                self.objects[ins_id].add_top_kf(kf_id, int(fused_area(first)))
+            if self.n_top_views <= 0 or self.objects[ins_id].is_top_kf(kf_id):
+                for m, _ in hits:
+                    mask_rows[m] = len(matched_ins_ids)
+                matched_ins_ids.append(ins_id)
+                keep_rows.append(first)
+        return matched_ins_ids, keep_rows, mask_rows
+
     def _match_and_track_instances_host(self, frame_data, map_data, c2w, seg_map: torch.Tensor, binary_maps: torch.Tensor):
         """The same stage with the decisions of ovo.py:255-280 taken on the host from the vote statistics (one D2H of 16 B per mask):
         debug exports, odd mask sizes, restored checkpoints (`_native_ok`)."""
         kf_id = self.kf_id
-        image, depth_in, ratio = frame_data
         points_3d, points_ids, points_ins_ids = map_data
         dev = points_3d.device
         lib = L.load()
-
-        h, w = depth_in.shape
-        depth = G.to_device(depth_in, torch.float32, dev)
-        pose = self._pose_host(c2w)
-        near, far = G.depth_range(depth_in)                       # frustum uses the raw depth (:209)
-        cam = G.frame_camera(near, far, h, w, pose, self._K_host, self.config["match_distance_th"])
+        depth, cam, r, seg_map, hist_cols = self._track_inputs(frame_data, c2w, seg_map, dev)
         if self.config.get("depth_filter", False):
             depth = G.depth_filter(depth)
 
         pts = L.dev(points_3d, torch.float32, "points_3d")
         ins = L.dev(points_ins_ids.reshape(-1), torch.int32, "points_ins_ids")
-        seg_map = L.dev(seg_map, torch.int32, "seg_map")
         n, n_masks = pts.shape[0], int(binary_maps.shape[0])
-        # votes table columns: [unassigned | instance 0 .. max id]; restore_dict leaves next_ins_id at 0 like the reference
-        hist_cols = max(self.next_ins_id, max(self.objects) + 1 if self.objects else 0) + 1
-        r = L.Ratio(0, 1.0, 1.0, 0)
-        if len(ratio) > 0:
-            r = L.Ratio(1, float(ratio[0]), float(ratio[1]), int(ratio[2]))
-
         point_seg = torch.empty(n, dtype=torch.int16, device=dev)
         hist = torch.empty((n_masks, hist_cols), dtype=torch.int32, device=dev)
         small = torch.empty(n_masks * 4 + 4, dtype=torch.int32, device=dev)        # stats | {in frustum, matched} as i64
@@ -383,30 +385,8 @@ class OVO:
                                       L.ptr(counters), L.stream()))
         L.check(lib.ovo_vote_stats(L.ptr(hist), n_masks, hist_cols, L.ptr(seg_map), seg_map.numel(), L.ptr(stats), L.stream()))
         host = small.cpu()                                           # the one sync of the tracking stage
-        table = host[:n_masks * 4].view(n_masks, 4).tolist()
         n_matched = int(host[n_masks * 4:].view(torch.int64)[1])
-
-        # ---- host decisions on the [n_masks x 4] table, in mask order (ovo.py:255-280)
-        track_th = self.config["track_th"]
-        target = [-1] * n_masks
-        matched_info: Dict[int, List[Tuple[int, int]]] = {}
-        fresh_masks: List[Tuple[int, int]] = []
-        for m, (n_pts, n_assigned, mode_id, area) in enumerate(table):
-            if n_pts <= track_th:
-                continue
-            n_fresh = n_pts - n_assigned
-            if n_assigned > track_th:
-                target[m] = mode_id
-                self.objects[mode_id].update([], kf_id, area)
-                matched_info.setdefault(mode_id, []).append((m, area))
-                fresh_masks.append((m, mode_id))
-            elif n_fresh > track_th:
-                new_id = self.next_ins_id
-                self.next_ins_id += 1
-                target[m] = new_id
-                self.objects[new_id] = Instance3D(new_id, kf_id=kf_id, points_ids=[], mask_area=area, bank=self.bank)
-                matched_info[new_id] = [(m, area)]
-                fresh_masks.append((m, new_id))
+        matched_info, target = self._walk_masks(host[:n_masks * 4].view(n_masks, 4).tolist(), kf_id)
 
         mask_target = torch.tensor(target, dtype=torch.int32).to(dev, non_blocking=True)
         updated = torch.empty_like(ins)
@@ -415,11 +395,17 @@ class OVO:
         if self.debug_info:                                        # point-id lists are only exported in debug checkpoints
             pid = points_ids.reshape(-1)
             was_free = ins == -1
-            for m, ins_id in fresh_masks:
-                sel = torch.nonzero((point_seg == m) & was_free).reshape(-1)
-                self.objects[ins_id].add_points_ids(pid[sel].reshape(-1, 1).cpu().tolist())
+            for m, ins_id in enumerate(target):
+                if ins_id >= 0:
+                    sel = torch.nonzero((point_seg == m) & was_free).reshape(-1)
+                    self.objects[ins_id].add_points_ids(pid[sel].reshape(-1, 1).cpu().tolist())
 
-        matched_ins_ids, binary_maps, mask_rows = self._fuse_masks_with_same_ins_id(binary_maps, matched_info, kf_id)
+        fused_area = self._fuse_masks_with_same_ins_id(binary_maps, matched_info)
+        matched_ins_ids, keep_rows, mask_rows = self._keep_rows(matched_info, kf_id, n_masks, fused_area.__getitem__)
+        if binary_maps[0].numel() % 16 == 0 and binary_maps.is_contiguous():
+            binary_maps = L.gather_rows(binary_maps, keep_rows)
+        else:
+            binary_maps = binary_maps.index_select(0, torch.tensor(keep_rows, dtype=torch.int64).to(binary_maps.device, non_blocking=True))
         self.last_point_seg, self.last_mask_rows = point_seg, mask_rows
         self.last_hits = None
 
@@ -430,49 +416,28 @@ class OVO:
             self.keyframes["ins_maps"].append(ins_maps.cpu().numpy())
         return matched_ins_ids, binary_maps, n_matched, updated
 
-    @staticmethod
-    def _pose_host(c2w) -> torch.Tensor:
-        """4x4 pose on the host for the frustum set-up (a CPU tensor costs nothing, a device tensor one 64-byte D2H)."""
-        return G._cpu32(c2w).contiguous()
-
-    def _fuse_masks_with_same_ins_id(self, binary_maps: torch.Tensor, matched_info, kf_id: int):
-        """Reference: ovo.py:284-324.  Also returns, per ORIGINAL mask index, the row of the fused descriptor
-        it contributes to (-1 = dropped) for the dense accumulator."""
+    def _fuse_masks_with_same_ins_id(self, binary_maps: torch.Tensor, matched_info) -> Dict[int, int]:
+        """The ORs of ovo.py:299-306: every further mask of an instance is fused into its first one, in place.  Returns {first mask: fused
+        area} when the top-k view heap wants the areas (n_top_views > 0)."""
         lib = L.load()
-        n_all = int(binary_maps.shape[0])
-        pixels = binary_maps[0].numel() if n_all else 0
+        pixels = binary_maps[0].numel() if binary_maps.shape[0] else 0
         maps_u8 = binary_maps.view(torch.uint8) if binary_maps.dtype == torch.bool else binary_maps
         pairs = [(hits[0][0], other) for hits in matched_info.values() for other, _ in hits[1:]]
-        fused_area = {}
-        if pairs and (pixels % 16 != 0 or not binary_maps.is_contiguous()):      # odd image sizes: plain torch
+        dst = sorted({d for d, _ in pairs}) if self.n_top_views > 0 else []
+        if not pairs:
+            return {}
+        if pixels % 16 != 0 or not binary_maps.is_contiguous():     # odd image sizes: plain torch
             for d, s in pairs:
                 binary_maps[d].logical_or_(binary_maps[s])
-            if self.n_top_views > 0:
-                fused_area = {d: int(binary_maps[d].sum().item()) for d in {d for d, _ in pairs}}
-        elif pairs:                                             # all ORs of the keyframe in one launch
-            flat = torch.tensor(pairs, dtype=torch.int32).reshape(-1).to(maps_u8.device, non_blocking=True)
-            L.check(lib.ovo_mask_or(L.ptr(maps_u8), pixels, L.ptr(flat), len(pairs), L.stream()))
-            if self.n_top_views > 0:                           # fused areas feed the top-k view heap (:305-309)
-                dst = sorted({d for d, _ in pairs})
-                rows = torch.tensor(dst, dtype=torch.int32).to(maps_u8.device, non_blocking=True)
-                area = torch.empty(len(dst), dtype=torch.int32, device=maps_u8.device)
-                L.check(lib.ovo_mask_area(L.ptr(maps_u8), pixels, L.ptr(rows), len(dst), L.ptr(area), L.stream()))
-                fused_area = dict(zip(dst, area.tolist()))
-        matched_ins_ids, keep_rows = [], []
-        mask_rows = [-1] * n_all
-        for ins_id, hits in matched_info.items():
-            first = hits[0][0]
-            if len(hits) > 1 and self.n_top_views > 0:
-                self.objects[ins_id].add_top_kf(kf_id, int(fused_area[first]))
-            if self.n_top_views <= 0 or self.objects[ins_id].is_top_kf(kf_id):
-                for m, _ in hits:
-                    mask_rows[m] = len(matched_ins_ids)
-                matched_ins_ids.append(ins_id)
-                keep_rows.append(first)
-        if pixels % 16 == 0 and binary_maps.is_contiguous():
-            return matched_ins_ids, L.gather_rows(binary_maps, keep_rows), mask_rows
-        idx = torch.tensor(keep_rows, dtype=torch.int64).to(binary_maps.device, non_blocking=True)
-        return matched_ins_ids, binary_maps.index_select(0, idx), mask_rows
+            return {d: int(binary_maps[d].sum().item()) for d in dst}
+        flat = torch.tensor(pairs, dtype=torch.int32).reshape(-1).to(maps_u8.device, non_blocking=True)
+        L.check(lib.ovo_mask_or(L.ptr(maps_u8), pixels, L.ptr(flat), len(pairs), L.stream()))       # all ORs of the keyframe in one launch
+        if not dst:
+            return {}
+        rows = torch.tensor(dst, dtype=torch.int32).to(maps_u8.device, non_blocking=True)
+        area = torch.empty(len(dst), dtype=torch.int32, device=maps_u8.device)
+        L.check(lib.ovo_mask_area(L.ptr(maps_u8), pixels, L.ptr(rows), len(dst), L.ptr(area), L.stream()))
+        return dict(zip(dst, area.tolist()))
 
     # ------------------------------------------------------------------ descriptors
     def compute_semantic_info(self) -> None:
@@ -594,133 +559,52 @@ class OVO:
                     merged = {ins_id: [new, before]}
         self.bank.fuse_add([(i, r, b) for i, (r, b) in merged.items()])
 
-    def prefetch_image_features(self, image, image_ready=None) -> bool:
-        """MI355X extension (no counterpart in the reference): start the mask-independent half of `_extract_clip` -- the
-        TextRegion crops' ViT forward (textregion.py:141-142 via :197-199) -- for `image` NOW, on a side HIP stream, so that
-        it overlaps the tracking stage (whose host decisions wait on a device->host copy) and the SAM2 encoder.  The
-        matching `_extract_clip(image, ...)` call (same image object) picks the tokens up and only pools; any other
-        image takes the ordinary path.  Returns False when the configured embed type has no such half."""
+    def _lookahead(self) -> Optional[TokenLookahead]:
+        """The look-ahead object (made on first use); None when the configured embed type has no mask-independent half."""
         tr = getattr(self.clip_generator, "textregion", None)
-        if tr is None or not isinstance(image, torch.Tensor) or not image.is_cuda:
-            return False
-        if self._vit_stream is None:
-            # (a high stream priority for this forward was measured: no effect on MI355X, 167 vs 168 frames/s)
-            self._vit_stream = side_stream(image.device, "OVO_VIT_CUS", int(os.environ.get("OVO_VIT_PRIORITY", "0")))
-        # the ViT workspace is shared between keyframes: wait for its last reader (the previous pooling), not for the whole
-        # main stream -- the previous keyframe's fusion / query tail then overlaps this forward
-        if self._tokens_free is not None:
-            self._vit_stream.wait_event(self._tokens_free)
-        else:
-            self._vit_stream.wait_stream(torch.cuda.current_stream())
-        if image_ready is not None:                               # the image's upload / producer, if it runs on another stream
-            self._vit_stream.wait_event(image_ready)
-        with torch.cuda.stream(self._vit_stream):
-            img = image.permute(2, 0, 1).contiguous()
-            feats = tr.get_img_features(img, scale=1.0 / 255.0)
-            done = torch.cuda.Event()
-            done.record(self._vit_stream)
-        self._prefetched = (image, img, feats, done)
-        return True
+        if tr is not None and self.lookahead is None:
+            self.lookahead = TokenLookahead(tr, self.bank.device)
+        return self.lookahead
+
+    def prefetch_image_features(self, image, image_ready=None) -> bool:
+        """MI355X extension (no counterpart in the reference): start the ViT forward of `image`'s TextRegion crops NOW on the look-ahead's
+        side stream (token_lookahead.py), so that it overlaps the tracking stage (whose host decisions wait on a device->host copy) and the
+        SAM2 encoder.  The matching `_extract_clip(image, ...)` call (same image object) picks the tokens up and only pools; any other image
+        takes the ordinary path and drops them.  Returns False when the configured embed type has no such half."""
+        la = self._lookahead()
+        return la is not None and la.encode_one(image, image_ready)
 
     def prefetch_image_features_batch(self, images, ready=(), stream=None) -> bool:
-        """`prefetch_image_features` for SEVERAL keyframes' images in ONE ViT forward (MI355X extension).  The reference defers a
-        keyframe's descriptors by `kf_queue_delay` keyframes (ovo.yaml:53, ovo.py:326-332), so nothing needs the tokens of one image
-        before the next images exist; encoding B images' TextRegion crops together makes the encoder GEMMs B times taller (M = B x 2 x 577
-        for PE-L/14-336 on 640x480), which is what fills 256 CUs.  Every `_extract_clip(image, ...)` of one of
-        these image objects then only pools its slice.  Token buffers are double-buffered per batch: the forward of batch k+2 waits for the
-        last pooling of batch k, batch k+1 is encoded while batch k is consumed."""
-        tr = getattr(self.clip_generator, "textregion", None)
-        images = list(images)
-        if tr is None or not images or not all(isinstance(i, torch.Tensor) and i.is_cuda for i in images):
-            return False
-        dev = images[0].device
-        if self._vit_stream is None:
-            self._vit_stream = side_stream(dev, "OVO_VIT_CUS", int(os.environ.get("OVO_VIT_PRIORITY", "0")))
-        if self._batch_slots is None:
-            self._batch_slots = [dict(batch=None, tokens=None, free=None, left=0) for _ in range(2)]
-            self._batch_next = 0
-        slot = self._batch_slots[self._batch_next]
-        self._batch_next ^= 1
-        if slot["left"] > 0:
-            raise L.OvoHipError("prefetch_image_features_batch: the batch before the previous one still has unconsumed images")
-        _, h, w = images[0].permute(2, 0, 1).shape
-        crops = tr.forward_crops(h, w)
-        nc, spec = len(crops), tr.vlm.spec
-        n = len(images) * nc
-        if slot["batch"] is None or slot["batch"].shape[0] < n:
-            slot["batch"] = torch.empty((n, 3, spec.image_size, spec.image_size), dtype=torch.float32, device=dev)
-            slot["tokens"] = torch.empty((n, spec.tokens, spec.width), dtype=torch.float32, device=dev)
-        side = stream if stream is not None else self._vit_stream   # `stream`: measurement runs that fold the streams
-        if slot["free"] is not None:
-            side.wait_event(slot["free"])                         # the last pooling that read this slot's tokens
-        for ev in ready:                                          # the images' uploads, when they are still in flight (resident images:
-            side.wait_event(ev)                                   # nothing to wait for -- and no wait on the caller's stream, whose queue
-        with torch.cuda.stream(side):                             # holds the previous keyframes' tails this forward should overlap)
-            srcs = [image if image.dtype == torch.uint8 and image.is_contiguous() else image.permute(2, 0, 1).contiguous() for image in images]   # HWC u8: read in place
-            if hasattr(tr.vlm, "preprocess_batch"):                # every frame's crops in one launch
-                tr.vlm.preprocess_batch(srcs, crops, scale=1.0 / 255.0, out=slot["batch"][:n])
-            else:
-                for k, src in enumerate(srcs):
-                    tr.vlm.preprocess(src, crops, scale=1.0 / 255.0, out=slot["batch"][k * nc:(k + 1) * nc])
-            tr.vlm.forward(slot["batch"][:n], tokens=True, out=slot["tokens"][:n])
-            done = torch.cuda.Event()
-            done.record(side)
-        slot["left"] = len(images)
-        for k, image in enumerate(images):
-            self._prefetched_batch[id(image)] = (image, slot["tokens"][k * nc:(k + 1) * nc], done, slot)
-        return True
+        """`prefetch_image_features` for SEVERAL keyframes' images in ONE ViT forward (`TokenLookahead.encode`); every `_extract_clip(image, ...)`
+        of one of these image objects then only pools its slice."""
+        la = self._lookahead()
+        return la is not None and la.encode(images, ready, stream)
 
     def discard_prefetched(self, image) -> None:
-        """A keyframe that gets no descriptor (no mask tracked, or every instance dropped by the top-k view filter) never reaches
-        `_extract_clip`: release its share of the look-ahead batch's token slot here, or the slot would stay "in use" and the forward two
-        groups later would refuse to overwrite it."""
-        hit = self._prefetched_batch.pop(id(image), None)
-        if hit is None or hit[0] is not image:
-            return
-        _, _, done, slot = hit
-        slot["left"] -= 1
-        if slot["left"] == 0:                                    # nobody read the tokens after `done`: the slot is free once they exist
-            slot["free"] = done
+        """A keyframe that never reaches `_extract_clip` gives its look-ahead tokens up."""
+        if self.lookahead is not None:
+            self.lookahead.discard(image)
 
     @_timed("t_clip")
     def _extract_clip(self, image: np.ndarray, binary_maps: torch.Tensor) -> torch.Tensor:
         """Reference: ovo.py:427-437 -- but the descriptors stay on the GPU."""
         if binary_maps is None:                                   # (pipeline.py: a keyframe another rank owns is tracked with want_maps=False)
             raise L.OvoHipError("_extract_clip: this keyframe's binary maps were not kept (track_finish(want_maps=False)): only its owner pools it")
-        hit = self._prefetched_batch.pop(id(image), None)
-        if hit is not None and hit[0] is image:                  # tokens from a batched look-ahead forward
-            _, feats, done, slot = hit
-            torch.cuda.current_stream().wait_event(done)
+        la = self.lookahead
+        feats = la.take(image) if la is not None else None
+        if feats is not None:                                    # tokens from a look-ahead forward: only pool
             tr = self.clip_generator.textregion
-            _, h, w = image.permute(2, 0, 1).shape
-            tr._crops(h, w)                                      # the tiling state of THIS image
+            tr._crops(*image.shape[:2])                          # the tiling state of THIS image
             out = tr.pe_value_with_sam2_attn(tr.get_features_mask(binary_maps), feats) if binary_maps.shape[0] > 0 else \
                 torch.empty((0, tr.out_dim), dtype=torch.float32, device=feats.device)
-            slot["left"] -= 1
-            if slot["left"] == 0:                                # last reader of this slot's tokens
-                slot["free"] = torch.cuda.Event()
-                slot["free"].record()
+            la.release(image)
             return out
-        pre, self._prefetched = self._prefetched, None
-        if pre is not None:
-            torch.cuda.current_stream().wait_event(pre[3])       # also on the ordinary path: it reuses the same workspace
-            if pre[0] is image and binary_maps.shape[0] > 0:
-                tr = self.clip_generator.textregion
-                out = tr.pe_value_with_sam2_attn(tr.get_features_mask(binary_maps), pre[2])
-                self._tokens_free = torch.cuda.Event()
-                self._tokens_free.record()
-                return out
         if isinstance(image, torch.Tensor):                      # already resident: HWC u8 -> CHW
             img = image.to(self.bank.device).permute(2, 0, 1).contiguous()
         else:
             img = torch.from_numpy(np.ascontiguousarray(image.transpose((2, 0, 1)))).to(self.bank.device, non_blocking=True)
-        out = self.clip_generator.extract_clip(img, binary_maps, self.config.get("return_all_clips", False))
-        if self._vit_stream is not None:
-            # the ordinary path ran the encoder on THIS stream in the shared workspace: a later prefetch must wait for it, not for a
-            # stale event of an earlier keyframe (and it may read `image` only after its producers on this stream)
-            self._tokens_free = torch.cuda.Event()
-            self._tokens_free.record()
-        return out
+        with la.workspace() if la is not None else contextlib.nullcontext():      # the encoder's workspace is the look-ahead's too
+            return self.clip_generator.extract_clip(img, binary_maps, self.config.get("return_all_clips", False))
 
     @_timed("t_up")
     def _store_and_fuse(self, clip_embeds: torch.Tensor, matched_ins_ids: List[int], kf_id: int, updates) -> None:

@@ -253,10 +253,8 @@ class FramePipeline:
                      for k in range(self.encoder_batch)]
             self._launch_encoders(blank)
             torch.cuda.synchronize()
-            for f in blank:
-                self.ovo._prefetched_batch.pop(id(f.rgb), None)
-            for slot in (self.ovo._batch_slots or []):
-                slot["left"], slot["free"] = 0, None
+            if self.ovo.lookahead is not None:
+                self.ovo.lookahead.reset()
         self._sam_by_frame.clear(); self._encoded.clear(); self._group_first.clear()
 
     def _launch_encoders(self, group: List[Frame]) -> None:
@@ -580,7 +578,7 @@ class FramePipeline:
 
     def join(self) -> None:
         """Make the main stream wait for the SAM2 and ViT streams (everything of the frames stepped so far)."""
-        for side in (self.sam_stream, self.ovo._vit_stream, self.chain_stream):
+        for side in (self.sam_stream, self.ovo.lookahead and self.ovo.lookahead.stream, self.chain_stream):
             if side is not None and side != torch.cuda.current_stream():
                 torch.cuda.current_stream().wait_stream(side)
 

@@ -42,7 +42,7 @@ def test_streams_do_not_change_results():
 
 
 def _check(ref, got, pipe):
-    assert pipe.ovo._vit_stream is not None, "the prefetch path did not run"
+    assert pipe.ovo.lookahead is not None and pipe.ovo.lookahead.stream is not None and pipe.ovo.lookahead.widest > 0, "the prefetch path did not run"
     assert any(r["desc"] is not None and r["desc"].shape[0] > 0 for r in ref), "fixture produced no descriptors"
     for a, b in zip(ref, got):
         assert a["n_points"] == b["n_points"] and a["n_instances"] == b["n_instances"]
@@ -69,13 +69,96 @@ def test_prefetch_falls_back_for_other_images():
     assert torch.equal(pipe.ovo._extract_clip(f0.rgb, f0.masks[:5]), d_plain)
 
 
+def _lookahead_pipe(n_frames):
+    from ovo_amd.pipeline import FramePipeline, synthetic_frames
+    pipe = FramePipeline(DEV, vit_card="tiny-pe", sam_card=None, n_map=60_000, n_text=3, scale=0.35, extra_capacity=200_000, track_th=40,
+                         dense=False)
+    return pipe.ovo, synthetic_frames(n_frames, DEV, scale=0.35, n_masks_grid=(3, 4), n_blobs=4)
+
+
+def test_single_prefetch_is_a_lookahead_of_one():
+    """The same descriptors, bit for bit, whichever way the ViT tokens reach the pooling: (a) the ordinary forward inside `_extract_clip`,
+    (b) `prefetch_image_features`, (c) a batch of one, (d) one batch of all frames consumed in order."""
+    ovo, frames = _lookahead_pipe(3)
+    plain = [ovo._extract_clip(f.rgb, f.masks[:5]) for f in frames]
+    assert ovo.lookahead is None and all(d.shape[0] == 5 and bool(d.abs().sum() > 0) for d in plain)
+    for f, d in zip(frames, plain):
+        assert ovo.prefetch_image_features(f.rgb)
+        assert torch.equal(ovo._extract_clip(f.rgb, f.masks[:5]), d)
+    for f, d in zip(frames, plain):
+        assert ovo.prefetch_image_features_batch([f.rgb])
+        assert torch.equal(ovo._extract_clip(f.rgb, f.masks[:5]), d)
+    assert ovo.lookahead.widest == 1
+    assert ovo.prefetch_image_features_batch([f.rgb for f in frames])
+    for f, d in zip(frames, plain):
+        assert torch.equal(ovo._extract_clip(f.rgb, f.masks[:5]), d)
+    assert ovo.lookahead.widest == 3 and ovo.lookahead.idle()
+
+
+def test_lookahead_mixed_order_and_workspace_ownership():
+    """No sync between the calls: a batch is encoded on the side stream, an image that is NOT in it is pooled at once (the ordinary forward, in
+    the encoder workspace the batch's forward is still using), then the batch is consumed / discarded out of step.  Every descriptor equals
+    the ordinary path's, every slot is released, and the next two batches are accepted."""
+    ovo, frames = _lookahead_pipe(4)
+    ref = [ovo._extract_clip(f.rgb, f.masks[:5]) for f in frames]
+    torch.cuda.synchronize()
+    f0, f1, f2, f3 = frames
+    assert ovo.prefetch_image_features_batch([f0.rgb, f1.rgb, f2.rgb])
+    la = ovo.lookahead
+    got3 = ovo._extract_clip(f3.rgb, f3.masks[:5])
+    got0 = ovo._extract_clip(f0.rgb, f0.masks[:5])
+    la.discard(f1.rgb)
+    got2 = ovo._extract_clip(f2.rgb, f2.masks[:5])
+    assert la.idle()
+    assert la.encode([f1.rgb, f3.rgb]) and la.encode([f0.rgb])      # the ordinary forward above now owns the workspace: these wait for it
+    got1, got3b = ovo._extract_clip(f1.rgb, f1.masks[:5]), ovo._extract_clip(f3.rgb, f3.masks[:5])
+    got0b = ovo._extract_clip(f0.rgb, f0.masks[:5])
+    torch.cuda.synchronize()
+    for got, k in ((got0, 0), (got2, 2), (got3, 3), (got1, 1), (got3b, 3), (got0b, 0)):
+        assert torch.equal(got, ref[k]), k
+    assert la.idle()
+
+
+def test_lookahead_refuses_a_third_batch_and_takes_it_after_release():
+    from ovo_amd import _lib as L
+    ovo, frames = _lookahead_pipe(5)
+    f0, f1 = frames[:2]
+    plain = ovo._extract_clip(f0.rgb, f0.masks[:5])
+    # a single prefetch nobody pools is dropped by the next one, or by the pooling of another image: it never holds a slot
+    for _ in range(2):
+        assert ovo.prefetch_image_features(f1.rgb)
+        assert torch.equal(ovo._extract_clip(f0.rgb, f0.masks[:5]), plain)
+        assert ovo.prefetch_image_features(f0.rgb)
+        assert torch.equal(ovo._extract_clip(f0.rgb, f0.masks[:5]), plain)
+    assert ovo.prefetch_image_features(f1.rgb) and ovo.prefetch_image_features(f1.rgb) and ovo.prefetch_image_features(f0.rgb)
+    la = ovo.lookahead
+    la.discard(f0.rgb)
+    assert la.idle()
+    # batches k and k + 1 pending, nothing consumed: the third is refused before anything is launched ...
+    batch_k, batch_k1, third = [f.rgb for f in frames[:2]], [f.rgb for f in frames[2:4]], [frames[4].rgb]
+    assert la.encode(batch_k) and la.encode(batch_k1)
+    with pytest.raises(L.OvoHipError):
+        la.encode(third)
+    assert la.take(third[0]) is None and la.widest == 2
+    # ... and accepted once every image of batch k is given up
+    la.discard(batch_k[0])
+    with pytest.raises(L.OvoHipError):
+        la.encode(third)
+    la.discard(batch_k[1])
+    assert la.encode(third)
+    assert torch.equal(ovo._extract_clip(third[0], frames[4].masks[:5]), ovo._extract_clip(third[0], frames[4].masks[:5]))
+    for image in batch_k1:
+        la.discard(image)
+    assert la.idle()
+
+
 def test_encoder_lookahead_batching_does_not_change_results():
     """Several keyframes' crops per ViT forward and several frames per SAM2 forward (encoder_batch = 3, one group of look-ahead): every
     descriptor, class, dense map and SAM2 feature is bit-identical to the frame-by-frame run -- a row of a GEMM / attention / LayerNorm
     does not depend on how many other rows the launch carries (same k-order in every tile shape)."""
     ref, _ = _run(prefetch=True, side_stream=True, n_frames=7)
     got, pipe = _run(prefetch=True, side_stream=True, n_frames=7, encoder_batch=3, pipelined=True)
-    assert pipe.ovo._batch_slots is not None, "the batched prefetch did not run"
+    assert pipe.ovo.lookahead is not None and pipe.ovo.lookahead.widest == 3, "the batched prefetch did not run"
     _check(ref, got, pipe)
 
 
@@ -188,8 +271,7 @@ def test_keyframe_without_descriptors_releases_its_lookahead_slot():
         frames[k] = Frame(f.index, f.rgb, f.rgb_lr, f.depth, f.c2w, torch.full_like(f.seg_map, -1), torch.zeros_like(f.masks))
     outs = [pipe.step(f, frames[i + 1:]) for i, f in enumerate(frames)]
     torch.cuda.synchronize()
-    assert not pipe.ovo._prefetched_batch                            # every prefetched image was consumed or discarded
-    assert all(s["left"] == 0 for s in pipe.ovo._batch_slots)
+    assert pipe.ovo.lookahead.widest == 2 and pipe.ovo.lookahead.idle()     # every prefetched image was consumed or discarded, no slot is in use
     assert outs[-1]["n_instances"] > 0
 
 
