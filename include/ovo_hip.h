@@ -313,6 +313,16 @@ int ovo_gemm_f32a(const ovo_gemm_t *g, const ovo_window_t *win, const float *x, 
  * (192, 192), (144, 192)) or rows < 16384: run ovo_gemm_f32a + ovo_gemm then (ovo_hiera_forward does exactly that). */
 int ovo_mlp_f32(float *x, int64_t rows, int d, const float *ln_g, const float *ln_b, float eps, const void *w1, int64_t ldw1,
                 const float *b1, int hidden, const void *w2, int64_t ldw2, const float *b2, ovo_stream_t stream);
+/* An FPN level of the SAM2 neck with the mask decoder's high-resolution convolution behind it, in ONE launch (FpnNeck's lateral 1 x 1
+ * convolution of level 0 / 1, then conv_s0 / conv_s1; ABI v16):
+ *     out[r, :] = W2 . bf16(W1 . bf16(x[r, :]) + b1) + b2
+ * x f32 [rows, d], W1 bf16 [hidden, ldw1 >= d] (columns >= d zero), W2 bf16 [n_out, ldw2 >= hidden], out f32 [rows, n_out] (out of place; x, out
+ * and the weights 16-byte aligned).  The hidden-wide lateral never reaches memory (as two products it is 2 x rows x hidden x 4 bytes of HBM
+ * traffic) and the result has the bits of the two products: the same roundings, the same sums.
+ * Returns OVO_E_UNSUPPORTED -- nothing launched -- unless (d, ldw1, hidden, n_out) is (112, 128, 256, 32) or (224, 256, 256, 64) and
+ * rows >= 16384: run ovo_gemm_f32a twice then (ovo_hiera_forward does exactly that). */
+int ovo_neck_f32(const float *x, int64_t rows, int d, const void *w1, int64_t ldw1, const float *b1, int hidden, const void *w2, int64_t ldw2,
+                 const float *b2, float *out, int n_out, ovo_stream_t stream);
 /* The attention half of a Hiera block of 8 x 8 (4 x 4) windows up to its output projection without the q | k | v tensor (sam2 `MultiScaleAttention` on
  * windowed tokens, reached at mask_generator.py:113; ABI v10): per window and head
  *     att[window-major row, head * hd + :] = softmax(q k^T) v,    q | k | v = LayerNorm(x; ln_g, ln_b, eps) . Wqkv^T + b
@@ -516,7 +526,8 @@ int ovo_vit_forward(const ovo_vit_config_t *cfg, const ovo_vit_weights_t *w, con
  * windowed multi-head attention blocks with 2x2 max-pool query pooling at stage changes and a few global
  * blocks, FPN 1x1 laterals with nearest top-down on the coarse levels, optional decoder conv_s0 / conv_s1.
  * Outputs are NHWC f32: feat0 [B, S/4, S/4, c0], feat1 [B, S/8, S/8, c1], feat2 [B, S/16, S/16, fpn_dim]
- * with (c0, c1) = (32, 64) when hi_res else (fpn_dim, fpn_dim). */
+ * with (c0, c1) = (32, 64) when hi_res else (fpn_dim, fpn_dim).  With hi_res, feat0 / feat1 and the neck / conv_s0 / conv_s1 weights must be
+ * 16-byte aligned where levels 0 / 1 run as one launch each (ovo_neck_f32's shapes: their laterals have no place in the workspace). */
 typedef struct {
     int32_t image_size;            /* 1024 */
     int32_t dims[4], heads[4], blocks[4], window[4];

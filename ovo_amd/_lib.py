@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "lib", "libovo_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 E_UNSUPPORTED = -3          # OVO_E_UNSUPPORTED: the entry point does not cover this shape; the caller takes its general path
 
 
@@ -206,6 +206,7 @@ _SIGNATURES = {
     "ovo_global_patch_filter": (_I32, [_P, _P, _I32, _I32, _I32, _F32, _P, _P]),
     "ovo_scale_rows_bf16": (_I32, [_P, _P, _I32, _I32, _P, _P]),
     "ovo_mlp_f32": (_I32, [_P, _I64, _I32, _P, _P, _F32, _P, _I64, _P, _I32, _P, _I64, _P, _P]),
+    "ovo_neck_f32": (_I32, [_P, _I64, _I32, _P, _I64, _P, _I32, _P, _I64, _P, _P, _I32, _P]),
     "ovo_window_attention_f32": (_I32, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _F32, _P, _I64, _P, _P, _I32, _P]),
     "ovo_l2_normalize_rows": (_I32, [_P, _I64, _I32, _P, _P]),
     "ovo_cast_f32": (_I32, [_P, _I64, _P, _I32, _P]),

@@ -28,6 +28,7 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno
 # epilogues unchanged (two alternating rounds of both builds in one session, tools/gemm_bench.py); results are bit-identical (the same IEEE operations)
 EXTRA = {"geometry.hip": ["-ffp-contract=off"], "evalknn.hip": ["-ffp-contract=off"], "mlp_stream.hip": ["-fno-slp-vectorize"], "gemm_stream.hip": ["-fno-slp-vectorize"],
          "winattn.hip": ["-fno-slp-vectorize"], "gemm8p.hip": ["-fno-slp-vectorize"],
+         "neck_stream.hip": ["-fno-slp-vectorize"],  # mlp_stream.hip's sibling: the same flags
          "merger.hip": ["-fno-slp-vectorize"]}       # k_merge_clips takes a row's sum of squares and shares its CU: the same treatment as the LayerNorm files
 
 

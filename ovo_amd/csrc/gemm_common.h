@@ -318,6 +318,13 @@ int gemm_f32a_stream(const ovo_gemm_t *p, const ovo_window_t *win, const float *
 int mlp_stream_launch(float *x, long long rows, int d, const float *ln_g, const float *ln_b, float eps, const void *w1, long long ldw1, const float *b1,
                       int hid, const void *w2, long long ldw2, const float *b2, hipStream_t s);
 
+// out f32 [rows, n_out] = W2 . bf16(W1 . bf16(x) + b1) + b2 in ONE launch, the hid-wide middle row never leaving registers (neck_stream.hip: an FPN lateral
+// with conv_s0 / conv_s1 behind it).  neck_stream_covers: the shape has an instantiation and no knob keeps the streaming kernels off -- what
+// hiera.hip's workspace layout asks before it leaves the laterals out; the launch also wants 16-byte aligned pointers (OVO_E_UNSUPPORTED, nothing launched)
+bool neck_stream_covers(long long rows, int d, long long ldw1, int hid, int n_out);
+int neck_stream_launch(const float *x, long long rows, int d, const void *w1, long long ldw1, const float *b1, int hid, const void *w2, long long ldw2,
+                       const float *b2, float *out, int n_out, hipStream_t s);
+
 // ovo_gemm_unwindow (f32 C += residual, rows re-ordered from window order) that ALSO writes ln_out bf16 [C rows, ld_ln] = LayerNorm(C row; g, b, eps): the
 // full-row tile of gemm.hip.  OVO_E_UNSUPPORTED (nothing launched) unless N = 448, K % 64 == 0, f32 output
 int gemm_unwindow_rowln(const ovo_gemm_t *p, const ovo_window_t *win, const float *ln_g, const float *ln_b, float eps, void *ln_out, long long ld_ln,

@@ -8,6 +8,11 @@
 //   ovo_gemm      output projection -> fp32 rows in window order
 //   (epilogue of that GEMM, ovo_gemm_unwindow)  window order -> spatial order, + residual (the pooled projected skip at stage changes)
 //   k_ln_window(identity) -> FC1 GEMM(+GELU) -> FC2 GEMM(+bias, += x)
+// FPN neck (sam2 FpnNeck + the mask decoder's conv_s0 / conv_s1), at the end of each stage and after the last block:
+//   levels 2, 3   lateral 1x1 conv of the stage's stream -> lat[2], lat[3]; k_topdown_add writes lat[2] + up(lat[3]) straight into feat2
+//   levels 0, 1   with hi_res: ONE launch each from the stream into feat0 / feat1 (neck_stream.hip: lateral + conv_s0 / conv_s1, the 256-channel lateral in
+//                 registers; lat[0] / lat[1] are not even reserved) where neck_fused() -- hiera_b+'s widths, >= 16384 tokens; otherwise, and with
+//                 OVO_HIERA_NECK_TWO_PASS set, the lateral into lat[s] and conv_s0 / conv_s1 as a second streaming GEMM.  Without hi_res: the laterals themselves
 // All GEMM operands have K padded to a multiple of 64 with zeros (dims 112 / 224 of hiera_b+, 144 / 288 of hiera_l; the 7x7x3 patch: 192).
 #include "gemm_common.h"
 
@@ -216,8 +221,8 @@ __global__ void __launch_bounds__(256) k_cast_pad(const float *__restrict__ x, l
     }
 }
 
-// fine[b, y, x, :] += coarse[b, y/2, x/2, :]   (nearest 2x top-down)
-__global__ void __launch_bounds__(256) k_topdown_add(float *__restrict__ fine, const float *__restrict__ coarse, int B, int H, int W, int C) {
+// out[b, y, x, :] = fine[b, y, x, :] + coarse[b, y/2, x/2, :]   (nearest 2x top-down, straight into the caller's level-2 tensor)
+__global__ void __launch_bounds__(256) k_topdown_add(const float *__restrict__ fine, const float *__restrict__ coarse, float *__restrict__ out, int B, int H, int W, int C) {
     const int c4 = C >> 2;
     const long long total = (long long)B * H * W * c4;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -227,9 +232,9 @@ __global__ void __launch_bounds__(256) k_topdown_add(float *__restrict__ fine, c
         const int y = (int)(t % H);
         const int b = (int)(t / H);
         const float4 u = ((const float4 *)coarse)[(((long long)b * (H / 2) + y / 2) * (W / 2) + x / 2) * c4 + c];
-        float4 v = ((float4 *)fine)[i];
+        float4 v = ((const float4 *)fine)[i];
         v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-        ((float4 *)fine)[i] = v;
+        ((float4 *)out)[i] = v;
     }
 }
 
@@ -270,6 +275,15 @@ struct Ws {
     size_t bytes;
 };
 
+// FPN level s (0 or 1) goes from the trunk's stream straight into feat0 / feat1 -- lateral and conv_s0 / conv_s1 in one launch (neck_stream.hip), lat[s] neither
+// written nor reserved.  Decided from the configuration alone, so that ovo_hiera_workspace_bytes and the forward agree; OVO_HIERA_NECK_TWO_PASS (A/B
+// runs, tests) keeps the two launches.
+bool neck_fused(const ovo_hiera_config_t &c, int B, int s) {
+    if (!c.hi_res || s > 1 || ovo_knob_set("OVO_HIERA_NECK_TWO_PASS")) return false;
+    const long long rows = ((long long)B * (c.image_size / 4) * (c.image_size / 4)) >> (2 * s);
+    return ovo_gemm_detail::neck_stream_covers(rows, c.dims[s], padk(c.dims[s]), c.fpn_dim, s == 0 ? 32 : 64);
+}
+
 Ws carve(const ovo_hiera_config_t &c, const Plan &p, int B, void *base) {
     size_t max_x = 0, max_h = 0, max_qkv = 0, max_att = 0, max_u = 0, max_tmp = 0, max_cast = 0;
     for (int i = 0; i < p.n_blocks; ++i) {
@@ -303,7 +317,7 @@ Ws carve(const ovo_hiera_config_t &c, const Plan &p, int B, void *base) {
     w.att = (uint16_t *)take(max_att * 2);
     w.u = (uint16_t *)take(max_u * 2);
     w.cast = (uint16_t *)take(max_cast * 2);
-    for (int s = 0; s < 4; ++s) { const size_t t = T0 >> (2 * s); w.lat[s] = (float *)take(t * c.fpn_dim * 4); }
+    for (int s = 0; s < 4; ++s) { const size_t t = T0 >> (2 * s); w.lat[s] = neck_fused(c, B, s) ? nullptr : (float *)take(t * c.fpn_dim * 4); }
     w.bytes = off;
     return w;
 }
@@ -689,24 +703,39 @@ int ovo_hiera_forward(const ovo_hiera_config_t *cfg, const ovo_hiera_weights_t *
         if (p.stage_end[i] >= 0) {                           // FPN lateral 1x1 conv of this stage's output
             const int s = p.stage_end[i];
             OVO_REQUIRE(w->neck_w[s] && w->neck_b[s], "missing neck weights");
+            if (neck_fused(c, B, s)) {                       // levels 0 / 1 with hi_res: lateral + conv_s0 / conv_s1 in one launch, the lateral in registers
+                const void *cw = s == 0 ? w->s0_w : w->s1_w;
+                const float *cb = s == 0 ? w->s0_b : w->s1_b;
+                float *feat = s == 0 ? feat0 : feat1;
+                OVO_REQUIRE(cw && cb, "missing conv_s0 / conv_s1 weights");
+                // (there is no lateral buffer to fall back to: the layout was decided without the pointers -- ovo_hip.h states the requirement)
+                OVO_REQUIRE((((uintptr_t)feat | (uintptr_t)w->neck_w[s] | (uintptr_t)cw) & 15) == 0, "feat0 / feat1 and the neck weights must be 16-byte aligned");
+                TRY(ovo_gemm_detail::neck_stream_launch(x, tok_out, dout, w->neck_w[s], kout, w->neck_b[s], c.fpn_dim, cw, c.fpn_dim, cb, feat, s == 0 ? 32 : 64, hs));
+                LAUNCHED();
+                continue;
+            }
             bool cast_done = false;
             TRY(gemm_from_f32(x, gi, dout, kout, nullptr, nullptr, 0.f, 2, k.cast, cast_done, w->neck_w[s], w->neck_b[s], k.lat[s], c.fpn_dim, 0,
                               c.fpn_dim, 0, stream));
         }
     }
-    // top-down on the coarse levels: level 2 += up(level 3); levels 0 and 1 are laterals only
+    // top-down on the coarse levels: feat2 = level 2 + up(level 3), written where the caller wants it; levels 0 and 1 are laterals only.  With hi_res they
+    // went through conv_s0 / conv_s1 at their stage's end when neck_fused() (one launch each from the stream, no lateral in memory), else here
     const int S16 = c.image_size / 16;
-    k_topdown_add<<<ovo_grid((long long)B * S16 * S16 * (c.fpn_dim / 4), 256), 256, 0, hs>>>(k.lat[2], k.lat[3], B, S16, S16, c.fpn_dim);
+    float *top = ((uintptr_t)feat2 & 15) == 0 ? feat2 : k.lat[2];                  // (float4 stores: a misaligned feat2 gets a copy, as before)
+    k_topdown_add<<<ovo_grid((long long)B * S16 * S16 * (c.fpn_dim / 4), 256), 256, 0, hs>>>(k.lat[2], k.lat[3], top, B, S16, S16, c.fpn_dim);
     LAUNCHED();
-    OVO_HIP(hipMemcpyAsync(feat2, k.lat[2], (size_t)B * S16 * S16 * c.fpn_dim * 4, hipMemcpyDeviceToDevice, hs));
+    if (top != feat2) OVO_HIP(hipMemcpyAsync(feat2, top, (size_t)B * S16 * S16 * c.fpn_dim * 4, hipMemcpyDeviceToDevice, hs));
     const long long t0 = (long long)B * T0, t1 = t0 / 4;
     if (c.hi_res) {
         OVO_REQUIRE(w->s0_w && w->s0_b && w->s1_w && w->s1_b, "missing conv_s0 / conv_s1 weights");
         bool cast_done = false;
         const Grid g0 = make_grid(B, S4, S4, 0), g1 = make_grid(B, S4 / 2, S4 / 2, 0);
-        TRY(gemm_from_f32(k.lat[0], g0, c.fpn_dim, c.fpn_dim, nullptr, nullptr, 0.f, 2, k.cast, cast_done, w->s0_w, w->s0_b, feat0, 32, 0, 32, 0, stream));
+        if (!neck_fused(c, B, 0))
+            TRY(gemm_from_f32(k.lat[0], g0, c.fpn_dim, c.fpn_dim, nullptr, nullptr, 0.f, 2, k.cast, cast_done, w->s0_w, w->s0_b, feat0, 32, 0, 32, 0, stream));
         cast_done = false;
-        TRY(gemm_from_f32(k.lat[1], g1, c.fpn_dim, c.fpn_dim, nullptr, nullptr, 0.f, 2, k.cast, cast_done, w->s1_w, w->s1_b, feat1, 64, 0, 64, 0, stream));
+        if (!neck_fused(c, B, 1))
+            TRY(gemm_from_f32(k.lat[1], g1, c.fpn_dim, c.fpn_dim, nullptr, nullptr, 0.f, 2, k.cast, cast_done, w->s1_w, w->s1_b, feat1, 64, 0, 64, 0, stream));
     } else {
         OVO_HIP(hipMemcpyAsync(feat0, k.lat[0], (size_t)t0 * c.fpn_dim * 4, hipMemcpyDeviceToDevice, hs));
         OVO_HIP(hipMemcpyAsync(feat1, k.lat[1], (size_t)t1 * c.fpn_dim * 4, hipMemcpyDeviceToDevice, hs));

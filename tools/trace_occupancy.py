@@ -12,7 +12,7 @@ marks = sorted(int(r[sk]) for r in rows if "k_marker" in r[nk])
 lo, hi = marks[0], marks[1]
 ev = [(int(r[sk]), int(r[ek]), r[nk]) for r in rows if lo < int(r[sk]) < hi and "k_marker" not in r[nk]]
 ev.sort()
-heavy = lambda n: any(t in n for t in ("k_gemm", "k_attention", "k_mlp_stream", "k_win_attn", "k_similarity_mfma", "k_patch_embed"))
+heavy = lambda n: any(t in n for t in ("k_gemm", "k_attention", "k_mlp_stream", "k_neck_stream", "k_win_attn", "k_similarity_mfma", "k_patch_embed"))
 
 
 def profile(events, label):
