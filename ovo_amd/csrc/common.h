@@ -55,7 +55,7 @@ void ovo_prof_count(const int32_t *device_count, double per_item, double fixed, 
 // ovo_knob_set(name): the variable exists, whatever its value; ovo_knob_int(name, dflt): atoi of it, or dflt; ovo_knob_str(name): a copy of its
 // first 15 characters.  Each expansion owns its cached value (a knob read in several files gets ONE accessor: gemm_common.h), and costs a
 // cached load and a branch when not dynamic.  Outside the contract, each with its reason where it stands: OVO_KNOBS_DYNAMIC itself, OVO_PROF_DUMP
-// (core.hip) and the buffer addresses of the OVO_GEMM_DEBUG builds (gemm8p.hip, mlp_stream.hip).
+// (core.hip) and the buffer address of the OVO_GEMM_DEBUG build (gemm8p.hip).
 static inline bool ovo_knobs_dynamic() {
     static const bool d = getenv("OVO_KNOBS_DYNAMIC") != nullptr;       // decides how every other knob is read: itself read once, always
     return d;

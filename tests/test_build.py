@@ -39,9 +39,9 @@ def test_a_changed_flag_rebuilds_its_object_and_relinks(tmp_path, monkeypatch):
     assert "-DOVO_DUMMY" not in ran[0][1]
     # the build's options are flags like any other, and leave the module's own table alone
     extra = {f: list(v) for f, v in B.EXTRA.items()}
-    assert step(gemm_debug=True) == ["gemm8p.o", "gemm8q.o", "mlp_stream.o", "libovo_hip.so"]
+    assert step(gemm_debug=True) == ["gemm8p.o", "gemm8q.o", "libovo_hip.so"]
     assert step(gemm_debug=True) == []
-    assert step(experimental=True) == ["gemm8p.o", "gemm8q.o", "geometry.o", "mlp_stream.o", "libovo_hip.so"]
+    assert step(experimental=True) == ["gemm8p.o", "gemm8q.o", "geometry.o", "libovo_hip.so"]
     assert step() == ["gemm8q.o", "geometry.o", "libovo_hip.so"]
     assert B.EXTRA == extra
     assert step(force=True)[-1] == "libovo_hip.so" and len(ran) == len(everything)
