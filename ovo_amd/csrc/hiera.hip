@@ -1,19 +1,22 @@
-// hiera.hip -- SAM2 image encoder forward (Hiera trunk + FPN neck) as one C call.
-//
-// Tokens live in an fp32 residual stream x[B, H, W, C] (NHWC).  Per block:
-//   k_ln_window   LayerNorm + window partition (+ zero rows for the padding windows, zero K-padding columns)
-//   ovo_gemm      QKV (bf16, MFMA)                         [rows, 3*dim_out]
-//   k_qpool       2x2 max-pool of q inside each window     (stage-change blocks only)
-//   ovo_attention per-window (or global) fused attention, windows folded into the batch dimension
-//   ovo_gemm      output projection -> fp32 rows in window order
-//   (epilogue of that GEMM, ovo_gemm_unwindow)  window order -> spatial order, + residual (the pooled projected skip at stage changes)
-//   k_ln_window(identity) -> FC1 GEMM(+GELU) -> FC2 GEMM(+bias, += x)
-// FPN neck (sam2 FpnNeck + the mask decoder's conv_s0 / conv_s1), at the end of each stage and after the last block:
-//   levels 2, 3   lateral 1x1 conv of the stage's stream -> lat[2], lat[3]; k_topdown_add writes lat[2] + up(lat[3]) straight into feat2
-//   levels 0, 1   with hi_res: ONE launch each from the stream into feat0 / feat1 (neck_stream.hip: lateral + conv_s0 / conv_s1, the 256-channel lateral in
-//                 registers; lat[0] / lat[1] are not even reserved) where neck_fused() -- hiera_b+'s widths, >= 16384 tokens; otherwise, and with
-//                 OVO_HIERA_NECK_TWO_PASS set, the lateral into lat[s] and conv_s0 / conv_s1 as a second streaming GEMM.  Without hi_res: the laterals themselves
+// hiera.hip -- SAM2 image encoder forward (Hiera trunk + FPN neck) as one C call: validate, make_plan (every shape, once), carve (the workspace), patch_embed,
+// per block skip_path -> attention -> out_projection -> mlp -> neck_level, then neck_tail.  Tokens live in an fp32 residual stream x[B, H, W, C] (NHWC), updated
+// in place.  A step runs its fused form where that covers the shape, else (the launcher answers OVO_E_UNSUPPORTED: TRY_FUSED) the plain one; [knob] = turns it off:
+//   patch_embed     k_patch_embed7, the 7 x 7 / stride-4 convolution + bias + position embedding straight from the image (E = 96 / 112 / 144, S % 128 == 0)
+//                   [OVO_HIERA_PATCH_GEMM]; else ovo_im2col + one GEMM per image (the position embedding, which has no batch dim, as its `add`)
+//   skip_path       stage changes only: maxpool2x2(proj(LN1(x))) in one streaming-GEMM launch (gemm_stream.hip, f32 A operand) [OVO_NO_LN_FOLD]; else k_ln_window
+//                   (LayerNorm + window partition, zero rows for padding windows, zero K-padding columns) -> ovo_gemm -> k_pool_unwindow
+//   attention       LN1 -> QKV (-> 2 x 2 max-pool of q at a stage change) -> window attention in one launch per pair of heads (winattn.hip: hiera_b+'s 8 x 8 windows,
+//                   >= 512 of them, pre-scaled q) [OVO_HIERA_NO_WINATTN, OVO_Q_PRESCALE=0]; else QKV by the streaming GEMM (LN1 in its operand load, pooled q from its
+//                   epilogue) [OVO_NO_LN_FOLD] or k_ln_window -> ovo_gemm (-> k_qpool8 / k_qpool), then ovo_attention with the windows folded into the batch dimension
+//   out_projection  ovo_gemm_unwindow: window order -> spatial order + residual (the pooled skip at a stage change) in the epilogue; OPT-IN [OVO_HIERA_PROJ_LN=1, N = 448]
+//                   a full-row tile that also leaves norm2 in k.h
+//   mlp             LN2 -> FC1 -> GELU -> FC2 -> += x in one launch (mlp_stream.hip: stages 1-2) [OVO_NO_MLP_FUSE]; else FC1 (LN2 in its operand load or as a k_ln_window
+//                   pass) + FC2 (+= x), over row chunks with OVO_HIERA_MLP_CHUNK_MB
+//   neck_level,     FPN (sam2 FpnNeck + the mask decoder's conv_s0 / conv_s1) at each stage's end.  Levels 2, 3: lateral 1x1 conv -> lat[2], lat[3]; k_topdown_add writes lat[2] + up(lat[3])
+//   neck_tail       into feat2.  Levels 0, 1 with hi_res: ONE launch each from the stream into feat0 / feat1 (neck_stream.hip; lat[0] / lat[1] not even reserved) where neck_fused()
+//                   [OVO_HIERA_NECK_TWO_PASS]; else the lateral into lat[s], then conv_s0 / conv_s1 as a second GEMM.  Without hi_res: the laterals
 // All GEMM operands have K padded to a multiple of 64 with zeros (dims 112 / 224 of hiera_b+, 144 / 288 of hiera_l; the 7x7x3 patch: 192).
+#include <algorithm>
 #include "gemm_common.h"
 
 namespace {
@@ -242,34 +245,53 @@ inline int padk(int v) { return (v + 63) / 64 * 64; }   // K of every GEMM opera
                                                          // ((16384,1344,224 -> 256): 34.8 -> 29.1 us although 14 % of the products are zeros)
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// One block of the trunk: every shape that carve (the workspace layout) and the steps of the forward need, computed ONCE by make_plan
+struct BlockShape {
+    int din, dout, kin, kout, heads, hd, H, Ho;     // channels in / out, their K-padded widths; H x H tokens per image in, Ho x Ho out
+    bool pool; int stage_end;                       // first block of stages 2-4 (q pooled 2 x 2, projected + pooled skip); stage index if the block closes a stage, else -1
+    Grid g, go, gi;                                 // windows of the input grid; of the output grid (halved where pooled); the output tokens as plain rows
+    long long n_win, tok_out, att_rows; int tk, tq; // windows (padding ones included), keys / queries per window; att_rows = n_win * tq
+    size_t n_x, n_h, n_qkv, n_att, n_u, n_tmp, n_cast;     // elements the block needs in each workspace buffer
+};
 struct Plan {
-    int n_blocks;
-    int dim_in[64], dim_out[64], heads[64], ws[64], pool[64], Hin[64];
-    int stage_end[64];        // stage index if the block closes a stage, else -1
+    int n_blocks, S4;                               // S4 x S4 tokens per image at stage 1
+    Grid level[2];                                  // FPN levels 0 / 1 as plain rows (conv_s0 / conv_s1 of the two-pass neck)
+    size_t n_col, n_cast, n_lat[4];                 // im2col patches, conv_s0's bf16 operand, the laterals
+    BlockShape b[64];
 };
 
-int make_plan(const ovo_hiera_config_t &c, Plan &p) {
-    int idx = 0, H = c.image_size / 4;
+int make_plan(const ovo_hiera_config_t &c, int B, Plan &p) {
+    int idx = 0, H = p.S4 = c.image_size / 4;
+    const size_t tok0 = (size_t)B * H * H;
+    p.level[0] = make_grid(B, H, H, 0); p.level[1] = make_grid(B, H / 2, H / 2, 0);
+    p.n_col = tok0 * 192; p.n_cast = tok0 * c.fpn_dim;
+    for (int s = 0; s < 4; ++s) p.n_lat[s] = (tok0 >> (2 * s)) * c.fpn_dim;
     for (int s = 0; s < 4; ++s)
         for (int b = 0; b < c.blocks[s]; ++b) {
             if (idx >= 64) return -1;
-            const bool first = s > 0 && b == 0;
-            p.dim_in[idx] = first ? c.dims[s - 1] : c.dims[s];
-            p.dim_out[idx] = c.dims[s];
-            p.heads[idx] = c.heads[s];
+            BlockShape &k = p.b[idx];
+            const bool first = k.pool = s > 0 && b == 0;
+            k.din = first ? c.dims[s - 1] : c.dims[s]; k.dout = c.dims[s]; k.kin = padk(k.din); k.kout = padk(k.dout);
+            k.heads = c.heads[s]; k.hd = k.heads > 0 ? k.dout / k.heads : 0;      // (ovo_hiera_workspace_bytes plans unvalidated configurations)
             int ws = first ? c.window[s - 1] : c.window[s];
-            for (int k = 0; k < c.n_global; ++k) if (c.global_blocks[k] == idx) ws = 0;
-            p.ws[idx] = ws;
-            p.pool[idx] = first;
-            p.Hin[idx] = H;
-            if (first) H /= 2;
-            p.stage_end[idx] = b == c.blocks[s] - 1 ? s : -1;
+            for (int j = 0; j < c.n_global; ++j) if (c.global_blocks[j] == idx) ws = 0;
+            k.H = H;
+            k.Ho = H = first ? H / 2 : H;
+            k.stage_end = b == c.blocks[s] - 1 ? s : -1;
+            k.g = make_grid(B, k.H, k.H, ws); k.go = make_grid(B, H, H, ws > 0 ? (first ? ws / 2 : ws) : 0); k.gi = make_grid(B, H, H, 0);
+            k.n_win = (long long)B * k.g.nwh * k.g.nww; k.tk = k.g.wh * k.g.ww; k.tq = first ? k.tk / 4 : k.tk;
+            k.tok_out = (long long)B * H * H; k.att_rows = k.n_win * k.tq;
+            const size_t rows = (size_t)k.g.rows, tin = (size_t)B * k.H * k.H, tout = (size_t)k.tok_out;
+            k.n_x = std::max(tin * k.din, tout * k.dout);
+            k.n_h = std::max(rows * k.kin, tout * k.kout);     // LN1 rows in window order, then LN2 of the output tokens
+            k.n_qkv = rows * 3 * k.dout; k.n_tmp = rows * k.dout;
+            k.n_att = (first ? rows / 4 : rows) * k.kout;      // (also the pooled q)
+            k.n_u = tout * 4 * k.dout; k.n_cast = tout * k.kout;
             ++idx;
         }
     p.n_blocks = idx;
     return 0;
 }
-
 struct Ws {
     uint16_t *col; float *x, *xr, *tmp; uint16_t *h, *qkv, *qp, *att, *u, *cast; float *lat[4];
     size_t bytes;
@@ -284,49 +306,45 @@ bool neck_fused(const ovo_hiera_config_t &c, int B, int s) {
     return ovo_gemm_detail::neck_stream_covers(rows, c.dims[s], padk(c.dims[s]), c.fpn_dim, s == 0 ? 32 : 64);
 }
 
+// the workspace layout: every buffer as large as the block that needs it most (the plan's n_* fields; nothing is derived here)
 Ws carve(const ovo_hiera_config_t &c, const Plan &p, int B, void *base) {
-    size_t max_x = 0, max_h = 0, max_qkv = 0, max_att = 0, max_u = 0, max_tmp = 0, max_cast = 0;
+    size_t max_x = 0, max_h = 0, max_qkv = 0, max_att = 0, max_u = 0, max_tmp = 0, max_cast = p.n_cast;
     for (int i = 0; i < p.n_blocks; ++i) {
-        const int H = p.Hin[i], Ho = p.pool[i] ? H / 2 : H;
-        const Grid g = make_grid(B, H, H, p.ws[i]);
-        const size_t tok_in = (size_t)B * H * H, tok_out = (size_t)B * Ho * Ho;
-        const size_t rows_out = p.pool[i] ? (size_t)g.rows / 4 : (size_t)g.rows;
-        max_x = max_x > tok_in * p.dim_in[i] ? max_x : tok_in * p.dim_in[i];
-        max_x = max_x > tok_out * p.dim_out[i] ? max_x : tok_out * p.dim_out[i];
-        size_t v = (size_t)g.rows * padk(p.dim_in[i]); max_h = max_h > v ? max_h : v;
-        v = tok_out * padk(p.dim_out[i]); max_h = max_h > v ? max_h : v;
-        v = (size_t)g.rows * 3 * p.dim_out[i]; max_qkv = max_qkv > v ? max_qkv : v;
-        v = rows_out * padk(p.dim_out[i]); max_att = max_att > v ? max_att : v;
-        v = tok_out * 4 * p.dim_out[i]; max_u = max_u > v ? max_u : v;
-        v = (size_t)g.rows * p.dim_out[i]; max_tmp = max_tmp > v ? max_tmp : v;
-        v = tok_out * padk(p.dim_out[i]); max_cast = max_cast > v ? max_cast : v;
+        const BlockShape &k = p.b[i];
+        max_x = std::max(max_x, k.n_x); max_h = std::max(max_h, k.n_h); max_qkv = std::max(max_qkv, k.n_qkv); max_att = std::max(max_att, k.n_att);
+        max_u = std::max(max_u, k.n_u); max_tmp = std::max(max_tmp, k.n_tmp); max_cast = std::max(max_cast, k.n_cast);
     }
-    const size_t T0 = (size_t)B * (c.image_size / 4) * (c.image_size / 4);
-    max_cast = max_cast > T0 * c.fpn_dim ? max_cast : T0 * c.fpn_dim;
-    Ws w;
-    char *b0 = (char *)base;
-    size_t off = 0;
-    auto take = [&](size_t n) { char *r = b0 ? b0 + off : nullptr; off += align256(n); return r; };
-    w.col = (uint16_t *)take(T0 * 192 * 2);
-    w.x = (float *)take(max_x * 4);
-    w.xr = (float *)take(max_x * 4);
-    w.tmp = (float *)take(max_tmp * 4);
-    w.h = (uint16_t *)take(max_h * 2);
-    w.qkv = (uint16_t *)take(max_qkv * 2);
-    w.qp = (uint16_t *)take(max_att * 2);
-    w.att = (uint16_t *)take(max_att * 2);
-    w.u = (uint16_t *)take(max_u * 2);
-    w.cast = (uint16_t *)take(max_cast * 2);
-    for (int s = 0; s < 4; ++s) { const size_t t = T0 >> (2 * s); w.lat[s] = neck_fused(c, B, s) ? nullptr : (float *)take(t * c.fpn_dim * 4); }
+    Ws w; size_t off = 0;
+    auto take = [&](size_t n) { char *r = base ? (char *)base + off : nullptr; off += align256(n); return r; };
+    w.col = (uint16_t *)take(p.n_col * 2); w.x = (float *)take(max_x * 4); w.xr = (float *)take(max_x * 4); w.tmp = (float *)take(max_tmp * 4);
+    w.h = (uint16_t *)take(max_h * 2); w.qkv = (uint16_t *)take(max_qkv * 2);
+    w.qp = (uint16_t *)take(max_att * 2); w.att = (uint16_t *)take(max_att * 2);
+    w.u = (uint16_t *)take(max_u * 2); w.cast = (uint16_t *)take(max_cast * 2);
+    for (int s = 0; s < 4; ++s) w.lat[s] = neck_fused(c, B, s) ? nullptr : (float *)take(p.n_lat[s] * 4);
     w.bytes = off;
     return w;
 }
 
-int gemm(const void *A, long long lda, const void *W, long long ldw, const float *bias, void *C, long long ldc, int out_dtype,
-         const float *add, long long ld_add, long long M, int N, int K, int act, ovo_stream_t s) {
+// the two descriptors every product of the forward is described by (bf16 operands, alpha = 1)
+ovo_gemm_t gemm_desc(const void *A, long long lda, const void *W, long long ldw, const float *bias, void *C, long long ldc, int out_dtype,
+                     const float *add, long long ld_add, long long M, int N, int K, int act) {
     ovo_gemm_t g;
     g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.C = C; g.ldc = ldc; g.add = add; g.ld_add = ld_add;
     g.M = (int)M; g.N = N; g.K = K; g.in_dtype = 2; g.out_dtype = out_dtype; g.act = act; g.alpha = 1.0f;
+    return g;
+}
+ovo_window_t window_of(const Grid &g) { return {g.B, g.H, g.W, g.wh, g.ww}; }
+
+#define TRY(call) do { const int rc__ = (call); if (rc__ != OVO_OK) return rc__; } while (0)
+// The "fused form, else fall back" rule, once: a fused launcher answers OVO_OK (ran = true), OVO_E_UNSUPPORTED (shape not covered, or turned off by its knob:
+// ran = false, the caller runs the plain form) or an error, which is returned as it is
+#define TRY_FUSED(ran, call) \
+    do { const int rc__ = (call); if (rc__ != OVO_OK && rc__ != OVO_E_UNSUPPORTED) return rc__; (ran) = rc__ == OVO_OK; } while (0)
+#define LAUNCHED() OVO_CHECK_LAUNCH()
+
+int gemm(const void *A, long long lda, const void *W, long long ldw, const float *bias, void *C, long long ldc, int out_dtype,
+         const float *add, long long ld_add, long long M, int N, int K, int act, ovo_stream_t s) {
+    const ovo_gemm_t g = gemm_desc(A, lda, W, ldw, bias, C, ldc, out_dtype, add, ld_add, M, N, K, act);
     return ovo_gemm(&g, s);
 }
 
@@ -334,13 +352,11 @@ int gemm(const void *A, long long lda, const void *W, long long ldw, const float
 // normalise / cast into `h` (window order when g.ws > 0), then ovo_gemm.  `h_done`: a previous call already filled `h` for this x.
 int gemm_from_f32(const float *x, const Grid &g, int d, int kp, const float *gamma, const float *beta, float eps, int mode, uint16_t *h, bool &h_done,
                   const void *W, const float *bias, void *C, long long ldc, int out_dtype, int N, int act, ovo_stream_t s) {
-    ovo_gemm_t q;
-    q.A = h; q.lda = kp; q.W = W; q.ldw = kp; q.bias = bias; q.C = C; q.ldc = ldc; q.add = nullptr; q.ld_add = 0;
-    q.M = (int)g.rows; q.N = N; q.K = kp; q.in_dtype = 2; q.out_dtype = out_dtype; q.act = act; q.alpha = 1.0f;
+    const ovo_gemm_t q = gemm_desc(h, kp, W, kp, bias, C, ldc, out_dtype, nullptr, 0, g.rows, N, kp, act);
     if (!h_done) {
-        const ovo_window_t w = {g.B, g.H, g.W, g.wh, g.ww};
-        const int rc = ovo_gemm_detail::gemm_f32a_stream(&q, g.ws > 0 ? &w : nullptr, x, d, gamma, beta, eps, mode, 0, s);
-        if (rc != OVO_E_UNSUPPORTED) return rc;
+        const ovo_window_t w = window_of(g); bool streamed;
+        TRY_FUSED(streamed, ovo_gemm_detail::gemm_f32a_stream(&q, g.ws > 0 ? &w : nullptr, x, d, gamma, beta, eps, mode, 0, s));
+        if (streamed) return OVO_OK;
         OVO_REQUIRE(d <= 2048 && g.rows < (1ll << 31), "LayerNorm rows of more than 2048 columns / more than 2^31 rows");
         if (mode == 1) launch_ln_window(x, g, d, kp, gamma, beta, eps, h, (hipStream_t)s);
         else k_cast_pad<<<ovo_grid(g.rows * kp, 256), 256, 0, (hipStream_t)s>>>(x, g.rows, d, kp, h);
@@ -519,21 +535,168 @@ int patch_embed_direct(const float *img, int S, int E, const void *w, int ldw, c
     }
 }
 
-}  // namespace
+// ---- the forward, one function per step of a block ----
+struct Fwd {                        // what one forward carries from step to step
+    const ovo_hiera_config_t &c; const ovo_hiera_weights_t &w; const Ws &k;
+    int B; float *feat0, *feat1; ovo_stream_t stream; hipStream_t hs;
+    float *x, *spare;               // the residual stream (updated in place) and the buffer a stage change pools its skip into
+    const float *residual;          // what the block's output projection adds: x itself, or the pooled skip
+    bool h_done;                    // k.h holds the LayerNorm of the current x (norm1 rows in window order; norm2 after the row-LN output projection)
+    long long att_rows; int att_kout;       // the layout k.att's padding columns were last zero-filled for (-1: none)
+};
 
-#define TRY(call)                        \
-    do {                                 \
-        const int rc__ = (call);         \
-        if (rc__ != OVO_OK) return rc__; \
-    } while (0)
-#define LAUNCHED() OVO_CHECK_LAUNCH()
+int patch_embed(const Plan &p, const float *images, Fwd &f) {
+    const ovo_hiera_config_t &c = f.c;
+    const long long T0 = (long long)p.S4 * p.S4; bool direct;
+    TRY_FUSED(direct, patch_embed_direct(images, c.image_size, c.dims[0], f.w.patch_w, 192, f.w.patch_b, f.w.pos, f.x, f.B, f.hs));
+    if (direct) return OVO_OK;
+    TRY(ovo_im2col(images, f.B, 3, c.image_size, c.image_size, 7, 4, 3, f.k.col, 192, f.stream));
+    for (int b = 0; b < f.B; ++b)
+        TRY(gemm(f.k.col + (size_t)b * T0 * 192, 192, f.w.patch_w, 192, f.w.patch_b, f.x + (size_t)b * T0 * c.dims[0], c.dims[0], 0, f.w.pos, c.dims[0], T0,
+                 c.dims[0], 192, 0, f.stream));
+    return OVO_OK;
+}
+
+// stage change only: skip = maxpool2x2(proj(LN1(x))) into `spare`, pooled rows only; else every token's projection into k.tmp (LN1 stays in k.h for QKV) + the pool pass
+int skip_path(const BlockShape &s, const ovo_hiera_block_t &L, Fwd &f) {
+    f.residual = s.din == s.dout ? f.x : f.spare;
+    if (s.din == s.dout) return OVO_OK;
+    bool streamed = false;
+    if (s.g.ws > 0) {
+        const ovo_gemm_t q = gemm_desc(nullptr, s.kin, L.res_w, s.kin, L.res_b, f.spare, s.dout, 0, nullptr, 0, s.g.rows, s.dout, s.kin, 0);
+        const ovo_window_t wd = window_of(s.g);
+        TRY_FUSED(streamed, ovo_gemm_detail::gemm_f32a_stream(&q, &wd, f.x, s.din, L.ln1_g, L.ln1_b, f.c.ln_eps, 1, 1, f.stream));
+    }
+    if (!streamed) {
+        TRY(gemm_from_f32(f.x, s.g, s.din, s.kin, L.ln1_g, L.ln1_b, f.c.ln_eps, 1, f.k.h, f.h_done, L.res_w, L.res_b, f.k.tmp, s.dout, 0, s.dout, 0, f.stream));
+        k_pool_unwindow<<<ovo_grid(s.tok_out * s.dout, 256), 256, 0, f.hs>>>(f.k.tmp, s.g, s.dout, f.spare);
+    }
+    return OVO_OK;
+}
+
+// LN1 -> QKV (-> pool of q) -> per-window (or global) attention -> k.att [att_rows, kout] in window order: winattn.hip (q | k | v never written), else three launches
+int attention(const BlockShape &s, const ovo_hiera_block_t &L, Fwd &f) {
+    const Ws &k = f.k;
+    const int dout = s.dout, hd = s.hd;
+    // K-padding columns of the attention output must be zero; the attention kernels only write the real ones, so they STAY zero from block to
+    // block while rows x row width do not change (the blocks of one stage): one fill per layout instead of one per block (3 of 5 for hiera_b+)
+    if (s.kout != dout && (f.att_rows != s.att_rows || f.att_kout != s.kout)) {
+        OVO_HIP(hipMemsetAsync(k.att, 0, (size_t)s.att_rows * s.kout * 2, f.hs));
+        f.att_rows = s.att_rows; f.att_kout = s.kout;
+    } else if (s.kout == dout) f.att_rows = -1;              // every column written: the next padded layout starts from a fresh fill
+    bool fused = false, q_pooled = false;
+    if (s.g.ws > 0 && !f.h_done && f.c.q_prescaled)
+        TRY_FUSED(fused, ovo_gemm_detail::win_attn_launch(f.x, f.B, s.H, s.H, s.g.ws, s.din, dout, s.heads, s.pool ? 1 : 0, L.ln1_g, L.ln1_b, f.c.ln_eps, L.qkv_w, s.kin,
+                                                          L.qkv_b, k.att, s.kout, f.hs));
+    if (fused) return OVO_OK;
+    // QKV into k.qkv; at a stage change the q columns are pooled 2 x 2 into k.qp: in the product's epilogue where the streaming GEMM runs it, else by a pass over k.qkv
+    if (s.pool && s.g.ws > 0 && !f.h_done) {
+        const ovo_gemm_t q = gemm_desc(nullptr, s.kin, L.qkv_w, s.kin, L.qkv_b, k.qkv, 3 * dout, 2, nullptr, 0, s.g.rows, 3 * dout, s.kin, 0);
+        const ovo_window_t wd = window_of(s.g);
+        TRY_FUSED(q_pooled, ovo_gemm_detail::gemm_f32a_stream(&q, &wd, f.x, s.din, L.ln1_g, L.ln1_b, f.c.ln_eps, 1, 0, f.stream, k.qp, dout));
+    }
+    if (!q_pooled) TRY(gemm_from_f32(f.x, s.g, s.din, s.kin, L.ln1_g, L.ln1_b, f.c.ln_eps, 1, k.h, f.h_done, L.qkv_w, L.qkv_b, k.qkv, 3 * dout, 2, 3 * dout, 0, f.stream));
+    if (s.pool && !q_pooled) {
+        const long long total8 = s.att_rows * (dout / 8);
+        if (dout % 8 == 0 && total8 < (1ll << 32) - (1ll << 22) && (((uintptr_t)k.qkv | (uintptr_t)k.qp) & 15) == 0)
+            k_qpool8<<<ovo_grid(total8, 256, 256 * 16), 256, 0, f.hs>>>(k.qkv, (uint32_t)total8, s.g.wh, s.g.ww, dout, k.qp);
+        else k_qpool<<<ovo_grid(s.att_rows * dout, 256), 256, 0, f.hs>>>(k.qkv, s.n_win, s.g.wh, s.g.ww, dout, k.qp);
+    }
+    ovo_attention_t a = {};
+    a.k = k.qkv + dout; a.v = k.qkv + 2 * dout; a.o = k.att;
+    a.k_sb = a.v_sb = (int64_t)s.tk * 3 * dout; a.k_sh = a.v_sh = hd; a.k_st = a.v_st = 3 * dout;
+    if (s.pool) { a.q = k.qp; a.q_sb = (int64_t)s.tq * dout; a.q_sh = hd; a.q_st = dout; }
+    else { a.q = k.qkv; a.q_sb = a.k_sb; a.q_sh = hd; a.q_st = 3 * dout; }
+    a.o_sb = (int64_t)s.tq * s.kout; a.o_sh = hd; a.o_st = s.kout;
+    a.B = (int)s.n_win; a.H = s.heads; a.Tq = s.tq; a.Tk = s.tk; a.hd = hd; a.scale = f.c.q_prescaled ? 0.0f : 1.0f / sqrtf((float)hd);
+    return ovo_attention(&a, f.stream);
+}
+
+// Output projection, window order (pooled window size) -> spatial order, + residual.  In place: same-dim blocks add onto x; at a stage change the old x is dead (only
+// LN1 read it) and the pooled skip lives in `spare`, so the smaller new stream is written over the old buffer.  Leaves h_done = "k.h holds norm2 of the new x".
+int out_projection(const BlockShape &s, const ovo_hiera_block_t &L, Fwd &f) {
+    const ovo_gemm_t og = gemm_desc(f.k.att, s.kout, L.out_w, s.kout, L.out_b, f.x, s.dout, 0, f.residual, s.dout, s.att_rows, s.dout, s.kout, 0);
+    const ovo_window_t ow = window_of(s.go);
+    // stage 3 (N = 448), OPT-IN (OVO_HIERA_PROJ_LN=1): a full-row 128 x 448 tile, norm2 of the result rows from its accumulators straight into k.h, the MLP then
+    // skips its LayerNorm pass.  MEASURED AND LEFT OFF: 25 us per block slower inside the forward (profiles/r05c_rowln_bench.txt, docs/DESIGN_HISTORY.md)
+    f.h_done = false;
+    if (ovo_knob_set("OVO_HIERA_PROJ_LN") && s.dout == 448 && s.kout == s.dout)
+        TRY_FUSED(f.h_done, ovo_gemm_detail::gemm_unwindow_rowln(&og, &ow, L.ln2_g, L.ln2_b, f.c.ln_eps, f.k.h, s.kout, f.stream));
+    if (!f.h_done) TRY(ovo_gemm_unwindow(&og, &ow, f.stream));
+    return OVO_OK;
+}
+
+// x += FC2(GELU(FC1(LN2(x)))): one launch, the hidden row in registers; else FC1 (norm2 in its operand load, or in k.h: by a pass or from out_projection) into k.u + FC2
+int mlp(const BlockShape &s, const ovo_hiera_block_t &L, Fwd &f) {
+    const int dout = s.dout; bool fused;
+    TRY_FUSED(fused, ovo_gemm_detail::mlp_stream_launch(f.x, s.tok_out, dout, L.ln2_g, L.ln2_b, f.c.ln_eps, L.fc1_w, s.kout, L.fc1_b, 4 * dout, L.fc2_w, 4 * dout,
+                                                        L.fc2_b, f.hs));
+    if (!fused) {
+        // Row chunks (OVO_HIERA_MLP_CHUNK_MB = chunk size, default 0 = one pass): FC1 / FC2 alternate over chunks of rows whose hidden block fits the 256 MB Infinity
+        // Cache, every chunk through the SAME hidden buffer.  MEASURED AND LEFT OFF (docs/DESIGN_HISTORY.md: one pass 409.4 frames/s, 96 MB chunks 404.0, 48 MB 398.2,
+        // 24 MB 387.1): the write stream of the FC1 chunks is not absorbed by the cache and every extra launch pair adds its ramp
+        const long long chunk_mb = ovo_knob_int("OVO_HIERA_MLP_CHUNK_MB", 0), tok = s.tok_out, hid_row = (long long)4 * dout * 2;
+        long long chunk_rows = chunk_mb > 0 ? (chunk_mb << 20) / hid_row / 4096 * 4096 : 0;
+        if (chunk_rows <= 0 || tok < 2 * chunk_rows || tok * hid_row <= (200ll << 20)) chunk_rows = tok;   // (a hidden block the cache holds anyway: one pass)
+        for (long long r0 = 0; r0 < tok; r0 += chunk_rows) {
+            const long long nr = tok - r0 < chunk_rows ? tok - r0 : chunk_rows;
+            const Grid gc = chunk_rows == tok ? s.gi : make_grid(1, (int)nr, 1, 0);     // (a chunk is no shape of the plan: rows r0 .. r0 + nr as one column)
+            bool h_ready = chunk_rows == tok ? f.h_done : false;                        // (a chunked pass re-normalises its rows: norm2 in k.h is for the one-pass form only)
+            float *xc = f.x + r0 * dout;
+            TRY(gemm_from_f32(xc, gc, dout, s.kout, L.ln2_g, L.ln2_b, f.c.ln_eps, 1, f.k.h, h_ready, L.fc1_w, L.fc1_b, f.k.u, 4 * dout, 2, 4 * dout, 1, f.stream));
+            TRY(gemm(f.k.u, 4 * dout, L.fc2_w, 4 * dout, L.fc2_b, xc, dout, 0, xc, dout, nr, dout, 4 * dout, 0, f.stream));
+        }
+    }
+    f.h_done = false;                                        // x moved on: whatever k.h holds is stale
+    LAUNCHED();
+    return OVO_OK;
+}
+
+// end of stage s: FPN level s from the stream -- lateral + conv_s0 / conv_s1 in one launch into feat0 / feat1 where neck_fused(), else the lateral into lat[s]
+int neck_level(const BlockShape &b, Fwd &f) {
+    const int s = b.stage_end;
+    if (s < 0) return OVO_OK;
+    const ovo_hiera_weights_t &w = f.w;
+    if (neck_fused(f.c, f.B, s)) {
+        TRY(ovo_gemm_detail::neck_stream_launch(f.x, b.tok_out, b.dout, w.neck_w[s], b.kout, w.neck_b[s], f.c.fpn_dim, s == 0 ? w.s0_w : w.s1_w, f.c.fpn_dim,
+                                                s == 0 ? w.s0_b : w.s1_b, s == 0 ? f.feat0 : f.feat1, s == 0 ? 32 : 64, f.hs));
+        LAUNCHED();
+        return OVO_OK;
+    }
+    bool cast_done = false;
+    return gemm_from_f32(f.x, b.gi, b.dout, b.kout, nullptr, nullptr, 0.f, 2, f.k.cast, cast_done, w.neck_w[s], w.neck_b[s], f.k.lat[s], f.c.fpn_dim, 0, f.c.fpn_dim,
+                         0, f.stream);
+}
+
+// top-down on the coarse levels: feat2 = level 2 + up(level 3), written where the caller wants it; levels 0 and 1 are laterals only: conv_s0 / conv_s1 of those
+// neck_level left in lat[s] (hi_res), or copies of them
+int neck_tail(const Plan &p, Fwd &f, float *feat2) {
+    const ovo_hiera_config_t &c = f.c; const Ws &k = f.k;
+    const int S16 = p.S4 / 4, fd = c.fpn_dim;
+    float *top = ((uintptr_t)feat2 & 15) == 0 ? feat2 : k.lat[2];                  // (float4 stores: a misaligned feat2 gets a copy, as before)
+    k_topdown_add<<<ovo_grid((long long)p.n_lat[2] / 4, 256), 256, 0, f.hs>>>(k.lat[2], k.lat[3], top, f.B, S16, S16, fd);
+    LAUNCHED();
+    if (top != feat2) OVO_HIP(hipMemcpyAsync(feat2, top, p.n_lat[2] * 4, hipMemcpyDeviceToDevice, f.hs));
+    for (int s = 0; s < 2; ++s) {
+        float *feat = s ? f.feat1 : f.feat0;
+        const int n = s ? 64 : 32;
+        bool cast_done = false;
+        if (!c.hi_res) OVO_HIP(hipMemcpyAsync(feat, k.lat[s], p.n_lat[s] * 4, hipMemcpyDeviceToDevice, f.hs));
+        else if (!neck_fused(c, f.B, s))
+            TRY(gemm_from_f32(k.lat[s], p.level[s], fd, fd, nullptr, nullptr, 0.f, 2, k.cast, cast_done, s ? f.w.s1_w : f.w.s0_w, s ? f.w.s1_b : f.w.s0_b, feat, n, 0, n, 0, f.stream));
+    }
+    LAUNCHED();
+    return OVO_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
 size_t ovo_hiera_workspace_bytes(const ovo_hiera_config_t *cfg, int B) {
     if (!cfg || B <= 0) return 0;
     Plan p;
-    if (make_plan(*cfg, p) != 0) return 0;
+    if (make_plan(*cfg, B, p) != 0) return 0;
     return carve(*cfg, p, B, nullptr).bytes;
 }
 
@@ -553,195 +716,32 @@ int ovo_hiera_forward(const ovo_hiera_config_t *cfg, const ovo_hiera_weights_t *
         OVO_REQUIRE(c.dims[s] % 8 == 0 && c.heads[s] > 0 && c.dims[s] % c.heads[s] == 0 && (c.dims[s] / c.heads[s]) % 8 == 0 &&
                         c.blocks[s] > 0 && c.window[s] > 0, "bad stage config");
     Plan p;
-    OVO_REQUIRE(make_plan(c, p) == 0, "too many blocks");
+    OVO_REQUIRE(make_plan(c, B, p) == 0, "too many blocks");
     OVO_REQUIRE(w->patch_w && w->patch_b && w->pos && w->blocks, "missing weights");
-    Ws k = carve(c, p, B, ws);
+    for (int i = 0; i < p.n_blocks; ++i) {                   // everything a step would otherwise find missing half-way through the launches
+        const BlockShape &s = p.b[i];
+        OVO_REQUIRE(!s.pool || (s.g.wh % 2 == 0 && s.H % 2 == 0), "query pooling needs even windows");
+        OVO_REQUIRE(s.din == s.dout || (w->blocks[i].res_w && w->blocks[i].res_b && s.pool), "stage-change block without projection weights");
+        OVO_REQUIRE(s.stage_end < 0 || (w->neck_w[s.stage_end] && w->neck_b[s.stage_end]), "missing neck weights");
+    }
+    OVO_REQUIRE(!c.hi_res || (w->s0_w && w->s0_b && w->s1_w && w->s1_b), "missing conv_s0 / conv_s1 weights");
+    // (the fused neck has no lateral buffer to fall back to: the layout was decided without the pointers -- ovo_hip.h states the requirement)
+    for (int s = 0; s < 2; ++s)
+        OVO_REQUIRE(!neck_fused(c, B, s) || (((uintptr_t)(s ? feat1 : feat0) | (uintptr_t)w->neck_w[s] | (uintptr_t)(s ? w->s1_w : w->s0_w)) & 15) == 0,
+                    "feat0 / feat1 and the neck weights must be 16-byte aligned");
+    const Ws k = carve(c, p, B, ws);
     OVO_REQUIRE(ws_bytes >= k.bytes, "workspace too small");
-    hipStream_t hs = (hipStream_t)stream;
-    const int S4 = c.image_size / 4;
-    const long long T0 = (long long)S4 * S4;
-
-    // patch embedding (+ position embedding through the GEMM epilogue), one image at a time (pos has no batch dim)
-    const int pe_rc = patch_embed_direct(images, c.image_size, c.dims[0], w->patch_w, 192, w->patch_b, w->pos, k.x, B, hs);
-    if (pe_rc == OVO_E_UNSUPPORTED) {
-        TRY(ovo_im2col(images, B, 3, c.image_size, c.image_size, 7, 4, 3, k.col, 192, stream));
-        for (int b = 0; b < B; ++b)
-            TRY(gemm(k.col + (size_t)b * T0 * 192, 192, w->patch_w, 192, w->patch_b, k.x + (size_t)b * T0 * c.dims[0], c.dims[0], 0, w->pos,
-                     c.dims[0], T0, c.dims[0], 192, 0, stream));
-    } else
-        TRY(pe_rc);
-
-    float *x = k.x, *spare = k.xr;
-    long long att_rows = -1;
-    int att_kout = 0;
+    Fwd f = {c, *w, k, B, feat0, feat1, stream, (hipStream_t)stream, k.x, k.xr, k.x, false, -1, 0};
+    TRY(patch_embed(p, images, f));
     for (int i = 0; i < p.n_blocks; ++i) {
-        const ovo_hiera_block_t &L = w->blocks[i];
-        const int din = p.dim_in[i], dout = p.dim_out[i], H = p.Hin[i], Ho = p.pool[i] ? H / 2 : H;
-        const int kin = padk(din), kout = padk(dout), hd = dout / p.heads[i];
-        const Grid g = make_grid(B, H, H, p.ws[i]);
-        OVO_REQUIRE(!p.pool[i] || (g.wh % 2 == 0 && H % 2 == 0), "query pooling needs even windows");
-        const long long tok_out = (long long)B * Ho * Ho;
-
-        // LayerNorm 1 happens inside the A-operand load of its consumers where the streaming GEMM runs them (stages 1-2), else as a pass into k.h
-        bool h_done = false;
-        const float *residual = x;
-        if (din != dout) {                                   // skip = maxpool(proj(LN(x)))
-            OVO_REQUIRE(L.res_w && L.res_b && p.pool[i], "stage-change block without projection weights");
-            // projection + 2 x 2 max-pool in one launch where the streaming GEMM covers it (pooled rows straight into `spare`) ...
-            ovo_gemm_t q;
-            q.A = nullptr; q.lda = kin; q.W = L.res_w; q.ldw = kin; q.bias = L.res_b; q.C = spare; q.ldc = dout; q.add = nullptr; q.ld_add = 0;
-            q.M = (int)g.rows; q.N = dout; q.K = kin; q.in_dtype = 2; q.out_dtype = 0; q.act = 0; q.alpha = 1.0f;
-            const ovo_window_t wd = {g.B, g.H, g.W, g.wh, g.ww};
-            const int rc = g.ws > 0 ? ovo_gemm_detail::gemm_f32a_stream(&q, &wd, x, din, L.ln1_g, L.ln1_b, c.ln_eps, 1, 1, stream) : OVO_E_UNSUPPORTED;
-            if (rc == OVO_E_UNSUPPORTED) {                   // ... else every token's projection into k.tmp, then the pool pass
-                TRY(gemm_from_f32(x, g, din, kin, L.ln1_g, L.ln1_b, c.ln_eps, 1, k.h, h_done, L.res_w, L.res_b, k.tmp, dout, 0, dout, 0, stream));
-                k_pool_unwindow<<<ovo_grid(tok_out * dout, 256), 256, 0, hs>>>(k.tmp, g, dout, spare);
-            } else if (rc != OVO_OK) {
-                return rc;
-            }
-            residual = spare;
-        }
-        const long long n_win = (long long)B * g.nwh * g.nww;
-        const int tk = g.wh * g.ww, tq = p.pool[i] ? tk / 4 : tk;
-        // K-padding columns of the attention output must be zero; the attention kernels only write the real ones, so they STAY zero from block to
-        // block while rows x row width do not change (the blocks of one stage): one fill per layout instead of one per block (3 of 5 for hiera_b+)
-        if (kout != dout && (att_rows != (long long)n_win * tq || att_kout != kout)) {
-            OVO_HIP(hipMemsetAsync(k.att, 0, (size_t)n_win * tq * kout * 2, hs));
-            att_rows = (long long)n_win * tq; att_kout = kout;
-        } else if (kout == dout) {
-            att_rows = -1;                                       // every column written: the next padded layout starts from a fresh fill
-        }
-        // stage 1 of hiera_b+ and the stage-change block after it (round 5): LayerNorm -> QKV (-> 2 x 2 pool of q) -> window attention in one pass over x
-        // per pair of heads, q | k | v never written (winattn.hip)
-        int fused_attn = OVO_E_UNSUPPORTED;
-        if (g.ws > 0 && !h_done && cfg->q_prescaled)
-            fused_attn = ovo_gemm_detail::win_attn_launch(x, B, H, H, g.ws, din, dout, p.heads[i], p.pool[i] ? 1 : 0, L.ln1_g, L.ln1_b, c.ln_eps, L.qkv_w, kin,
-                                                          L.qkv_b, k.att, kout, hs);
-        if (fused_attn != OVO_OK && fused_attn != OVO_E_UNSUPPORTED) return fused_attn;
-        if (fused_attn == OVO_E_UNSUPPORTED) {
-        // QKV; at a stage change the q columns are pooled 2 x 2 in the product's epilogue where the streaming GEMM runs it (else k_qpool below)
-        bool q_pooled = false;
-        if (p.pool[i] && g.ws > 0 && !h_done) {
-            ovo_gemm_t q;
-            q.A = nullptr; q.lda = kin; q.W = L.qkv_w; q.ldw = kin; q.bias = L.qkv_b; q.C = k.qkv; q.ldc = 3 * dout; q.add = nullptr; q.ld_add = 0;
-            q.M = (int)g.rows; q.N = 3 * dout; q.K = kin; q.in_dtype = 2; q.out_dtype = 2; q.act = 0; q.alpha = 1.0f;
-            const ovo_window_t wd = {g.B, g.H, g.W, g.wh, g.ww};
-            const int rc = ovo_gemm_detail::gemm_f32a_stream(&q, &wd, x, din, L.ln1_g, L.ln1_b, c.ln_eps, 1, 0, stream, k.qp, dout);
-            if (rc == OVO_OK) q_pooled = true;
-            else if (rc != OVO_E_UNSUPPORTED) return rc;
-        }
-        if (!q_pooled)
-            TRY(gemm_from_f32(x, g, din, kin, L.ln1_g, L.ln1_b, c.ln_eps, 1, k.h, h_done, L.qkv_w, L.qkv_b, k.qkv, 3 * dout, 2, 3 * dout, 0, stream));
-        ovo_attention_t a = {};
-        a.k = k.qkv + dout; a.v = k.qkv + 2 * dout; a.o = k.att;
-        a.k_sb = a.v_sb = (int64_t)tk * 3 * dout; a.k_sh = a.v_sh = hd; a.k_st = a.v_st = 3 * dout;
-        if (p.pool[i]) {
-            if (!q_pooled) {
-                const long long total8 = n_win * tq * (dout / 8);
-                if (dout % 8 == 0 && total8 < (1ll << 32) - (1ll << 22) && (((uintptr_t)k.qkv | (uintptr_t)k.qp) & 15) == 0)
-                    k_qpool8<<<ovo_grid(total8, 256, 256 * 16), 256, 0, hs>>>(k.qkv, (uint32_t)total8, g.wh, g.ww, dout, k.qp);
-                else k_qpool<<<ovo_grid(n_win * tq * dout, 256), 256, 0, hs>>>(k.qkv, n_win, g.wh, g.ww, dout, k.qp);
-            }
-            a.q = k.qp; a.q_sb = (int64_t)tq * dout; a.q_sh = hd; a.q_st = dout;
-        } else {
-            a.q = k.qkv; a.q_sb = a.k_sb; a.q_sh = hd; a.q_st = 3 * dout;
-        }
-        a.o_sb = (int64_t)tq * kout; a.o_sh = hd; a.o_st = kout;
-        a.B = (int)n_win; a.H = p.heads[i]; a.Tq = tq; a.Tk = tk; a.hd = hd; a.scale = cfg->q_prescaled ? 0.0f : 1.0f / sqrtf((float)hd);
-        TRY(ovo_attention(&a, stream));
-        }
-        // output projection; its epilogue also takes the rows from window order (pooled window size) back to spatial order and
-        // adds the residual (ovo_gemm_unwindow; k_unwindow_add was a pass of its own).  In place: same-dim blocks add onto x; at a
-        // stage change the old x is dead (only LN1 read it) and the pooled skip lives in `spare`, so the smaller new stream is
-        // written over the old buffer.
-        const Grid go = make_grid(B, Ho, Ho, p.ws[i] > 0 ? (p.pool[i] ? p.ws[i] / 2 : p.ws[i]) : 0);
-        bool ln2_done = false;
-        {
-            ovo_gemm_t og;
-            og.A = k.att; og.lda = kout; og.W = L.out_w; og.ldw = kout; og.bias = L.out_b; og.C = x; og.ldc = dout; og.add = residual; og.ld_add = dout;
-            og.M = (int)(n_win * tq); og.N = dout; og.K = kout; og.in_dtype = 2; og.out_dtype = 0; og.act = 0; og.alpha = 1.0f;
-            const ovo_window_t ow = {go.B, go.H, go.W, go.wh, go.ww};
-            // stage 3 (N = 448), OPT-IN (OVO_HIERA_PROJ_LN=1): a full-row 128 x 448 tile, norm2 of the result rows from its accumulators straight into k.h, the
-            // MLP below then skips its LayerNorm pass.  MEASURED AND LEFT OFF (tools/rowln_bench.py, profiles/r05c_rowln_bench.txt): 87 us against 64 (128 x 64
-            // tiles) + 28 (LayerNorm pass) alone, but 25 us per block SLOWER inside the forward (15.97 vs 15.57 ms per 12 frames): one 512-thread workgroup
-            // per CU with a two-stage ring of 72 KB K-tiles does not overlap its neighbours the way the small tiles and the copy-rate LayerNorm pass do.
-            const bool rowln = ovo_knob_set("OVO_HIERA_PROJ_LN");
-            int rc = OVO_E_UNSUPPORTED;
-            if (rowln && dout == 448 && kout == dout)
-                rc = ovo_gemm_detail::gemm_unwindow_rowln(&og, &ow, L.ln2_g, L.ln2_b, c.ln_eps, k.h, kout, stream);
-            if (rc == OVO_OK) ln2_done = true;
-            else if (rc != OVO_E_UNSUPPORTED) return rc;
-            else TRY(ovo_gemm_unwindow(&og, &ow, stream));
-        }
-        // MLP
-        const Grid gi = make_grid(B, Ho, Ho, 0);
-        h_done = false;
-        // Row chunks (round 5): the hidden activations of stages 1-2 (12 frames: 786 432 x 448 and 196 608 x 896 bf16 = 704 / 352 MB) were written by
-        // FC1 and read back by FC2 through HBM.  The MLP is row-wise, so FC1 / FC2 alternate over chunks of rows whose hidden block fits the 256 MB
-        // Infinity Cache with room to spare, every chunk through the SAME hidden buffer: FC2 reads what FC1 just left in the cache and the next
-        // chunk overwrites those lines before they are written back.  MEASURED AND LEFT OFF (bench.py, one box, 12-frame groups): one pass 409.4
-        // frames/s, 96 MB chunks 404.0, 48 MB 398.2, 24 MB 387.1 -- the write stream of the FC1 chunks is not absorbed by the cache (the launches
-        // stay write-bound) and every extra launch pair adds its ramp.  OVO_HIERA_MLP_CHUNK_MB = chunk size (default 0 = one pass over all rows).
-        const long long chunk_mb = ovo_knob_int("OVO_HIERA_MLP_CHUNK_MB", 0);
-        const long long hid_row = (long long)4 * dout * 2;
-        long long chunk_rows = chunk_mb > 0 ? (chunk_mb << 20) / hid_row / 4096 * 4096 : 0;
-        if (chunk_rows <= 0 || tok_out < 2 * chunk_rows || tok_out * hid_row <= (200ll << 20)) chunk_rows = tok_out;   // (a hidden block the cache holds anyway: one pass)
-        // stages 1-2 (hidden width 4 dout, tall streams): LayerNorm -> FC1 -> GELU -> FC2 -> + residual in one pass, the hidden row in registers (mlp_stream.hip)
-        const int fused = ovo_gemm_detail::mlp_stream_launch(x, tok_out, dout, L.ln2_g, L.ln2_b, c.ln_eps, L.fc1_w, kout, L.fc1_b, 4 * dout, L.fc2_w, 4 * dout, L.fc2_b, hs);
-        if (fused != OVO_OK && fused != OVO_E_UNSUPPORTED) return fused;
-        for (long long r0 = fused == OVO_OK ? tok_out : 0; r0 < tok_out; r0 += chunk_rows) {
-            const long long nr = tok_out - r0 < chunk_rows ? tok_out - r0 : chunk_rows;
-            const Grid gc = chunk_rows == tok_out ? gi : make_grid(1, (int)nr, 1, 0);
-            bool h_ready = chunk_rows == tok_out ? (h_done || ln2_done) : false;      // (a chunked pass re-normalises its rows: ln2_done is for the one-pass form only)
-            float *xc = x + r0 * dout;
-            TRY(gemm_from_f32(xc, gc, dout, kout, L.ln2_g, L.ln2_b, c.ln_eps, 1, k.h, h_ready, L.fc1_w, L.fc1_b, k.u, 4 * dout, 2, 4 * dout, 1, stream));
-            TRY(gemm(k.u, 4 * dout, L.fc2_w, 4 * dout, L.fc2_b, xc, dout, 0, xc, dout, nr, dout, 4 * dout, 0, stream));
-        }
-        h_done = false;
-        LAUNCHED();
-
-        if (p.stage_end[i] >= 0) {                           // FPN lateral 1x1 conv of this stage's output
-            const int s = p.stage_end[i];
-            OVO_REQUIRE(w->neck_w[s] && w->neck_b[s], "missing neck weights");
-            if (neck_fused(c, B, s)) {                       // levels 0 / 1 with hi_res: lateral + conv_s0 / conv_s1 in one launch, the lateral in registers
-                const void *cw = s == 0 ? w->s0_w : w->s1_w;
-                const float *cb = s == 0 ? w->s0_b : w->s1_b;
-                float *feat = s == 0 ? feat0 : feat1;
-                OVO_REQUIRE(cw && cb, "missing conv_s0 / conv_s1 weights");
-                // (there is no lateral buffer to fall back to: the layout was decided without the pointers -- ovo_hip.h states the requirement)
-                OVO_REQUIRE((((uintptr_t)feat | (uintptr_t)w->neck_w[s] | (uintptr_t)cw) & 15) == 0, "feat0 / feat1 and the neck weights must be 16-byte aligned");
-                TRY(ovo_gemm_detail::neck_stream_launch(x, tok_out, dout, w->neck_w[s], kout, w->neck_b[s], c.fpn_dim, cw, c.fpn_dim, cb, feat, s == 0 ? 32 : 64, hs));
-                LAUNCHED();
-                continue;
-            }
-            bool cast_done = false;
-            TRY(gemm_from_f32(x, gi, dout, kout, nullptr, nullptr, 0.f, 2, k.cast, cast_done, w->neck_w[s], w->neck_b[s], k.lat[s], c.fpn_dim, 0,
-                              c.fpn_dim, 0, stream));
-        }
+        const BlockShape &s = p.b[i]; const ovo_hiera_block_t &L = w->blocks[i];
+        TRY(skip_path(s, L, f));
+        TRY(attention(s, L, f));
+        TRY(out_projection(s, L, f));
+        TRY(mlp(s, L, f));
+        TRY(neck_level(s, f));
     }
-    // top-down on the coarse levels: feat2 = level 2 + up(level 3), written where the caller wants it; levels 0 and 1 are laterals only.  With hi_res they
-    // went through conv_s0 / conv_s1 at their stage's end when neck_fused() (one launch each from the stream, no lateral in memory), else here
-    const int S16 = c.image_size / 16;
-    float *top = ((uintptr_t)feat2 & 15) == 0 ? feat2 : k.lat[2];                  // (float4 stores: a misaligned feat2 gets a copy, as before)
-    k_topdown_add<<<ovo_grid((long long)B * S16 * S16 * (c.fpn_dim / 4), 256), 256, 0, hs>>>(k.lat[2], k.lat[3], top, B, S16, S16, c.fpn_dim);
-    LAUNCHED();
-    if (top != feat2) OVO_HIP(hipMemcpyAsync(feat2, top, (size_t)B * S16 * S16 * c.fpn_dim * 4, hipMemcpyDeviceToDevice, hs));
-    const long long t0 = (long long)B * T0, t1 = t0 / 4;
-    if (c.hi_res) {
-        OVO_REQUIRE(w->s0_w && w->s0_b && w->s1_w && w->s1_b, "missing conv_s0 / conv_s1 weights");
-        bool cast_done = false;
-        const Grid g0 = make_grid(B, S4, S4, 0), g1 = make_grid(B, S4 / 2, S4 / 2, 0);
-        if (!neck_fused(c, B, 0))
-            TRY(gemm_from_f32(k.lat[0], g0, c.fpn_dim, c.fpn_dim, nullptr, nullptr, 0.f, 2, k.cast, cast_done, w->s0_w, w->s0_b, feat0, 32, 0, 32, 0, stream));
-        cast_done = false;
-        if (!neck_fused(c, B, 1))
-            TRY(gemm_from_f32(k.lat[1], g1, c.fpn_dim, c.fpn_dim, nullptr, nullptr, 0.f, 2, k.cast, cast_done, w->s1_w, w->s1_b, feat1, 64, 0, 64, 0, stream));
-    } else {
-        OVO_HIP(hipMemcpyAsync(feat0, k.lat[0], (size_t)t0 * c.fpn_dim * 4, hipMemcpyDeviceToDevice, hs));
-        OVO_HIP(hipMemcpyAsync(feat1, k.lat[1], (size_t)t1 * c.fpn_dim * 4, hipMemcpyDeviceToDevice, hs));
-    }
-    LAUNCHED();
-    return OVO_OK;
+    return neck_tail(p, f, feat2);
 }
 
 }  // extern "C"
