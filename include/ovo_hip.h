@@ -673,6 +673,32 @@ int ovo_map_reanchor(const float *xyz, const int32_t *ids, const int32_t *ins, c
                      int32_t *ins_out, uint8_t *rgb_out, int64_t cap_out, const int64_t *seg_src_host, const int64_t *seg_dst_host,
                      const float *seg_T_host, int K, void *ws, size_t ws_bytes, ovo_stream_t stream);
 
+/* Everything else that is indexed by map row, through the SAME table (ABI v17; FramePipeline.close_loop): the round pipeline's per-point dense state --
+ * acc f32[*, D] (descriptor sums), cnt i32[*], and the resident class map cls i64[*] / conf f32[*] -- moved OUT OF PLACE in one launch.  Rows are
+ * block-cyclic on both sides, by the rule of ovo_scatter_accum_query: global row g lies in block b = g / shard_block, which rank b % shards holds as its
+ * local block b / shards.
+ *   source       shard-major [src_shards, src_rows_local, ...], exactly what an all-gather of the ranks' shards returns (src_shards = 1: plain point
+ *                order), holding the n_src rows of the old map
+ *   destination  THIS rank's shard (shard_rank of shard_count), rows_out local rows
+ * For every destination global row d in [0, n_fill) that this rank owns:
+ *   d <  total = seg_dst[K]   seg_dst[k] <= d < seg_dst[k+1]: the four arrays' rows of source global row seg_src[k] + d - seg_dst[k], copied bit for bit
+ *                             (no arithmetic touches the payload: NaN payloads, -0.0 and denormals survive)
+ *   d >= total                the empty state: acc row = 0, cnt = 0, cls = empty_cls, conf = empty_conf
+ * Rows other ranks own do not exist here; local rows past this rank's rows of n_fill are not touched.  cls / conf and cls_out / conf_out may be NULL
+ * together (a pipeline without the resident class map).  K == 0 is NOT a no-op: every row below n_fill becomes empty (the table and ws may then be NULL).
+ * Out of place only.  The table (HOST arrays, as for ovo_map_reanchor) and every argument are checked before anything is queued; a violation returns
+ * OVO_E_ARG with nothing launched:  seg_dst starts at 0 and never decreases; every segment inside [0, n_src];  n_fill >= total;  src_rows_local holds
+ * every source rank's rows of n_src and rows_out this rank's rows of n_fill;  D > 0, D % 4 == 0, acc and acc_out 16-byte aligned (a lane moves 16
+ * bytes);  shard_block a power of two;  0 <= shard_rank < shard_count, src_shards > 0;  no output or workspace range overlapping a source range or
+ * another output.  ws: device scratch of ovo_dense_repack_workspace_bytes(K) bytes (8-byte aligned) the table is staged into on the stream; a pinned
+ * table has to stay unchanged until the stream has passed the call.  A row's result depends on its source row and the table alone: bit-identical from
+ * run to run. */
+size_t ovo_dense_repack_workspace_bytes(int K);
+int ovo_dense_repack(const float *acc, const int32_t *cnt, const int64_t *cls, const float *conf, int D, int src_shards, int64_t src_rows_local,
+                     int64_t n_src, float *acc_out, int32_t *cnt_out, int64_t *cls_out, float *conf_out, int64_t rows_out, int shard_rank,
+                     int shard_count, int shard_block, int64_t n_fill, int64_t empty_cls, float empty_conf, const int64_t *seg_src_host,
+                     const int64_t *seg_dst_host, int K, void *ws, size_t ws_bytes, ovo_stream_t stream);
+
 
 /* =============================================================================================
  * The keyframe chain without host round trips (MI355X extension of a6 / a9; what the reference does with a `.sum()` / vstack

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "lib", "libovo_hip.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 E_UNSUPPORTED = -3          # OVO_E_UNSUPPORTED: the entry point does not cover this shape; the caller takes its general path
 
 
@@ -222,6 +222,8 @@ _SIGNATURES = {
     "ovo_remap_instances": (_I32, [_P, _I64, _P, _I32, _P]),
     "ovo_map_reanchor_workspace_bytes": (_SZ, [_I32]),
     "ovo_map_reanchor": (_I32, [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _I32, _P, _SZ, _P]),
+    "ovo_dense_repack_workspace_bytes": (_SZ, [_I32]),
+    "ovo_dense_repack": (_I32, [_P, _P, _P, _P, _I32, _I32, _I64, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I64, _I64, _F32, _P, _P, _I32, _P, _SZ, _P]),
     "ovo_sam_i2t_attention": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_sam_t2i_attention": (_I32, [_P, _P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_paint_segmap": (_I32, [_P, _I32, _I64, _P, _P]),

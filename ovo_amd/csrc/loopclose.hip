@@ -10,6 +10,8 @@
 //   k_map_reanchor     : the whole point map moved OUT OF PLACE in one launch -- every surviving keyframe's slice of rows transformed by its
 //                        own 3 x 4 matrix and re-packed in the tracker's keyframe order (the reference: one slice, cat, einsum per keyframe,
 //                        then four torch.cat over the whole map)
+//   k_dense_repack     : everything ELSE that is indexed by map row -- the round pipeline's per-point accumulators and resident class map, block-cyclic
+//                        shards of them -- moved through the same segment table, a bit-for-bit row copy at 16 bytes per lane
 #include "common.h"
 
 namespace {
@@ -102,10 +104,131 @@ __global__ void __launch_bounds__(256) k_map_reanchor(const float *__restrict__ 
     }
 }
 
+// ---- the dense state through the same table (ovo_dense_repack).  Rows are BLOCK-CYCLIC on both sides: global row g sits in block g >> bl, which rank
+// (g >> bl) % shards holds as its local block (g >> bl) / shards (k_scatter_query's rule, fusion.hip); the source is shard-major [src_shards][src_rows_local].
+// A WAVE owns DR_ROWS consecutive local destination rows of this rank's shard.  Their states are found first, by a loop every lane runs with the same
+// values: the global row d, then -- d < total -- its segment: ONE binary search for the run's first row (and again where the run crosses into its next
+// shard block, shard_count - 1 blocks further on in global rows), a forward walk for the rows after it (rows ascend, so the walk never restarts).  Lane j
+// keeps row j's flat source row (DR_FILL: the empty state; DR_SKIP: past n_fill, not touched) and copies its 4- and 8-byte fields; the accumulator rows
+// then stream as one flat list of 16-byte pieces, 64 contiguous pieces per wave-instruction, DR_UNROLL loads issued before the first store (D = 1024:
+// two 4 KB rows in flight per wave).  Plain vector loads and stores, no arithmetic on the payload: NaN payloads, -0.0 and denormals pass through.
+constexpr int DR_ROWS = 16, DR_UNROLL = 8;
+constexpr long long DR_FILL = -1, DR_SKIP = -2;
+
+struct DenseRepack {
+    const float *acc; const int32_t *cnt; const int64_t *cls; const float *conf;
+    float *acc_o; int32_t *cnt_o; int64_t *cls_o; float *conf_o;
+    const int64_t *seg_dst, *seg_src;
+    long long total, n_fill, rows_needed, src_rows_local, empty_cls;
+    float empty_conf;
+    int K, C, src_shards, shard_rank, shard_count, bl;      // C = D / 4 pieces per row, bl = log2(shard_block)
+};
+
+__device__ __forceinline__ long long dr_flat_source(const DenseRepack &a, long long s) {
+    if (a.src_shards == 1) return s;
+    const long long b = s >> a.bl;
+    return (b % a.src_shards) * a.src_rows_local + (((b / a.src_shards) << a.bl) | (s & ((1LL << a.bl) - 1)));
+}
+
+__global__ void __launch_bounds__(256) k_dense_repack(const DenseRepack a) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long long l0 = ((long long)blockIdx.x * 4 + wave) * DR_ROWS;
+    if (l0 >= a.rows_needed) return;
+    const long long mask = (1LL << a.bl) - 1;
+    long long mine = DR_SKIP;
+    int k = -1;
+    for (int j = 0; j < DR_ROWS; ++j) {
+        const long long l = l0 + j;
+        if (l >= a.rows_needed) break;
+        const long long d = ((((l >> a.bl) * a.shard_count + a.shard_rank) << a.bl) | (l & mask));
+        long long st = DR_SKIP;
+        if (d < a.total) {
+            if (k < 0 || (l & mask) == 0) {                      // first row of the run, or of the next shard block: search
+                int lo = 0, hi = a.K;                            // first index in [0, K] whose seg_dst > d (exists: seg_dst[K] = total > d; >= 1: seg_dst[0] = 0)
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (a.seg_dst[mid] > d) hi = mid; else lo = mid + 1;
+                }
+                k = lo - 1;
+            } else {
+                while (a.seg_dst[k + 1] <= d) ++k;               // k + 1 <= K: seg_dst[K] = total > d
+            }
+            st = dr_flat_source(a, a.seg_src[k] + (d - a.seg_dst[k]));
+        } else if (d < a.n_fill) {
+            st = DR_FILL;
+        }
+        if (lane == j) mine = st;
+    }
+    if (lane < DR_ROWS && mine != DR_SKIP) {
+        const long long l = l0 + lane;
+        a.cnt_o[l] = mine >= 0 ? a.cnt[mine] : 0;
+        if (a.cls_o) {
+            a.cls_o[l] = mine >= 0 ? a.cls[mine] : a.empty_cls;
+            a.conf_o[l] = mine >= 0 ? a.conf[mine] : a.empty_conf;
+        }
+    }
+    const int C = a.C, n_items = DR_ROWS * C;
+    const float4 *src4 = (const float4 *)a.acc;
+    float4 *dst4 = (float4 *)a.acc_o + l0 * C;
+    for (int base = 0; base < n_items; base += 64 * DR_UNROLL) {
+        float4 v[DR_UNROLL];
+        long long st[DR_UNROLL];
+#pragma unroll
+        for (int u = 0; u < DR_UNROLL; ++u) {
+            const int i = base + u * 64 + lane;
+            const int j = i < n_items ? i / C : DR_ROWS - 1;
+            st[u] = __shfl(mine, j, 64);                         // (every lane takes part: the row's state lives in lane j)
+            if (i >= n_items) st[u] = DR_SKIP;
+            v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (st[u] >= 0) v[u] = src4[st[u] * C + (i - j * C)];
+        }
+#pragma unroll
+        for (int u = 0; u < DR_UNROLL; ++u)
+            if (st[u] != DR_SKIP) dst4[base + u * 64 + lane] = v[u];
+    }
+}
+
 // byte ranges [a, a + na) and [b, b + nb) share a byte
 inline bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return na && nb && pa < pb + nb && pb < pa + na;
+}
+
+// The checks every segment table gets on the host before a kernel may trust it (ovo_map_reanchor, ovo_dense_repack): nullptr, or what is wrong with it.
+inline const char *segment_table_error(const int64_t *seg_src, const int64_t *seg_dst, int K, int64_t n_src) {
+    if (seg_dst[0] != 0) return "seg_dst must start at 0";
+    for (int k = 0; k < K; ++k) {
+        const int64_t len = seg_dst[k + 1] - seg_dst[k];
+        if (len < 0) return "seg_dst decreases";
+        if (!(seg_src[k] >= 0 && seg_src[k] <= n_src && len <= n_src - seg_src[k])) return "segment outside the source map";
+    }
+    return nullptr;
+}
+
+// nullptr, or which of the `nd` outputs (the workspace among them) overlaps one of the `ns` sources or an earlier output; null pointers are skipped
+inline const char *overlap_error(const void *const *src, const size_t *src_bytes, int ns, const void *const *dst, const size_t *dst_bytes, int nd) {
+    for (int d = 0; d < nd; ++d) {
+        if (!dst[d]) continue;
+        for (int s = 0; s < ns; ++s) if (src[s] && ranges_overlap(dst[d], dst_bytes[d], src[s], src_bytes[s])) return "an output buffer aliases a source buffer";
+        for (int e = 0; e < d; ++e) if (dst[e] && ranges_overlap(dst[d], dst_bytes[d], dst[e], dst_bytes[e])) return "output buffers overlap";
+    }
+    return nullptr;
+}
+
+// seg_dst i64[K + 1] | seg_src i64[K] at the start of ws.  Pageable host memory is staged by the runtime before these return; a PINNED table has to
+// stay as it is until the stream has passed the call.
+inline hipError_t stage_segment_table(void *ws, const int64_t *seg_src_host, const int64_t *seg_dst_host, int K, hipStream_t st) {
+    int64_t *d_dst = (int64_t *)ws, *d_src = d_dst + K + 1;
+    const hipError_t e = hipMemcpyAsync(d_dst, seg_dst_host, sizeof(int64_t) * ((size_t)K + 1), hipMemcpyHostToDevice, st);
+    return e != hipSuccess ? e : hipMemcpyAsync(d_src, seg_src_host, sizeof(int64_t) * (size_t)K, hipMemcpyHostToDevice, st);
+}
+
+// rows of rank r's shard that hold rows of [0, n): block-cyclic over `shards` ranks in blocks of 2^bl rows (FramePipeline.local_rows)
+inline int64_t shard_local_rows(int64_t n, int r, int shards, int bl) {
+    const int64_t full = n >> bl, rem = n & (((int64_t)1 << bl) - 1);
+    const int64_t mine = full > r ? (full - r + shards - 1) / shards : 0;
+    return (mine << bl) + (full % shards == r ? rem : 0);
 }
 
 }  // namespace
@@ -157,35 +280,81 @@ extern "C" int ovo_map_reanchor(const float *xyz, const int32_t *ids, const int3
     if (K == 0) return OVO_OK;
     OVO_REQUIRE(seg_src_host && seg_dst_host && seg_T_host, "null segment table");
     // every entry is range-checked HERE, before anything is queued: the kernel trusts the table
-    OVO_REQUIRE(seg_dst_host[0] == 0, "seg_dst must start at 0");
-    for (int k = 0; k < K; ++k) {
-        const int64_t len = seg_dst_host[k + 1] - seg_dst_host[k];
-        OVO_REQUIRE(len >= 0, "seg_dst decreases");
-        OVO_REQUIRE(seg_src_host[k] >= 0 && seg_src_host[k] <= n_src && len <= n_src - seg_src_host[k], "segment outside the source map");
-    }
+    const char *bad = segment_table_error(seg_src_host, seg_dst_host, K, n_src);
+    OVO_REQUIRE(!bad, bad);
     const int64_t total = seg_dst_host[K];
     OVO_REQUIRE(total <= cap_out, "seg_dst[K] exceeds the output capacity");
     if (total == 0) return OVO_OK;
     OVO_REQUIRE(xyz && ids && ins && xyz_out && ids_out && ins_out && (rgb_out || !rgb), "null buffer");
     OVO_REQUIRE(ws && ws_bytes >= ovo_map_reanchor_workspace_bytes(K) && ((uintptr_t)ws & 7) == 0, "workspace missing, too small or not 8-byte aligned");
     const void *src[4] = {xyz, ids, ins, rgb}, *dst[5] = {xyz_out, ids_out, ins_out, rgb ? rgb_out : nullptr, ws};
-    const size_t row_bytes[4] = {12, 4, 4, 3};
-    for (int d = 0; d < 5; ++d) {
-        if (!dst[d]) continue;
-        const size_t nd = d < 4 ? row_bytes[d] * (size_t)cap_out : ws_bytes;
-        for (int s = 0; s < 4; ++s) OVO_REQUIRE(!src[s] || !ranges_overlap(dst[d], nd, src[s], row_bytes[s] * (size_t)n_src), "an output buffer aliases a source buffer");
-        for (int e = 0; e < d; ++e) OVO_REQUIRE(!dst[e] || !ranges_overlap(dst[d], nd, dst[e], e < 4 ? row_bytes[e] * (size_t)cap_out : ws_bytes), "output buffers overlap");
-    }
+    const size_t src_bytes[4] = {12 * (size_t)n_src, 4 * (size_t)n_src, 4 * (size_t)n_src, 3 * (size_t)n_src};
+    const size_t dst_bytes[5] = {12 * (size_t)cap_out, 4 * (size_t)cap_out, 4 * (size_t)cap_out, 3 * (size_t)cap_out, ws_bytes};
+    bad = overlap_error(src, src_bytes, 4, dst, dst_bytes, 5);
+    OVO_REQUIRE(!bad, bad);
     const int64_t blocks = (total + REANCHOR_ROWS - 1) / REANCHOR_ROWS;
     OVO_REQUIRE(blocks <= 0x7fffffffLL, "map too large for one launch");
     hipStream_t st = (hipStream_t)stream;
     int64_t *d_dst = (int64_t *)ws, *d_src = d_dst + K + 1;
     float *d_T = (float *)(d_src + K);
-    // pageable host memory is staged by the runtime before these return; a PINNED table has to stay as it is until the stream has passed the call
-    OVO_HIP(hipMemcpyAsync(d_dst, seg_dst_host, sizeof(int64_t) * ((size_t)K + 1), hipMemcpyHostToDevice, st));
-    OVO_HIP(hipMemcpyAsync(d_src, seg_src_host, sizeof(int64_t) * (size_t)K, hipMemcpyHostToDevice, st));
+    OVO_HIP(stage_segment_table(ws, seg_src_host, seg_dst_host, K, st));
     OVO_HIP(hipMemcpyAsync(d_T, seg_T_host, sizeof(float) * 12 * (size_t)K, hipMemcpyHostToDevice, st));
     k_map_reanchor<<<(unsigned)blocks, 256, 0, st>>>(xyz, ids, ins, rgb, xyz_out, ids_out, ins_out, rgb ? rgb_out : nullptr, d_dst, d_src, d_T, K, total);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
+
+// workspace layout: seg_dst i64 [K + 1] | seg_src i64 [K]
+extern "C" size_t ovo_dense_repack_workspace_bytes(int K) { return K > 0 ? sizeof(int64_t) * (2 * (size_t)K + 1) : 0; }
+
+extern "C" int ovo_dense_repack(const float *acc, const int32_t *cnt, const int64_t *cls, const float *conf, int D, int src_shards, int64_t src_rows_local,
+                                int64_t n_src, float *acc_out, int32_t *cnt_out, int64_t *cls_out, float *conf_out, int64_t rows_out, int shard_rank,
+                                int shard_count, int shard_block, int64_t n_fill, int64_t empty_cls, float empty_conf, const int64_t *seg_src_host,
+                                const int64_t *seg_dst_host, int K, void *ws, size_t ws_bytes, ovo_stream_t stream) {
+    // everything is checked HERE, before anything is queued: the kernel trusts the table and the shapes
+    OVO_REQUIRE(K >= 0 && n_src >= 0 && n_fill >= 0 && rows_out >= 0 && src_rows_local >= 0, "bad argument");
+    OVO_REQUIRE(D > 0 && D % 4 == 0, "D must be a positive multiple of 4");
+    OVO_REQUIRE(shard_block > 0 && (shard_block & (shard_block - 1)) == 0, "shard_block must be a power of two");
+    OVO_REQUIRE(shard_count > 0 && shard_rank >= 0 && shard_rank < shard_count && src_shards > 0, "bad shard layout");
+    int bl = 0;
+    while ((1 << bl) < shard_block) ++bl;
+    int64_t total = 0;
+    if (K > 0) {
+        OVO_REQUIRE(seg_src_host && seg_dst_host, "null segment table");
+        const char *bad = segment_table_error(seg_src_host, seg_dst_host, K, n_src);
+        OVO_REQUIRE(!bad, bad);
+        total = seg_dst_host[K];
+    }
+    OVO_REQUIRE(n_fill >= total, "seg_dst[K] exceeds n_fill");
+    int64_t src_need = shard_local_rows(n_src, 0, src_shards, bl);                       // rank 0 holds the most complete blocks, the partial block's owner its rest
+    const int64_t last = shard_local_rows(n_src, (int)((n_src >> bl) % src_shards), src_shards, bl);
+    if (last > src_need) src_need = last;
+    OVO_REQUIRE(src_rows_local >= src_need, "the source shards do not hold n_src rows");
+    const int64_t rows_needed = shard_local_rows(n_fill, shard_rank, shard_count, bl);
+    OVO_REQUIRE(rows_out >= rows_needed, "the output shard does not hold this rank's rows of n_fill");
+    if (rows_needed == 0) return OVO_OK;
+    OVO_REQUIRE(acc_out && cnt_out && (total == 0 || (acc && cnt)), "null buffer");
+    OVO_REQUIRE(!cls == !conf && !cls_out == !conf_out && (!cls || cls_out) && (!cls_out || cls || total == 0),
+                "cls / conf and their outputs are given together or not at all");
+    OVO_REQUIRE((((uintptr_t)acc | (uintptr_t)acc_out) & 15) == 0, "acc and acc_out must be 16-byte aligned");
+    OVO_REQUIRE(K == 0 || (ws && ws_bytes >= ovo_dense_repack_workspace_bytes(K) && ((uintptr_t)ws & 7) == 0), "workspace missing, too small or not 8-byte aligned");
+    const size_t rs = (size_t)src_shards * (size_t)src_rows_local, ro = (size_t)rows_out;
+    const void *src[4] = {acc, cnt, cls, conf}, *dst[5] = {acc_out, cnt_out, cls_out, conf_out, K > 0 ? ws : nullptr};
+    const size_t src_bytes[4] = {4 * (size_t)D * rs, 4 * rs, 8 * rs, 4 * rs}, dst_bytes[5] = {4 * (size_t)D * ro, 4 * ro, 8 * ro, 4 * ro, ws_bytes};
+    const char *bad = overlap_error(src, src_bytes, 4, dst, dst_bytes, 5);
+    OVO_REQUIRE(!bad, bad);
+    const int64_t blocks = (rows_needed + 4 * DR_ROWS - 1) / (4 * DR_ROWS);
+    OVO_REQUIRE(blocks <= 0x7fffffffLL && (int64_t)DR_ROWS * (D / 4) <= 0x7fffffffLL, "shard too large for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    DenseRepack a;
+    a.acc = acc; a.cnt = cnt; a.cls = cls; a.conf = conf;
+    a.acc_o = acc_out; a.cnt_o = cnt_out; a.cls_o = cls_out; a.conf_o = conf_out;
+    a.seg_dst = (const int64_t *)ws; a.seg_src = a.seg_dst + K + 1;
+    a.total = total; a.n_fill = n_fill; a.rows_needed = rows_needed; a.src_rows_local = src_rows_local; a.empty_cls = empty_cls;
+    a.empty_conf = empty_conf;
+    a.K = K; a.C = D / 4; a.src_shards = src_shards; a.shard_rank = shard_rank; a.shard_count = shard_count; a.bl = bl;
+    if (K > 0) OVO_HIP(stage_segment_table(ws, seg_src_host, seg_dst_host, K, st));
+    k_dense_repack<<<(unsigned)blocks, 256, 0, st>>>(a);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }

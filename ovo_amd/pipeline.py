@@ -25,6 +25,10 @@ Several GPUs (one process each): a ROUND is `world` consec
     rows, in keyframe order -- the merged accumulator is the concatenation of the shards and equals the one-process accumulator bit
     for bit (a floating-point all-reduce of per-GPU partial sums would not); the dense query runs on the local rows only.
 tests/test_gpu_multirank.py runs two ranks on one GPU and asserts equality with the one-process run.
+
+Loop closure (`FramePipeline.close_loop`, the reference's default `close_loops: True`): the pipeline records which rows every keyframe appended
+(`kfs`, as `WrapperORBSLAM` does); after the tracker has corrected its keyframe poses ONE `ovo_map_reanchor` launch moves and re-packs the
+replicated point map and ONE `ovo_dense_repack` launch per rank moves the row-indexed dense state through the same segment table.
 """
 from __future__ import annotations
 
@@ -44,6 +48,7 @@ from .encoders.vit import SPECS as VIT_SPECS, HipViT
 from .entities.clip_generator import CLIPGenerator
 from .entities.ovo import OVO
 from .entities.round_chain import RoundLauncher
+from .slam.orbslam import dense_repack, reanchor_map
 from .slam.vanilla_mapper import VanillaMapper
 from .utils import clip_utils, geometry_utils as G
 from .utils.streams import side_stream
@@ -127,6 +132,12 @@ class FramePipeline:
                                     "ids": torch.arange(n_map, dtype=torch.int32)[:, None], "max_id": n_map,
                                     "color": torch.zeros((n_map, 3), dtype=torch.uint8)})
         self.slam._reserve(n_map + extra_capacity)
+        # loop closure (`close_loop`): rows [0, n_seed) belong to no keyframe; kfs[frame id] = the rows that keyframe appended (WrapperORBSLAM.kfs's shape)
+        self.n_seed = self.slam._n
+        self.kfs: Dict[int, Dict[str, object]] = {}
+        self._kf_rows_end = self.n_seed                            # the map's size after the last keyframe recorded in `kfs`
+        self._round_kf_seq: Dict[int, list] = {}                   # first frame index of a round -> [(frame id, sequence number of its map step or 0)]
+        self._reanchor_ws = None
         self.masks = ResidentMasks()
         clip_cfg = {"embed_type": "TextRegion", "model_card": vit_card, "k_top_views": k_top_views, "fusion": "avg_pooling", "seed": seed,
                     "share_identical_crops": bool(share_crops)}
@@ -189,6 +200,8 @@ class FramePipeline:
             self.incremental_query = self.D % 16 == 0 and not os.environ.get("OVO_DENSE_FULL_QUERY")
             if self.incremental_query:
                 _, self.dense_cls, self.dense_conf = clip_utils.similarity(self.acc, self.texts, cnt=self.cnt, want_sim=False, want_argmax=True)
+                # the state of a row without points: what `close_loop` gives the rows behind the re-packed map
+                self.empty_cls, self.empty_conf = int(self.dense_cls[0]), float(self.dense_conf[0])
                 self.touched = torch.empty(self.rows_local, dtype=torch.int32, device=self.device)
                 self.n_touched = torch.zeros(2, dtype=torch.int32, device=self.device)     # two counters, used alternately
                 self._touch_parity = 0
@@ -234,6 +247,7 @@ class FramePipeline:
             for p in self._chains.pop(first):
                 self.ovo.detect_and_track_finish(p)
             self._round_seq.pop(first, None)
+            self._record_keyframes(first)
         self.slam.settle()
 
     def _gather(self, t: torch.Tensor) -> torch.Tensor:
@@ -371,12 +385,15 @@ class FramePipeline:
             # and a pre-queued NEXT round may already have moved the mapper's own count past it)
             seq = self._round_seq.pop(group[0].index, 0)
             n = self.slam.size_after(seq) if seq else self.ovo.last_n_points
+            self._record_keyframes(group[0].index, seq, n)
         else:
             for f in group:
                 fd = [f.index, f.rgb_lr, f.depth, f.c2w]
                 self.slam.track_camera(fd)
                 c2w = self.slam._c2w_host[f.index]
                 self.slam.map(fd, c2w)
+                self.kfs[f.index] = {"id": f.index, "pcd_idxs": (self._kf_rows_end, self.slam._n)}      # (`map` has settled: the size is the host's own)
+                self._kf_rows_end = self.slam._n
                 updated = self.ovo.detect_and_track_objects([f.index, f.rgb, f.depth, ratio], self.slam.get_map(), c2w)
                 if updated is not None:
                     self.slam.update_pcd_obj_ids(updated)
@@ -470,6 +487,7 @@ class FramePipeline:
         # tail(r - 1) -> chains(r + 1) -> tail(r + 1) ..., 4.5 ms per round).  The other direction is an event: chain k -> tail k.
         with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
             round_seq = 0                                          # sequence number of the round's LAST map step (0: none was built)
+            kf_seq = self._round_kf_seq[group[0].index] = []
             for f in group:
                 fd = [f.index, f.rgb_lr, f.depth, f.c2w]
                 self.slam.track_camera(fd)
@@ -479,6 +497,7 @@ class FramePipeline:
                 m = self.slam.map_launch(fd, c2w, defer=True)
                 if m is not None:
                     round_seq = self.slam.last_seq
+                kf_seq.append((f.index, self.slam.last_seq if m is not None else 0))
                 p = self.ovo.detect_and_track_launch([f.index, f.rgb, f.depth, ratio], self.slam, c2w, defer=True)
                 pend.append(p)
                 if m is not None or p is not None:
@@ -545,6 +564,89 @@ class FramePipeline:
         # run, where eight processes' kernels interleave (wrong descriptors for the last round's instances in 2 of 3 runs; never seen at world 2).
         if self.chain_stream is not None:
             self.chain_stream.wait_stream(torch.cuda.current_stream())
+
+    # ------------------------------------------------------------------ loop closure
+    def _record_keyframes(self, first: int, last_seq: int = 0, last_n: int = 0) -> None:
+        """`kfs` entries of a finished round: the rows each of its keyframes appended, from the map steps' result blocks -- pinned host memory
+        the round's tracking results were already waited behind (no launch, no sync, no device read).  `last_seq`, `last_n`: the block the caller
+        has read already (the round's last map step and the size after it)."""
+        for frame_id, seq in self._round_kf_seq.pop(first, ()):
+            # no valid depth: no map step, no rows
+            end = self._kf_rows_end if not seq else last_n if seq == last_seq else self.slam.size_after(seq)
+            self.kfs[frame_id] = {"id": frame_id, "pcd_idxs": (self._kf_rows_end, end)}
+            self._kf_rows_end = end
+
+    def close_loop(self, updated_keyframes, world_ref=None, semantic_update=True, same_instance=None) -> Dict[str, object]:
+        """After a loop closure / global bundle adjustment of the tracker (`WrapperORBSLAM.update_map` for the round pipeline).
+        `updated_keyframes`: what `tracker.get_keyframe_points()` reports -- rows of 13 numbers (keyframe id, top three rows of the corrected
+        pose), in the tracker's order; ids the pipeline does not know are skipped, pipeline keyframes that are not listed are pruned with their
+        rows, the seed rows (`n_map`) stay in front.  `world_ref` (default: identity) multiplies the tracker's poses from the left.
+          1. the point map is re-anchored and re-packed in the tracker's order (`reanchor_map`: one `ovo_map_reanchor` launch, replicated on every
+             rank; a keyframe whose pose did not change keeps its points bit for bit);
+          2. the dense state -- acc / cnt and the resident dense_cls / dense_conf -- moves through the same segment table into fresh buffers (one
+             `ovo_dense_repack` launch); rows behind the map get the state of a point nothing was accumulated into;
+          3. `semantic_update`: the instances follow, as in `OVOSemMap.run` (`OVO.update_map` with `same_instance`, `update_pcd_obj_ids`);
+             off: map and dense state only (tests, diagnosis);
+          4. everything that still names old rows or old buffers is reset.
+        Several ranks: EVERY rank calls this with the same list between two rounds.  The shards of the four dense arrays (the rows that hold
+        points) are all-gathered and each rank re-packs its own shard straight from the shard-major result: a MAP-SIZED collective (GBs at the
+        bench's shape), as `gather_dense` is -- rare, and outside the keyframe loop; exchanging only the rows that change owner is not done.
+        Not with a round pre-queued (`step_round(..., upcoming=...)`: its chains hold the old rows and buffers; step it or `drain()` first) and not
+        under `emulate`.  Returns {"n_points", "n_dropped", "n_keyframes", "n_pruned_keyframes"}."""
+        if self._chains:
+            raise L.OvoHipError("close_loop: a round is pre-queued -- step it (or drain()) before the map is re-anchored")
+        if self.emulate:
+            raise L.OvoHipError("close_loop: not under emulate= (a timing stand-in holds no real shards)")
+        self.join()
+        self.slam.settle()
+        n_old, old_kfs = self.slam._n, self.kfs
+        world_ref = torch.eye(4) if world_ref is None else torch.as_tensor(world_ref).detach().cpu().float()
+        nb = int(L.load().ovo_map_reanchor_workspace_bytes(1 + sum(int(r[0]) in old_kfs for r in updated_keyframes)))
+        if self._reanchor_ws is None or self._reanchor_ws.numel() < nb:
+            self._reanchor_ws = torch.empty(max(nb, 1 << 12), dtype=torch.uint8, device=self.device)
+        kept, seg_src, seg_dst, self.kfs = reanchor_map(self.slam, old_kfs, updated_keyframes, world_ref, head_rows=self.n_seed,
+                                                        exact_identity=True, ws=self._reanchor_ws)
+        n_new = self._kf_rows_end = int(seg_dst[-1])
+        if self.dense:
+            B, R = self.SHARD_BLOCK, self.world
+            blocks = -(-self.slam._cap // B)                        # (the capacity grows only when the tracker lists a keyframe twice)
+            rows_local = max(self.rows_local, -(-blocks // R) * B if R > 1 else self.slam._cap)
+            inc = self.incremental_query
+            src = [self.acc, self.cnt, self.dense_cls if inc else None, self.dense_conf if inc else None]
+            if R > 1:                                              # shard-major, only the rows that hold points -- as gather_dense; no merge copy
+                rows = -(-(-(-n_old // B)) // R) * B                 # gather_dense's `per * B`: the blocks that hold points, dealt to R ranks
+                src = [None if t is None else self._gather(t[:rows].contiguous()) for t in src]
+            dev = self.device
+            out = [torch.empty((rows_local, self.D), dtype=torch.float32, device=dev), torch.empty(rows_local, dtype=torch.int32, device=dev),
+                   torch.empty(rows_local, dtype=torch.int64, device=dev) if inc else None,
+                   torch.empty(rows_local, dtype=torch.float32, device=dev) if inc else None]
+            dense_repack(src, out, n_old, seg_src, seg_dst, n_fill=rows_local * R, empty_cls=self.empty_cls if inc else -1,
+                         empty_conf=self.empty_conf if inc else 0.0, src_shards=R, shard=(self.rank, R, B), ws=self._reanchor_ws)
+            torch.cuda.current_stream().synchronize()              # the old buffers are released below
+            del src
+            self.acc, self.cnt, self.rows_local = out[0], out[1], rows_local
+            if inc:
+                self.dense_cls, self.dense_conf = out[2], out[3]
+                if self.touched.numel() < rows_local:
+                    self.touched = torch.empty(rows_local, dtype=torch.int32, device=dev)
+                self.n_touched.zero_()                             # the lists name old rows
+                self._touch_parity = 0
+        if semantic_update:                                        # OVOSemMap.run's sequence after slam.map reports an updated map
+            updated = self.ovo.update_map(self.slam.get_map(), self.kfs, same_instance=same_instance)
+            if updated is not None:
+                self.slam.update_pcd_obj_ids(updated)
+        # what still names old rows / old buffers: the last keyframe's point -> mask lists, the tracker's scratch, per-round sequence numbers, the
+        # views of the old class map handed out by the last step
+        self.ovo.last_point_seg = self.ovo.last_mask_rows = self.ovo.last_hits = None
+        self.ovo.last_n_points = n_new
+        self.ovo._track_ws = None
+        self._round_seq.clear()
+        self._round_kf_seq.clear()
+        for k in ("dense_cls", "dense_conf"):
+            self.last.pop(k, None)
+        n_pruned = sum(1 for k in old_kfs if k not in self.kfs)
+        return {"n_points": n_new, "n_dropped": sum(v["pcd_idxs"][1] - v["pcd_idxs"][0] for k, v in old_kfs.items() if k not in self.kfs),
+                "n_keyframes": len(self.kfs), "n_pruned_keyframes": n_pruned}
 
     # ------------------------------------------------------------------ dense shards
     def local_rows(self, n: int) -> int:

@@ -28,13 +28,17 @@ def convert_pose(traj) -> torch.Tensor:
     return torch.from_numpy(np.concatenate([top, np.asarray([[0, 0, 0, 1]], np.float32)]))
 
 
-def build_segment_table(kfs: Dict[int, Dict[str, Any]], updated_ids: Sequence[int]) -> Tuple[List[int], np.ndarray, np.ndarray]:
+def build_segment_table(kfs: Dict[int, Dict[str, Any]], updated_ids: Sequence[int], head_rows: int = 0) -> Tuple[List[int], np.ndarray, np.ndarray]:
     """The re-packing of orbslam.py:80-107 as a table: for the tracker's keyframes IN ITS ORDER, skipping the ones `kfs` does not know (:84-88),
-    (kept ids, seg_src i64[K], seg_dst i64[K + 1]) -- segment k copies rows kfs[id]["pcd_idxs"] to rows [seg_dst[k], seg_dst[k + 1])."""
+    (kept ids, seg_src i64[K], seg_dst i64[K + 1]) -- segment k copies rows kfs[id]["pcd_idxs"] to rows [seg_dst[k], seg_dst[k + 1]).
+    `head_rows` > 0: a leading segment [0, head_rows) that stays where it is (rows that belong to no keyframe: the map a pipeline was seeded with);
+    the keyframes' segments follow it, so the arrays are one entry longer than `kept`."""
     kept = [int(i) for i in updated_ids if int(i) in kfs]
-    src = np.asarray([kfs[i]["pcd_idxs"][0] for i in kept], dtype=np.int64).reshape(-1)
-    length = np.asarray([kfs[i]["pcd_idxs"][1] - kfs[i]["pcd_idxs"][0] for i in kept], dtype=np.int64).reshape(-1)
-    dst = np.zeros(len(kept) + 1, dtype=np.int64)
+    head = [(0, int(head_rows))] if head_rows > 0 else []
+    runs = head + [tuple(kfs[i]["pcd_idxs"]) for i in kept]
+    src = np.asarray([a for a, _ in runs], dtype=np.int64).reshape(-1)
+    length = np.asarray([b - a for a, b in runs], dtype=np.int64).reshape(-1)
+    dst = np.zeros(len(runs) + 1, dtype=np.int64)
     np.cumsum(length, out=dst[1:])
     return kept, src, dst
 
@@ -65,6 +69,88 @@ def map_reanchor(src, out, n_src: int, seg_src: np.ndarray, seg_dst: np.ndarray,
                                  L.ptr(out[3]), cap_out, seg_src.ctypes.data, seg_dst.ctypes.data, seg_T.ctypes.data, K, L.ptr(ws), ws.numel(),
                                  L.stream()))
     return int(seg_dst[K])
+
+
+def dense_repack(src, out, n_src: int, seg_src: np.ndarray, seg_dst: np.ndarray, n_fill: int, empty_cls: int = -1, empty_conf: float = 0.0,
+                 src_shards: int = 1, shard: Tuple[int, int, int] = (0, 1, 4096), ws: torch.Tensor = None) -> int:
+    """`ovo_dense_repack` on the current stream: everything a pipeline indexes by map row, moved through the segment table `map_reanchor` used.
+    src = (acc f32[src_shards * R, D] or [src_shards, R, D], cnt i32, cls i64 or None, conf f32 or None): the old state, shard-major as
+    `parallel.allgather` returns it (src_shards = 1: plain point order); out = the same four for THIS rank's shard (rank, count, block) = `shard`;
+    rows [seg_dst[K], n_fill) get the empty state.  Returns the rows written (seg_dst[K])."""
+    lib = L.load()
+    seg_src = np.ascontiguousarray(seg_src, dtype=np.int64)
+    seg_dst = np.ascontiguousarray(seg_dst, dtype=np.int64)
+    K = int(seg_src.shape[0])
+    if seg_dst.shape[0] != K + 1:
+        raise L.OvoHipError(f"dense_repack: {K} segments need seg_dst[{K + 1}]")
+    names = ("acc", "cnt", "cls", "conf")
+    dtypes = (torch.float32, torch.int32, torch.int64, torch.float32)
+    for group in (src, out):
+        for t, name, dt in zip(group, names, dtypes):
+            if t is not None:
+                L.dev(t, dt, name)
+    D = int(out[0].shape[-1])
+    if int(src[0].shape[-1]) != D:
+        raise L.OvoHipError("dense_repack: source and output rows differ in width")
+    if any(t is not None and t.numel() // (D if i == 0 else 1) % src_shards for i, t in enumerate(src)):
+        raise L.OvoHipError("dense_repack: the source arrays do not split into src_shards equal shards")
+    src_rows_local = min(int(t.numel()) // (D if i == 0 else 1) for i, t in enumerate(src) if t is not None) // src_shards
+    rows_out = min(int(t.shape[0]) for t in out if t is not None)
+    nb = int(lib.ovo_dense_repack_workspace_bytes(K))
+    if ws is None:
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=out[0].device)
+    L.check(lib.ovo_dense_repack(L.ptr(src[0]), L.ptr(src[1]), L.ptr(src[2]), L.ptr(src[3]), D, src_shards, src_rows_local, n_src,
+                                 L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), rows_out, int(shard[0]), int(shard[1]), int(shard[2]),
+                                 n_fill, int(empty_cls), float(empty_conf), seg_src.ctypes.data, seg_dst.ctypes.data, K, L.ptr(ws), ws.numel(),
+                                 L.stream()))
+    return int(seg_dst[K])
+
+
+def reanchor_map(m: VanillaMapper, kfs: Dict[int, Dict[str, Any]], updated_keyframes, world_ref: torch.Tensor, head_rows: int = 0,
+                 exact_identity: bool = False, ws: torch.Tensor = None):
+    """orbslam.py:68-115 with one launch for the whole map, on any `VanillaMapper` `m` whose keyframes appended the rows `kfs` names:
+    `updated_keyframes` = the tracker's keyframe rows (id, then the top three rows of the corrected pose) in ITS order.  Every surviving
+    keyframe's rows move by `updated_c2w @ inv(old_c2w)`, pruned keyframes' rows are dropped, the map is re-packed in the tracker's order into
+    fresh capacity buffers and `m`'s poses become the surviving keyframes' new ones.  `head_rows`: rows [0, head_rows) belong to no keyframe and
+    stay in front under the exact identity.  `exact_identity`: a keyframe whose updated pose is bit-equal to its stored pose gets the exact
+    identity instead of `P @ inv(P)` (which is the identity only up to the f32 composition error).
+    Returns (kept, seg_src, seg_dst, new_kfs): the table it used -- whatever else is indexed by map row is re-packed through the same one -- and
+    the surviving keyframes with their new row ranges; the caller stores `new_kfs`.  The stream is synchronised before the old buffers are released."""
+    if m._deferred:                                        # they hold the old buffers' addresses (the rule of _reserve), and `settle` would wait for them forever
+        raise L.OvoHipError("update_map: deferred map steps outstanding -- launch the round before the map is re-anchored")
+    m.settle()
+    updated_kfs = [r for r in updated_keyframes if int(r[0]) in kfs]      # unknown keyframes are skipped (:84-88)
+    kept, seg_src, seg_dst = build_segment_table(kfs, [int(r[0]) for r in updated_kfs], head_rows)
+    h = len(seg_src) - len(kept)                           # 1 with a head segment
+    identity = np.eye(4, dtype=np.float32)[:3].reshape(-1)
+    seg_T = np.zeros((len(seg_src), 12), dtype=np.float32)
+    seg_T[:h] = identity
+    poses = []
+    for k, (kf_id, updated_kf) in enumerate(zip(kept, updated_kfs)):
+        kf_c2w = m._host_pose(kf_id, m.estimated_c2ws[kf_id]).float()
+        updated_kf_c2w = world_ref @ convert_pose(np.asarray(updated_kf)[1:13])
+        if exact_identity and torch.equal(updated_kf_c2w, kf_c2w):
+            seg_T[h + k] = identity
+        else:
+            transform = updated_kf_c2w @ torch.linalg.inv(kf_c2w)      # the reference's own expression (:93), f32 on the CPU
+            seg_T[h + k] = transform[:3].reshape(-1).numpy()
+        poses.append(updated_kf_c2w)
+    total = int(seg_dst[-1])
+    dev, cap = m.device, max(m._cap, total)                # > _cap only when the tracker lists a keyframe twice
+    out = (torch.empty((cap, 3), dtype=torch.float32, device=dev), torch.empty((cap,), dtype=torch.int32, device=dev),
+           torch.empty((cap,), dtype=torch.int32, device=dev), torch.empty((cap, 3), dtype=torch.uint8, device=dev))
+    map_reanchor((m._xyz, m._ids, m._ins, m._rgb), out, m._n_known, seg_src, seg_dst, seg_T, ws)
+    torch.cuda.current_stream().synchronize()              # the old buffers are released below, and other streams may read the new ones next
+    m._xyz, m._ids, m._ins, m._rgb = out
+    m._cap = cap
+    m._n = total                                           # nothing in flight: map_ref() hands the host's size over and the device state is re-seeded from it
+    new_kfs, new_c2w = {}, {}
+    for k, kf_id in enumerate(kept):
+        new_kfs[kf_id] = {"id": kfs[kf_id]["id"], "pcd_idxs": (int(seg_dst[h + k]), int(seg_dst[h + k + 1]))}
+        new_c2w[kfs[kf_id]["id"]] = poses[k]
+    m.estimated_c2ws = new_c2w                             # only the surviving keyframes' poses (:109)
+    m._c2w_host = dict(new_c2w)
+    return kept, seg_src, seg_dst, new_kfs
 
 
 class ReplayTracker:
@@ -162,39 +248,12 @@ class WrapperORBSLAM(VanillaMapper):
             self.update_map()
 
     def update_map(self) -> None:
-        """orbslam.py:68-115 with one launch for the whole map."""
-        if self._deferred:                                 # they hold the old buffers' addresses (the rule of _reserve), and `settle` would wait for them forever
-            raise L.OvoHipError("update_map: deferred map steps outstanding -- launch the round before the map is re-anchored")
-        self.settle()
-        updated_kfs = [r for r in self.tracker.get_keyframe_points() if int(r[0]) in self.kfs]      # unknown keyframes are skipped (:84-88)
-        kept, seg_src, seg_dst = build_segment_table(self.kfs, [int(r[0]) for r in updated_kfs])
-        seg_T = np.zeros((len(kept), 12), dtype=np.float32)
-        poses = []
-        for k, (kf_id, updated_kf) in enumerate(zip(kept, updated_kfs)):
-            kf_c2w = self._host_pose(kf_id, self.estimated_c2ws[kf_id]).float()
-            updated_kf_c2w = self.world_ref @ convert_pose(np.asarray(updated_kf)[1:13])
-            transform = updated_kf_c2w @ torch.linalg.inv(kf_c2w)      # the reference's own expression (:93), f32 on the CPU
-            seg_T[k] = transform[:3].reshape(-1).numpy()
-            poses.append(updated_kf_c2w)
-        total = int(seg_dst[-1])
-        dev, cap = self.device, max(self._cap, total)      # > _cap only when the tracker lists a keyframe twice
-        out = (torch.empty((cap, 3), dtype=torch.float32, device=dev), torch.empty((cap,), dtype=torch.int32, device=dev),
-               torch.empty((cap,), dtype=torch.int32, device=dev), torch.empty((cap, 3), dtype=torch.uint8, device=dev))
-        nb = int(L.load().ovo_map_reanchor_workspace_bytes(len(kept)))
+        """orbslam.py:68-115 with one launch for the whole map (`reanchor_map`)."""
+        rows = self.tracker.get_keyframe_points()
+        nb = int(L.load().ovo_map_reanchor_workspace_bytes(sum(int(r[0]) in self.kfs for r in rows)))
         if self._reanchor_ws is None or self._reanchor_ws.numel() < nb:
-            self._reanchor_ws = torch.empty(max(nb, 1 << 12), dtype=torch.uint8, device=dev)
-        map_reanchor((self._xyz, self._ids, self._ins, self._rgb), out, self._n_known, seg_src, seg_dst, seg_T, self._reanchor_ws)
-        torch.cuda.current_stream().synchronize()          # the old buffers are released below, and other streams may read the new ones next
-        self._xyz, self._ids, self._ins, self._rgb = out
-        self._cap = cap
-        self._n = total                                    # nothing in flight: map_ref() hands the host's size over and the device state is re-seeded from it
-        new_kfs, new_c2w = {}, {}
-        for k, kf_id in enumerate(kept):
-            new_kfs[kf_id] = {"id": self.kfs[kf_id]["id"], "pcd_idxs": (int(seg_dst[k]), int(seg_dst[k + 1]))}
-            new_c2w[self.kfs[kf_id]["id"]] = poses[k]
-        self.kfs = new_kfs
-        self.estimated_c2ws = new_c2w                      # only the surviving keyframes' poses (:109)
-        self._c2w_host = dict(new_c2w)
+            self._reanchor_ws = torch.empty(max(nb, 1 << 12), dtype=torch.uint8, device=self.device)
+        *_, self.kfs = reanchor_map(self, self.kfs, rows, self.world_ref, head_rows=0, exact_identity=False, ws=self._reanchor_ws)
         self.map_updated = True
 
     def __del__(self) -> None:
