@@ -46,11 +46,12 @@ from . import parallel, synthetic as syn
 from .encoders.hiera import SPECS as HIERA_SPECS, HipHiera
 from .encoders.vit import SPECS as VIT_SPECS, HipViT
 from .entities.clip_generator import CLIPGenerator
+from .entities.dense_map import DenseMap
 from .entities.ovo import OVO
 from .entities.round_chain import RoundLauncher
-from .slam.orbslam import dense_repack, reanchor_map
+from .slam.orbslam import reanchor_map
 from .slam.vanilla_mapper import VanillaMapper
-from .utils import clip_utils, geometry_utils as G
+from .utils import clip_utils, geometry_utils as G, segment_utils
 from .utils.streams import side_stream
 
 
@@ -90,11 +91,18 @@ def synthetic_frames(n: int, device, scale: float = 1.0, n_masks_grid=(4, 6), n_
         rgb = syn.render_rgb(H, W, seed + t)
         depth = syn.render_depth(c2w, K, h, w, seed + t)
         masks = syn.make_masks(H, W, grid=n_masks_grid, n_blobs=n_blobs, seed=seed + t)
-        from .utils import geometry_utils as G
         out.append(Frame(t, torch.from_numpy(rgb).to(device), torch.from_numpy(np.ascontiguousarray(rgb[e:H - e, e:W - e])).to(device),
                          G.tag_depth_range(torch.from_numpy(depth).to(device), depth), c2w, torch.from_numpy(syn.masks_to_segmap(masks)).to(device),
                          torch.from_numpy(masks).to(device)))
     return out
+
+
+@dataclass
+class QueuedRound:
+    """A round whose map updates and tracking chains are on the device and whose results nobody has read yet."""
+    pend: list                 # what `OVO.detect_and_track_launch` returned per keyframe (None: nothing to track)
+    last_seq: int              # sequence number of the round's LAST map step (0: none was built)
+    kf_seq: list               # [(frame id, sequence number of its map step or 0)]
 
 
 def _hwc(rgb: torch.Tensor) -> torch.Tensor:
@@ -136,7 +144,6 @@ class FramePipeline:
         self.n_seed = self.slam._n
         self.kfs: Dict[int, Dict[str, object]] = {}
         self._kf_rows_end = self.n_seed                            # the map's size after the last keyframe recorded in `kfs`
-        self._round_kf_seq: Dict[int, list] = {}                   # first frame index of a round -> [(frame id, sequence number of its map step or 0)]
         self._reanchor_ws = None
         self.masks = ResidentMasks()
         clip_cfg = {"embed_type": "TextRegion", "model_card": vit_card, "k_top_views": k_top_views, "fusion": "avg_pooling", "seed": seed,
@@ -187,35 +194,15 @@ class FramePipeline:
         self.exchange_ms = 0.0                                     # host wall time spent in the rounds' collectives (bench.py reports it)
         self.exchanges = 0
         self.exchange_events: list = []                            # (start, end) hipEvents around every round's all-gather
-        if dense:
-            cap = self.slam._cap
-            blocks = -(-cap // self.SHARD_BLOCK)
-            self.rows_local = -(-blocks // self.world) * self.SHARD_BLOCK if self.world > 1 else cap    # rows of THIS rank's shard
-            self.acc = torch.zeros((self.rows_local, self.D), dtype=torch.float32, device=self.device)
-            self.cnt = torch.zeros(self.rows_local, dtype=torch.int32, device=self.device)
-            # The dense class / confidence map stays RESIDENT: a keyframe changes the accumulators of the points it matched (10-20 % of
-            # the map) and only those rows can change class, so the scatter pass emits their indices and the query re-evaluates just
-            # them (`ovo_similarity_rows`) -- bit-identical to re-querying all rows (tests/test_gpu_pipeline.py), a fraction of the 5 GB
-            # stream.  Initial state = the query of the empty accumulators, computed once here over the whole capacity.
-            self.incremental_query = self.D % 16 == 0 and not os.environ.get("OVO_DENSE_FULL_QUERY")
-            if self.incremental_query:
-                _, self.dense_cls, self.dense_conf = clip_utils.similarity(self.acc, self.texts, cnt=self.cnt, want_sim=False, want_argmax=True)
-                # the state of a row without points: what `close_loop` gives the rows behind the re-packed map
-                self.empty_cls, self.empty_conf = int(self.dense_cls[0]), float(self.dense_conf[0])
-                self.touched = torch.empty(self.rows_local, dtype=torch.int32, device=self.device)
-                self.n_touched = torch.zeros(2, dtype=torch.int32, device=self.device)     # two counters, used alternately
-                self._touch_parity = 0
-                # round 6: the tracking chain lists the points its masks cover and ONE launch accumulates and re-queries them (`ovo_scatter_accum_query`);
-                # the scan + apply + query launches above remain for keyframes tracked on the host path and for OVO_NO_FUSED_SCATTER=1
-                if not os.environ.get("OVO_NO_FUSED_SCATTER") and n_text <= 16 and n_text * self.D * 4 <= 96 * 1024:
-                    self.ovo.hit_shard = (self.rank, self.world, self.SHARD_BLOCK)
+        self.dense_map = DenseMap(self.slam._cap, self.D, self.texts, (self.rank, self.world, self.SHARD_BLOCK), self.device, self._gather) if dense else None
+        if dense and self.dense_map.fused:                         # the tracking chain lists the points of this rank's shard for the one-launch form
+            self.ovo.hit_shard = (self.rank, self.world, self.SHARD_BLOCK)
         self.last: Dict[str, object] = {}
         # Masks from this rank's OWN generator (SAM2 end to end, or an injected `mask_source(frame) -> (seg_map, masks)`): the owner of a
         # keyframe produces them, `parallel.share_masks` carries them bit-packed to the replicas, which track with exactly those bits.
         self.mask_source = None
         self.mask_exchanges = 0
-        self._chains: Dict[int, list] = {}                         # first frame index of a round -> its queued chains (software pipelining)
-        self._round_seq: Dict[int, int] = {}                       # first frame index of a round -> sequence number of its last map step
+        self._queued: Dict[int, QueuedRound] = {}                  # first frame index of a round -> the round, pre-queued (software pipelining)
         # result rings for two rounds in flight (this one being read, the next one pre-queued) plus margin: a full ring would make the
         # launchers wait for result blocks of steps that are built but not launched yet
         self.slam.ring_slots(max(64, 4 * self.world + 8))
@@ -243,11 +230,11 @@ class FramePipeline:
         """End of stream: a round that was pre-queued (software pipelining, `step_round(..., upcoming=...)`) but never stepped has already
         advanced the map and the per-point instance ids on the device.  Read its result blocks and do the host bookkeeping -- the instances
         and keyframe queue then match the map again; its keyframes get no descriptors (call `OVO.complete_semantic_info()` for those)."""
-        for first in sorted(self._chains):
-            for p in self._chains.pop(first):
+        for first in sorted(self._queued):
+            q = self._queued.pop(first)
+            for p in q.pend:
                 self.ovo.detect_and_track_finish(p)
-            self._round_seq.pop(first, None)
-            self._record_keyframes(first)
+            self._record_keyframes(q)
         self.slam.settle()
 
     def _gather(self, t: torch.Tensor) -> torch.Tensor:
@@ -271,10 +258,14 @@ class FramePipeline:
                 self.ovo.lookahead.reset()
         self._sam_by_frame.clear(); self._encoded.clear(); self._group_first.clear()
 
+    def _sam_side(self):
+        """The stream the batched SAM2 work runs on (`serial`: the caller's)."""
+        return torch.cuda.current_stream() if self.serial else (self.sam_stream or torch.cuda.current_stream())
+
     def _launch_encoders(self, group: List[Frame]) -> None:
         """SAM2 image encoder and ViT forward of a group of keyframes, each as one batched forward on its side stream."""
         if self.sam is not None:
-            side = torch.cuda.current_stream() if self.serial else (self.sam_stream or torch.cuda.current_stream())
+            side = self._sam_side()
             for g in group:
                 if g.ready is not None:                            # the frame's upload, if it is still in flight
                     side.wait_event(g.ready)
@@ -314,7 +305,7 @@ class FramePipeline:
             hit = self._sam_by_frame.get(f.index)
             outs, k = hit
             emb = {"image_embed": outs[2][k:k + 1], "high_res_feats": (outs[0][k:k + 1], outs[1][k:k + 1])}
-            side = torch.cuda.current_stream() if self.serial else (self.sam_stream or torch.cuda.current_stream())
+            side = self._sam_side()
             with torch.cuda.stream(side):
                 return self.amg.generate_launch(f.rgb, embeddings=emb)
         amg_pending = None
@@ -347,7 +338,6 @@ class FramePipeline:
     def step_round(self, group: List[Frame], upcoming: Optional[List[Frame]] = None) -> Dict[str, object]:
         """`world` consecutive keyframes, keyframe k owned by rank k (one process: a round is one keyframe).  `upcoming`: the frames
         after the round, in order (their owners follow the same k = position % world rule)."""
-        lib = L.load()
         if len(group) != self.world:
             raise L.OvoHipError(f"a round is {self.world} keyframes, got {len(group)}")
         upcoming = list(upcoming or [])
@@ -360,110 +350,20 @@ class FramePipeline:
         if self.mask_source is not None or (self.amg is not None and (self.world > 1 or self.own_masks)):
             self._exchange_masks(group, amg_pending)
             amg_pending = None
-        # ---- the order-dependent passes, for every keyframe of the round, on every rank (replicated map and tracker).  The whole
-        # round is QUEUED first -- map update and tracking chain of every keyframe, sizes and instance ids device-resident
-        # (`ovo_map_step` / `ovo_track_step`) -- then finished in order: the host bookkeeping of keyframe k runs while the device
-        # works on k + 1 ..., and nothing on the device ever waits for the host.
-        plans, segs = [], []
+        # ---- the order-dependent passes, for every keyframe of the round, on every rank (replicated map and tracker)
         ratio = (1.0, 1.0, self.crop_edge) if self.crop_edge else ()
         native = not self.ovo.config.get("log", False) and all(self.ovo._native_ok(self.masks.frames[f.index].masks) for f in group)
-        if native:
-            pend = self._chains.pop(group[0].index, None) or self._launch_chains(group, ratio)
-            # software pipelining of rounds: the NEXT round's chains are queued now, before this round's results are read -- while the
-            # host does this round's bookkeeping, pooling, exchange and fusion the device already works on the next round's tracking,
-            # and vice versa (queue -> wait -> bookkeeping in one round leaves host and device waiting for each other in turn)
-            nxt = upcoming[:self.world]
-            if self.pipeline_rounds and len(nxt) == self.world and self.mask_source is None and self.amg is None \
-                    and all(self.ovo._native_ok(f.masks) for f in nxt):
-                self.masks.frames.update({f.index: f for f in nxt})
-                self._chains[nxt[0].index] = self._launch_chains(nxt, ratio)
-            for k, p in enumerate(pend):                           # (assignment happened in place in the mapper's buffer; only the owner of a
-                self.ovo.detect_and_track_finish(p, want_maps=(k == self.rank))     # keyframe reads its kept binary maps: `_extract_clip` below)
-                plans.append(self.ovo._plan_semantic_info() if len(self.ovo.keyframes_queue) > 0 else None)
-                segs.append((self.ovo.last_point_seg, self.ovo.last_mask_rows, self.ovo.last_hits))
-            # the map's size after this round: from the round's last map step (a keyframe without masks reports none through the tracker,
-            # and a pre-queued NEXT round may already have moved the mapper's own count past it)
-            seq = self._round_seq.pop(group[0].index, 0)
-            n = self.slam.size_after(seq) if seq else self.ovo.last_n_points
-            self._record_keyframes(group[0].index, seq, n)
-        else:
-            for f in group:
-                fd = [f.index, f.rgb_lr, f.depth, f.c2w]
-                self.slam.track_camera(fd)
-                c2w = self.slam._c2w_host[f.index]
-                self.slam.map(fd, c2w)
-                self.kfs[f.index] = {"id": f.index, "pcd_idxs": (self._kf_rows_end, self.slam._n)}      # (`map` has settled: the size is the host's own)
-                self._kf_rows_end = self.slam._n
-                updated = self.ovo.detect_and_track_objects([f.index, f.rgb, f.depth, ratio], self.slam.get_map(), c2w)
-                if updated is not None:
-                    self.slam.update_pcd_obj_ids(updated)
-                plans.append(self.ovo._plan_semantic_info() if len(self.ovo.keyframes_queue) > 0 else None)
-                segs.append((self.ovo.last_point_seg, self.ovo.last_mask_rows, self.ovo.last_hits))
-            n = self.slam._n
+        plans, segs, n = self._track_round_queued(group, upcoming, ratio) if native else self._track_round_host(group, ratio)
         # ---- descriptors of the keyframe this rank owns, then the round's one exchange
         plan = plans[self.rank]
         desc_mine = self.ovo._extract_clip(plan["image"], plan["binary_maps"]) if plan is not None else None
-        if self.world > 1:
-            for p in plans:                                        # the plans are replicated: every rank sees an overflow, none is left in the collective
-                if p is not None and len(p["matched_ins_ids"]) > self.MAX_DESC:
-                    raise L.OvoHipError(f"{len(p['matched_ins_ids'])} descriptors in one keyframe: raise FramePipeline.MAX_DESC")
-            t0 = time.perf_counter()
-            if desc_mine is not None:
-                self.xchg[:desc_mine.shape[0]].copy_(desc_mine)
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if len(self.exchange_events) < 4096 else None
-            if ev:
-                ev[0].record()
-            gathered = self._gather(self.xchg)                     # [world, MAX_DESC, D]: every owner's descriptors, rank-major = keyframe order
-            if ev:                                                 # device time of the collective itself (hipEvents on the stream it runs on)
-                ev[1].record()
-                self.exchange_events.append(ev)
-            descs = [gathered[k, :len(p["matched_ins_ids"])] if p is not None else None for k, p in enumerate(plans)]
-            self.exchange_ms += 1e3 * (time.perf_counter() - t0)
-            self.exchanges += 1
-        else:
-            descs = [desc_mine]
+        descs = self._exchange_descriptors(plans, desc_mine) if self.world > 1 else [desc_mine]
         # ---- every rank: store + re-fuse in keyframe order (identical instance tables), dense accumulate on its own rows
         # (the instance table is read after the round only: the round's running-sum fusions are one launch, the mask-row lists one upload)
         self.ovo._apply_semantic_plans([(p, d) for p, d in zip(plans, descs) if p is not None])
-        live = [k for k, (p, d) in enumerate(zip(plans, descs)) if p is not None and self.dense and d.shape[0] > 0]
-        all_rows = torch.tensor([r for k in live for r in segs[k][1]], dtype=torch.int32).to(self.device, non_blocking=True) if live else None
-        row_off = 0
-        for k, (p, d, (point_seg, mask_rows, hits)) in enumerate(zip(plans, descs, segs)):
-            if p is None:
-                continue
-            if self.dense and d.shape[0] > 0:
-                rows = all_rows[row_off:row_off + len(mask_rows)]
-                row_off += len(mask_rows)
-                if hits is not None and self.incremental_query:    # one launch: accumulate the listed rows and re-evaluate exactly them
-                    n_list = hits.numel() - 4
-                    L.check(lib.ovo_scatter_accum_query(L.ptr(hits), hits[n_list:].data_ptr(), min(point_seg.shape[0], self.rows_local), L.ptr(point_seg),
-                                                        L.ptr(rows), rows.shape[0], L.ptr(d), self.D, L.ptr(self.acc), L.ptr(self.cnt), self.rank, self.world,
-                                                        self.SHARD_BLOCK, L.ptr(self.texts), self.texts.shape[0], 0, 0.0, 0.0, 0.0,
-                                                        L.ptr(self.dense_cls), L.ptr(self.dense_conf), L.stream()))
-                    continue
-                touched, n_cur, n_nxt = None, None, None
-                if self.incremental_query:
-                    k = self._touch_parity
-                    self._touch_parity ^= 1
-                    touched, n_cur, n_nxt = L.ptr(self.touched), self.n_touched[k:].data_ptr(), self.n_touched[k ^ 1:].data_ptr()
-                L.check(lib.ovo_scatter_accum_touched(L.ptr(point_seg), point_seg.shape[0], L.ptr(rows), rows.shape[0], L.ptr(d), self.D,
-                                                      L.ptr(self.acc), L.ptr(self.cnt), touched, n_cur, n_nxt, self.rank, self.world,
-                                                      self.SHARD_BLOCK, L.stream()))
-                if self.incremental_query:                         # only the rows this keyframe changed can change class
-                    L.check(lib.ovo_similarity_rows(L.ptr(self.acc), 0, touched, n_cur, min(point_seg.shape[0], self.rows_local), self.D,
-                                                    L.ptr(self.texts), self.texts.shape[0], L.ptr(self.cnt), 0, 0.0, 0.0, 0.0,
-                                                    L.ptr(self.dense_cls), L.ptr(self.dense_conf), L.stream()))
-        out: Dict[str, object] = {"n_points": n, "n_instances": len(self.ovo.objects)}
-        if len(self.ovo.objects) > 0:                              # query: instances x texts, fused argmax
-            table = self.ovo.get_objs_clips()
-            out["sim"], out["cls"], out["conf"] = clip_utils.similarity(table, self.texts, want_argmax=True)
         if self.dense:
-            nl = self.local_rows(n)
-            if self.incremental_query:                             # the resident map, patched above for the rows the round changed
-                out["dense_cls"], out["dense_conf"] = self.dense_cls[:nl], self.dense_conf[:nl]
-            else:                                                  # dense query: per-point mean descriptor x texts, every (local) row
-                _, out["dense_cls"], out["dense_conf"] = clip_utils.similarity(self.acc[:nl], self.texts, cnt=self.cnt[:nl], want_sim=False,
-                                                                               want_argmax=True)
+            self._accumulate_dense(plans, descs, segs)
+        out = self._query(n)
         if amg_pending is not None:                                # host filter + NMS + binarise: by now the statistics are long there
             self.sam_out = self.amg.generate_finish(amg_pending)
         if self.join_each_step:                                    # strict frame boundaries (tests); the stream of frames is
@@ -471,8 +371,93 @@ class FramePipeline:
         self.last = out
         return out
 
+    def _tracked(self, plans: list, segs: list) -> None:
+        """One keyframe's tracking is finished: its plan (None: nothing queued for descriptors) and its point -> mask lists."""
+        plans.append(self.ovo._plan_semantic_info() if len(self.ovo.keyframes_queue) > 0 else None)
+        segs.append((self.ovo.last_point_seg, self.ovo.last_mask_rows, self.ovo.last_hits))
+
+    def _track_round_queued(self, group: List[Frame], upcoming: List[Frame], ratio):
+        """Device decisions.  The whole round is QUEUED first -- map update and tracking chain of every keyframe, sizes and instance ids
+        device-resident (`ovo_map_step` / `ovo_track_step`) -- then finished in order: the host bookkeeping of keyframe k runs while the
+        device works on k + 1 ..., and nothing on the device ever waits for the host.  Returns (plans, segs, the map's size after the round)."""
+        plans, segs = [], []
+        q = self._queued.pop(group[0].index, None) or self._launch_chains(group, ratio)
+        # software pipelining of rounds: the NEXT round's chains are queued now, before this round's results are read -- while the
+        # host does this round's bookkeeping, pooling, exchange and fusion the device already works on the next round's tracking,
+        # and vice versa (queue -> wait -> bookkeeping in one round leaves host and device waiting for each other in turn)
+        nxt = upcoming[:self.world]
+        if self.pipeline_rounds and len(nxt) == self.world and self.mask_source is None and self.amg is None \
+                and all(self.ovo._native_ok(f.masks) for f in nxt):
+            self.masks.frames.update({f.index: f for f in nxt})
+            self._queued[nxt[0].index] = self._launch_chains(nxt, ratio)
+        for k, p in enumerate(q.pend):                             # (assignment happened in place in the mapper's buffer; only the owner of a
+            self.ovo.detect_and_track_finish(p, want_maps=(k == self.rank))     # keyframe reads its kept binary maps: `_extract_clip`)
+            self._tracked(plans, segs)
+        # the map's size after this round: from the round's last map step (a keyframe without masks reports none through the tracker,
+        # and a pre-queued NEXT round may already have moved the mapper's own count past it)
+        n = self.slam.size_after(q.last_seq) if q.last_seq else self.ovo.last_n_points
+        self._record_keyframes(q, n)
+        return plans, segs, n
+
+    def _track_round_host(self, group: List[Frame], ratio):
+        """Host decisions (a keyframe `OVO._native_ok` turns down, or `log`): map, track and plan one keyframe at a time, each with its syncs."""
+        plans, segs = [], []
+        for f in group:
+            fd = [f.index, f.rgb_lr, f.depth, f.c2w]
+            self.slam.track_camera(fd)
+            c2w = self.slam._c2w_host[f.index]
+            self.slam.map(fd, c2w)
+            self.kfs[f.index] = {"id": f.index, "pcd_idxs": (self._kf_rows_end, self.slam._n)}      # (`map` has settled: the size is the host's own)
+            self._kf_rows_end = self.slam._n
+            updated = self.ovo.detect_and_track_objects([f.index, f.rgb, f.depth, ratio], self.slam.get_map(), c2w)
+            if updated is not None:
+                self.slam.update_pcd_obj_ids(updated)
+            self._tracked(plans, segs)
+        return plans, segs, self.slam._n
+
+    def _exchange_descriptors(self, plans: list, desc_mine) -> list:
+        """The round's one exchange: every owner's descriptors to every rank.  Returns them per keyframe (None: no plan)."""
+        for p in plans:                                            # the plans are replicated: every rank sees an overflow, none is left in the collective
+            if p is not None and len(p["matched_ins_ids"]) > self.MAX_DESC:
+                raise L.OvoHipError(f"{len(p['matched_ins_ids'])} descriptors in one keyframe: raise FramePipeline.MAX_DESC")
+        t0 = time.perf_counter()
+        if desc_mine is not None:
+            self.xchg[:desc_mine.shape[0]].copy_(desc_mine)
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if len(self.exchange_events) < 4096 else None
+        if ev:
+            ev[0].record()
+        gathered = self._gather(self.xchg)                         # [world, MAX_DESC, D]: every owner's descriptors, rank-major = keyframe order
+        if ev:                                                     # device time of the collective itself (hipEvents on the stream it runs on)
+            ev[1].record()
+            self.exchange_events.append(ev)
+        descs = [gathered[k, :len(p["matched_ins_ids"])] if p is not None else None for k, p in enumerate(plans)]
+        self.exchange_ms += 1e3 * (time.perf_counter() - t0)
+        self.exchanges += 1
+        return descs
+
+    def _accumulate_dense(self, plans: list, descs: list, segs: list) -> None:
+        """Every keyframe's descriptors into this rank's rows of the dense map, in keyframe order; the round's mask-row lists are one upload."""
+        live = [k for k, (p, d) in enumerate(zip(plans, descs)) if p is not None and d.shape[0] > 0]
+        if not live:
+            return
+        all_rows = torch.tensor([r for k in live for r in segs[k][1]], dtype=torch.int32).to(self.device, non_blocking=True)
+        row_off = 0
+        for k in live:
+            point_seg, mask_rows, hits = segs[k]
+            self.dense_map.apply(point_seg, all_rows[row_off:row_off + len(mask_rows)], descs[k], hits)
+            row_off += len(mask_rows)
+
+    def _query(self, n: int) -> Dict[str, object]:
+        out: Dict[str, object] = {"n_points": n, "n_instances": len(self.ovo.objects)}
+        if len(self.ovo.objects) > 0:                              # query: instances x texts, fused argmax
+            table = self.ovo.get_objs_clips()
+            out["sim"], out["cls"], out["conf"] = clip_utils.similarity(table, self.texts, want_argmax=True)
+        if self.dense:
+            out["dense_cls"], out["dense_conf"] = self.dense_map.result(n)
+        return out
+
     # ------------------------------------------------------------------ owner -> replica masks
-    def _launch_chains(self, group: List[Frame], ratio) -> list:
+    def _launch_chains(self, group: List[Frame], ratio) -> QueuedRound:
         """Queue map update + tracking chain of every keyframe of a round -- no host round trip -- as ONE launch (`ovo_round_chain`:
         persistent workgroups walking through all passes of all keyframes); a round that call does not cover goes keyframe by
         keyframe (`ovo_map_step` / `ovo_track_step`)."""
@@ -487,7 +472,7 @@ class FramePipeline:
         # tail(r - 1) -> chains(r + 1) -> tail(r + 1) ..., 4.5 ms per round).  The other direction is an event: chain k -> tail k.
         with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
             round_seq = 0                                          # sequence number of the round's LAST map step (0: none was built)
-            kf_seq = self._round_kf_seq[group[0].index] = []
+            kf_seq = []
             for f in group:
                 fd = [f.index, f.rgb_lr, f.depth, f.c2w]
                 self.slam.track_camera(fd)
@@ -505,7 +490,6 @@ class FramePipeline:
                     tracks.append(p["step"] if p is not None else L.TrackStep())
             # the map's size after the round = result block of its last map step; a round in which no keyframe had valid depth built none
             # (the mapper's last_seq then names an OLDER round's slot, possibly reused): the consumer falls back to the tracker's count
-            self._round_seq[group[0].index] = round_seq
             if maps:
                 self.round_launcher.launch(maps, tracks, None)     # (the current stream IS the chain stream here)
             self.slam.launched()
@@ -516,14 +500,13 @@ class FramePipeline:
                     for p in pend:
                         if p is not None:
                             p["done"] = done
-        return pend
+        return QueuedRound(pend, round_seq, kf_seq)
 
     def _own_masks(self, mine: Frame, amg_pending):
         """(seg_map, masks) of the keyframe this rank owns from ITS generator; (None, None) when it kept no mask."""
         if self.mask_source is not None:
             seg, masks = self.mask_source(mine)
             return (seg, masks) if masks is not None and masks.shape[0] > 0 else (None, None)
-        from .utils import segment_utils
         r = self.amg.generate_finish(amg_pending)                  # filter + box NMS (mask_generator.py:113)
         self.sam_out = r
         masks = r["masks"]
@@ -542,7 +525,6 @@ class FramePipeline:
         """Every keyframe of the round is tracked on every rank with the masks its OWNER's generator produced (mask_generator.py:102-120 runs
         on the owner only).  A keyframe whose owner kept no mask falls back to the masks the frame carries (the precomputed-mask seam,
         mask_generator.py:94-95) -- with random-init SAM2 weights that is every keyframe, stated in bench.py's help."""
-        from .utils import segment_utils
         mine = group[self.rank]
         H, W = mine.rgb.shape[:2]
         _, masks = self._own_masks(mine, amg_pending)
@@ -566,13 +548,13 @@ class FramePipeline:
             self.chain_stream.wait_stream(torch.cuda.current_stream())
 
     # ------------------------------------------------------------------ loop closure
-    def _record_keyframes(self, first: int, last_seq: int = 0, last_n: int = 0) -> None:
+    def _record_keyframes(self, q: QueuedRound, last_n: int = 0) -> None:
         """`kfs` entries of a finished round: the rows each of its keyframes appended, from the map steps' result blocks -- pinned host memory
-        the round's tracking results were already waited behind (no launch, no sync, no device read).  `last_seq`, `last_n`: the block the caller
-        has read already (the round's last map step and the size after it)."""
-        for frame_id, seq in self._round_kf_seq.pop(first, ()):
+        the round's tracking results were already waited behind (no launch, no sync, no device read).  `last_n`: the size after the round's last
+        map step, if the caller has read that block already."""
+        for frame_id, seq in q.kf_seq:
             # no valid depth: no map step, no rows
-            end = self._kf_rows_end if not seq else last_n if seq == last_seq else self.slam.size_after(seq)
+            end = self._kf_rows_end if not seq else last_n if last_n and seq == q.last_seq else self.slam.size_after(seq)
             self.kfs[frame_id] = {"id": frame_id, "pcd_idxs": (self._kf_rows_end, end)}
             self._kf_rows_end = end
 
@@ -593,7 +575,7 @@ class FramePipeline:
         bench's shape), as `gather_dense` is -- rare, and outside the keyframe loop; exchanging only the rows that change owner is not done.
         Not with a round pre-queued (`step_round(..., upcoming=...)`: its chains hold the old rows and buffers; step it or `drain()` first) and not
         under `emulate`.  Returns {"n_points", "n_dropped", "n_keyframes", "n_pruned_keyframes"}."""
-        if self._chains:
+        if self._queued:
             raise L.OvoHipError("close_loop: a round is pre-queued -- step it (or drain()) before the map is re-anchored")
         if self.emulate:
             raise L.OvoHipError("close_loop: not under emulate= (a timing stand-in holds no real shards)")
@@ -608,75 +590,31 @@ class FramePipeline:
                                                         exact_identity=True, ws=self._reanchor_ws)
         n_new = self._kf_rows_end = int(seg_dst[-1])
         if self.dense:
-            B, R = self.SHARD_BLOCK, self.world
-            blocks = -(-self.slam._cap // B)                        # (the capacity grows only when the tracker lists a keyframe twice)
-            rows_local = max(self.rows_local, -(-blocks // R) * B if R > 1 else self.slam._cap)
-            inc = self.incremental_query
-            src = [self.acc, self.cnt, self.dense_cls if inc else None, self.dense_conf if inc else None]
-            if R > 1:                                              # shard-major, only the rows that hold points -- as gather_dense; no merge copy
-                rows = -(-(-(-n_old // B)) // R) * B                 # gather_dense's `per * B`: the blocks that hold points, dealt to R ranks
-                src = [None if t is None else self._gather(t[:rows].contiguous()) for t in src]
-            dev = self.device
-            out = [torch.empty((rows_local, self.D), dtype=torch.float32, device=dev), torch.empty(rows_local, dtype=torch.int32, device=dev),
-                   torch.empty(rows_local, dtype=torch.int64, device=dev) if inc else None,
-                   torch.empty(rows_local, dtype=torch.float32, device=dev) if inc else None]
-            dense_repack(src, out, n_old, seg_src, seg_dst, n_fill=rows_local * R, empty_cls=self.empty_cls if inc else -1,
-                         empty_conf=self.empty_conf if inc else 0.0, src_shards=R, shard=(self.rank, R, B), ws=self._reanchor_ws)
-            torch.cuda.current_stream().synchronize()              # the old buffers are released below
-            del src
-            self.acc, self.cnt, self.rows_local = out[0], out[1], rows_local
-            if inc:
-                self.dense_cls, self.dense_conf = out[2], out[3]
-                if self.touched.numel() < rows_local:
-                    self.touched = torch.empty(rows_local, dtype=torch.int32, device=dev)
-                self.n_touched.zero_()                             # the lists name old rows
-                self._touch_parity = 0
+            self.dense_map.repack(n_old, seg_src, seg_dst, self.slam._cap, self._reanchor_ws)
         if semantic_update:                                        # OVOSemMap.run's sequence after slam.map reports an updated map
             updated = self.ovo.update_map(self.slam.get_map(), self.kfs, same_instance=same_instance)
             if updated is not None:
                 self.slam.update_pcd_obj_ids(updated)
-        # what still names old rows / old buffers: the last keyframe's point -> mask lists, the tracker's scratch, per-round sequence numbers, the
-        # views of the old class map handed out by the last step
+        # what still names old rows / old buffers: the last keyframe's point -> mask lists, the tracker's scratch, the views of the old class map
+        # handed out by the last step (per-round sequence numbers live in a QueuedRound, and none is queued: checked on entry)
         self.ovo.last_point_seg = self.ovo.last_mask_rows = self.ovo.last_hits = None
         self.ovo.last_n_points = n_new
         self.ovo._track_ws = None
-        self._round_seq.clear()
-        self._round_kf_seq.clear()
         for k in ("dense_cls", "dense_conf"):
             self.last.pop(k, None)
         n_pruned = sum(1 for k in old_kfs if k not in self.kfs)
         return {"n_points": n_new, "n_dropped": sum(v["pcd_idxs"][1] - v["pcd_idxs"][0] for k, v in old_kfs.items() if k not in self.kfs),
                 "n_keyframes": len(self.kfs), "n_pruned_keyframes": n_pruned}
 
-    # ------------------------------------------------------------------ dense shards
-    def local_rows(self, n: int) -> int:
-        """Rows of this rank's shard that hold points of a map with n points (block-cyclic, blocks of SHARD_BLOCK points)."""
-        if self.world == 1:
-            return n
-        B, R, r = self.SHARD_BLOCK, self.world, self.rank
-        full, rem = divmod(n, B)                                   # `full` complete blocks, then one of `rem` points
-        mine = (full - r + R - 1) // R if full > r else 0          # complete blocks owned by r
-        return mine * B + (rem if full % R == r else 0)
+    # ------------------------------------------------------------------ dense map
+    @property
+    def incremental_query(self) -> bool:
+        """The dense class map is resident and patched per keyframe (`DenseMap.incremental`); only meaningful with `dense`."""
+        return self.dense_map.incremental
 
     def gather_dense(self, n: Optional[int] = None):
-        """The whole dense state on every rank, in point order: (acc f32[n, D], cnt i32[n], cls i64[n], conf f32[n]).  The concatenation
-        of the shards -- no arithmetic, so it equals the one-process accumulators bit for bit.  A map-sized collective: for export /
-        tests, never inside the keyframe loop (queries run on the shards)."""
-        n = self.slam._n if n is None else n
-        if self.world == 1:
-            inc = getattr(self, "incremental_query", False)
-            return self.acc[:n], self.cnt[:n], self.dense_cls[:n] if inc else None, self.dense_conf[:n] if inc else None
-        B, R = self.SHARD_BLOCK, self.world
-        nb = -(-n // B)
-        per = -(-nb // R)                                          # blocks per rank (the last rank's may be short / absent)
-        rows = per * B
-
-        def merge(local: torch.Tensor) -> torch.Tensor:
-            g = self._gather(local[:rows].contiguous())            # [R, per * B, ...]
-            g = g.reshape(R, per, B, *local.shape[1:]).transpose(0, 1).reshape(per * R * B, *local.shape[1:])   # block b = (b // R, b % R)
-            return g[:n]
-        return merge(self.acc), merge(self.cnt), merge(self.dense_cls) if self.incremental_query else None, \
-            merge(self.dense_conf) if self.incremental_query else None
+        """`DenseMap.gather` of the first n points (default: the whole map): a map-sized collective that every rank calls."""
+        return self.dense_map.gather(self.slam._n if n is None else n)
 
     def join(self) -> None:
         """Make the main stream wait for the SAM2 and ViT streams (everything of the frames stepped so far)."""

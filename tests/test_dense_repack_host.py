@@ -1,7 +1,6 @@
 """The host side of loop closure in the round pipeline (no GPU): ovo_dense_repack's argument checks -- every one of them before anything is queued --
-the segment-table builder with a head segment, and the block-cyclic rule the kernel, `FramePipeline.local_rows` and `gather_dense` share."""
+the segment-table builder with a head segment, and the block-cyclic rule the kernel, `dense_map.shard_rows` and `merge_shards` share."""
 import ctypes as C
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -104,7 +103,7 @@ def _owner(g, B, R):
 
 @pytest.mark.parametrize("B, R", [(16, 1), (16, 2), (16, 3), (4096, 8)])
 def test_block_cyclic_rule_agrees_with_the_pipeline(B, R):
-    from ovo_amd.pipeline import FramePipeline
+    from ovo_amd.entities.dense_map import shard_rows
     sizes = [0, 1, B - 1, B, B + 1, R * B - 1, R * B, R * B + 1, 5 * B, 5 * B + 3, (2 * R + 1) * B, (2 * R + 1) * B + B - 1]
     for n in sizes:
         g = np.arange(n)
@@ -113,10 +112,10 @@ def test_block_cyclic_rule_agrees_with_the_pipeline(B, R):
             mine = local[rank == r]
             want = 0 if mine.size == 0 else int(mine.max()) + 1
             assert np.array_equal(np.sort(mine), np.arange(want))                  # a rank's rows are dense from 0
-            assert FramePipeline.local_rows(SimpleNamespace(world=R, rank=r, SHARD_BLOCK=B), n) == want, (n, r)
+            assert shard_rows(n, r, R, B) == want, (n, r)
         if R == 1:
             continue
-        # gather_dense's merge: shards cut to per * B rows, stacked rank-major, [R, per, B] -> [per, R, B] -> the first n rows
+        # merge_shards' order: shards cut to per * B rows, stacked rank-major, [R, per, B] -> [per, R, B] -> the first n rows
         per = -(-(-(-n // B)) // R)
         shards = np.full((R, per * B), -1, np.int64)
         shards[rank, local] = g

@@ -77,14 +77,14 @@ def _worker(rank, world, port, path, encoder_batch, own_masks=False, n_frames=N_
         assert calls == list(range(rank, n_frames, world)) and pipe.mask_exchanges == n_frames // world
     # invariant of the resident dense map on every shard: it equals a full re-query of the shard's rows
     from ovo_amd.utils import clip_utils
-    nl = pipe.local_rows(pipe.slam._n)
-    _, cls, conf = clip_utils.similarity(pipe.acc[:nl], pipe.texts, cnt=pipe.cnt[:nl], want_sim=False, want_argmax=True)
-    bad = (cls != pipe.dense_cls[:nl]).nonzero().reshape(-1)
-    assert bad.numel() == 0, (rank, nl, bad[:8].tolist(), pipe.cnt[:nl][bad[:8]].tolist(), int(pipe.n_touched[0]), int(pipe.n_touched[1]))
-    assert torch.equal(conf, pipe.dense_conf[:nl])
+    nl = pipe.dense_map.local_rows(pipe.slam._n)
+    _, cls, conf = clip_utils.similarity(pipe.dense_map.acc[:nl], pipe.texts, cnt=pipe.dense_map.cnt[:nl], want_sim=False, want_argmax=True)
+    bad = (cls != pipe.dense_map.dense_cls[:nl]).nonzero().reshape(-1)
+    assert bad.numel() == 0, (rank, nl, bad[:8].tolist(), pipe.dense_map.cnt[:nl][bad[:8]].tolist(), int(pipe.dense_map.n_touched[0]), int(pipe.dense_map.n_touched[1]))
+    assert torch.equal(conf, pipe.dense_map.dense_conf[:nl])
     state = _state(pipe)                                           # gather_dense is a collective: every rank calls it
     state["exchanges"] = pipe.exchanges
-    state["rows_local"] = pipe.rows_local
+    state["rows_local"] = pipe.dense_map.rows_local
     if rank == 0:
         torch.save(state, path)
     parallel.barrier()
@@ -123,7 +123,7 @@ def _ranks_equal_single_process(world, n_frames, encoder_batch, own_masks):
     assert len(ref["objects"]) > 5 and ref["cnt"].sum() > 0 and (ref["cls"] >= 0).any(), "fixture too small to mean anything"
     from ovo_amd.utils import clip_utils
     n = pipe.slam._n
-    _, full_cls, full_conf = clip_utils.similarity(pipe.acc[:n], pipe.texts, cnt=pipe.cnt[:n], want_sim=False, want_argmax=True)
+    _, full_cls, full_conf = clip_utils.similarity(pipe.dense_map.acc[:n], pipe.texts, cnt=pipe.dense_map.cnt[:n], want_sim=False, want_argmax=True)
     assert torch.equal(ref["cls"], full_cls.cpu()) and torch.equal(ref["conf"], full_conf.cpu())      # the reference run's own invariant
     for k in ("pcd", "ids", "obj_ids", "colors", "table", "acc", "cnt", "cls", "conf", "sim", "inst_cls"):
         if not torch.equal(got[k], ref[k]):

@@ -200,10 +200,10 @@ def _incremental_dense_run(fused: bool, monkeypatch):
     frames = synthetic_frames(5, DEV, scale=0.35, n_masks_grid=(3, 4), n_blobs=4)
     fractions, accs = [], []
     for f in frames:
-        parity = None if fused else pipe._touch_parity
+        parity = None if fused else pipe.dense_map._touch_parity
         out = pipe.step(f)
         n = out["n_points"]
-        _, cls, conf = clip_utils.similarity(pipe.acc[:n], pipe.texts, cnt=pipe.cnt[:n], want_sim=False, want_argmax=True)
+        _, cls, conf = clip_utils.similarity(pipe.dense_map.acc[:n], pipe.texts, cnt=pipe.dense_map.cnt[:n], want_sim=False, want_argmax=True)
         assert torch.equal(out["dense_cls"], cls) and torch.equal(out["dense_conf"], conf)
         seg = pipe.ovo.last_point_seg
         matched = torch.nonzero(seg >= 0).flatten()
@@ -212,12 +212,12 @@ def _incremental_dense_run(fused: bool, monkeypatch):
             touched = int(hits[-4].item())
             assert torch.equal(torch.sort(hits[:touched].long()).values, matched)          # every matched point, once, in any order
         else:                                                      # (a keyframe without descriptors launches no scatter and leaves the counters alone)
-            touched = int(pipe.n_touched[pipe._touch_parity ^ 1].item()) if pipe._touch_parity != parity else 0
+            touched = int(pipe.dense_map.n_touched[pipe.dense_map._touch_parity ^ 1].item()) if pipe.dense_map._touch_parity != parity else 0
             kept = torch.tensor(pipe.ovo.last_mask_rows, device=seg.device) >= 0
             assert touched <= matched.numel()
             assert touched == int(kept[seg[matched].long()].sum().item())                  # every matched point of a kept mask, once
         fractions.append(touched / n)
-        accs.append((pipe.acc[:n].clone(), pipe.cnt[:n].clone()))
+        accs.append((pipe.dense_map.acc[:n].clone(), pipe.dense_map.cnt[:n].clone()))
     assert (out["dense_cls"] >= 0).any() and max(fractions) > 0 and max(fractions) < 0.6
     return accs
 
@@ -237,6 +237,30 @@ def test_fused_scatter_query_accumulators_equal_the_three_launch_path(monkeypatc
     for (xa, ca), (xb, cb) in zip(a, b):
         assert torch.equal(xa, xb) and torch.equal(ca, cb)
     assert float(a[-1][0].abs().sum()) > 0
+
+
+def test_host_decision_rounds_equal_queued_rounds():
+    """A round whose keyframes are tracked one by one with host decisions (`_native_ok` false: `step_round`'s other branch -- map, track, plan per
+    keyframe, dense state through scan + apply + touched-rows query) against the queued round with device decisions: the same map, instances,
+    keyframe rows and dense accumulators, and a resident class map that equals the full re-query after every keyframe."""
+    from ovo_amd.pipeline import FramePipeline, synthetic_frames
+    from ovo_amd.utils import clip_utils
+    frames = synthetic_frames(4, DEV, scale=0.35, n_masks_grid=(3, 4), n_blobs=4)
+    pipes = [FramePipeline(DEV, vit_card="tiny-pe", sam_card=None, n_map=60_000, n_text=7, scale=0.35, extra_capacity=200_000, track_th=40)
+             for _ in range(2)]
+    queued, host = pipes
+    host.ovo.config["host_decisions"] = True
+    for f in frames:
+        a, out = queued.step(f), host.step(f)
+        assert a["n_points"] == out["n_points"] and a["n_instances"] == out["n_instances"]
+        n, dm = out["n_points"], host.dense_map
+        _, cls, conf = clip_utils.similarity(dm.acc[:n], host.texts, cnt=dm.cnt[:n], want_sim=False, want_argmax=True)
+        assert torch.equal(out["dense_cls"], cls) and torch.equal(out["dense_conf"], conf)
+    assert (out["dense_cls"] >= 0).any(), "fixture classified no point"
+    assert torch.equal(queued.slam.pcd[:n], host.slam.pcd[:n]) and torch.equal(queued.slam.pcd_obj_ids[:n], host.slam.pcd_obj_ids[:n])
+    assert list(queued.ovo.objects) == list(host.ovo.objects) and queued.ovo.next_ins_id == host.ovo.next_ins_id
+    assert queued.kfs == host.kfs
+    assert torch.equal(queued.dense_map.acc[:n], dm.acc[:n]) and torch.equal(queued.dense_map.cnt[:n], dm.cnt[:n])
 
 
 def test_hit_list_of_a_point_shard():
@@ -308,7 +332,7 @@ def test_drain_reads_back_a_prequeued_round():
     instances then match what the device already did to the map."""
     pipe, _ = _rounds(400_000, n_rounds=3, drain_at=2)             # two rounds stepped, the third pre-queued
     full, _ = _rounds(400_000, n_rounds=3)
-    assert not pipe._chains and not pipe.ovo._track_pending
+    assert not pipe._queued and not pipe.ovo._track_pending
     assert torch.equal(pipe.slam.pcd_obj_ids, full.slam.pcd_obj_ids) and pipe.slam._n == full.slam._n
     assert list(pipe.ovo.objects) == list(full.ovo.objects) and pipe.ovo.next_ins_id == full.ovo.next_ins_id
 

@@ -122,15 +122,15 @@ def test_a_real_closure():
     assert list(pipe.kfs) == order
     assert [pipe.kfs[k] for k in order] == [{"id": k, "pcd_idxs": (int(a), int(b))} for k, a, b in zip(order, ends[:-1], ends[1:])]
     # the dense state: the re-pack of what was there, bit for bit, then the empty state up to the capacity
-    got = [pipe.acc, pipe.cnt, pipe.dense_cls, pipe.dense_conf]
+    got = [pipe.dense_map.acc, pipe.dense_map.cnt, pipe.dense_map.dense_cls, pipe.dense_map.dense_conf]
     for name, g, d in zip(("acc", "cnt", "cls", "conf"), got, dense):
         g, w = g[:n].cpu().numpy(), d[gather]
         bits = (lambda x: x.view(np.int32)) if g.dtype == np.float32 else (lambda x: x)
         assert np.array_equal(bits(g), bits(w)), name
     cap = pipe.slam._cap
-    assert pipe.acc.shape[0] == cap > n
-    assert not pipe.acc[n:].any() and not pipe.cnt[n:].any()
-    assert (pipe.dense_cls[n:] == pipe.empty_cls).all() and (pipe.dense_conf[n:] == pipe.empty_conf).all()
+    assert pipe.dense_map.acc.shape[0] == cap > n
+    assert not pipe.dense_map.acc[n:].any() and not pipe.dense_map.cnt[n:].any()
+    assert (pipe.dense_map.dense_cls[n:] == pipe.dense_map.empty_cls).all() and (pipe.dense_map.dense_conf[n:] == pipe.dense_map.empty_conf).all()
     # the map
     assert np.array_equal(pipe.slam.pcd_ids.cpu().numpy(), ids[gather]) and np.array_equal(pipe.slam.pcd_colors.cpu().numpy(), col[gather])
     assert np.array_equal(pipe.slam.pcd_obj_ids.cpu().numpy(), obj[gather])              # (nothing merges under this predicate)
@@ -156,9 +156,9 @@ def test_a_real_closure():
     grown = sum(pipe.kfs[k]["pcd_idxs"][1] - pipe.kfs[k]["pcd_idxs"][0] for k in (4, 5))
     assert grown > 0 and out["n_points"] == pipe.slam._n == n + grown and pipe.kfs[5]["pcd_idxs"][1] == n + grown
     m = pipe.slam._n
-    _, cls, conf = clip_utils.similarity(pipe.acc[:m], pipe.texts, cnt=pipe.cnt[:m], want_sim=False, want_argmax=True)
-    assert torch.equal(cls, pipe.dense_cls[:m]) and torch.equal(conf, pipe.dense_conf[:m])
-    assert torch.equal(out["dense_cls"], pipe.dense_cls[:m]) and (cls[n:] >= 0).any()    # the new keyframes' points got classes
+    _, cls, conf = clip_utils.similarity(pipe.dense_map.acc[:m], pipe.texts, cnt=pipe.dense_map.cnt[:m], want_sim=False, want_argmax=True)
+    assert torch.equal(cls, pipe.dense_map.dense_cls[:m]) and torch.equal(conf, pipe.dense_map.dense_conf[:m])
+    assert torch.equal(out["dense_cls"], pipe.dense_map.dense_cls[:m]) and (cls[n:] >= 0).any()    # the new keyframes' points got classes
 
 
 # ------------------------------------------------------------------------------------------------ 3. two ranks equal one process
@@ -211,7 +211,7 @@ def test_close_loop_refuses_a_pre_queued_round_and_emulation():
     frames = _frames(3)
     pipe = FramePipeline(DEV, **KW)
     pipe.step(frames[0], frames[1:])                               # the look-ahead pre-queues keyframe 1's chains
-    assert pipe._chains
+    assert pipe._queued
     with pytest.raises(_lib.OvoHipError):
         pipe.close_loop([_row(0, frames[0].c2w)])
     pipe.drain()

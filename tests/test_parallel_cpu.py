@@ -71,9 +71,9 @@ def test_single_process_is_a_noop():
 
 
 def test_dense_shard_bookkeeping():
-    """Block-cyclic point shards of the dense accumulators (pipeline.FramePipeline.local_rows / gather_dense): every point has exactly one
-    owner and one local row, local rows of a rank are dense in [0, local_rows(n)), and the merge order restores point order."""
-    from ovo_amd.pipeline import FramePipeline
+    """Block-cyclic point shards of the dense accumulators (entities/dense_map.py: shard_rows / merge_shards): every point has exactly one
+    owner and one local row, local rows of a rank are dense in [0, shard_rows(n)), and the merge order restores point order."""
+    from ovo_amd.entities.dense_map import merge_shards, shard_rows
     B = 8
     for world in (1, 2, 3, 8):
         for n in (0, 1, 7, 8, 9, 16, 17, 63, 64, 65, 200):
@@ -82,8 +82,7 @@ def test_dense_shard_bookkeeping():
                 blk = p // B
                 owners[blk % world].append(((blk // world) * B + p % B, p))
             for r in range(world):
-                fake = type("P", (), {"world": world, "rank": r, "SHARD_BLOCK": B})()
-                nl = FramePipeline.local_rows(fake, n)
+                nl = shard_rows(n, r, world, B)
                 rows = sorted(lr for lr, _ in owners[r])
                 assert rows == list(range(nl)), (world, n, r, nl, rows[:5])
             # merge: [world, per * B] -> block b = (b // world, b % world)
@@ -94,5 +93,4 @@ def test_dense_shard_bookkeeping():
                 for r in range(world):
                     for lr, p in owners[r]:
                         local[r, lr] = p
-                merged = local.reshape(world, per, B).transpose(0, 1).reshape(per * world * B)[:n]
-                assert torch.equal(merged, torch.arange(n))
+                assert torch.equal(merge_shards(local, n, B), torch.arange(n))

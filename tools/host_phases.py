@@ -31,10 +31,10 @@ for f in frames[4:]:
     nn = pipe.slam._n
     rows = torch.tensor(pipe.ovo.last_mask_rows, dtype=torch.int32).to(dev, non_blocking=True)
     L.check(lib.ovo_scatter_accum(L.ptr(pipe.ovo.last_point_seg), pipe.ovo.last_point_seg.shape[0], L.ptr(rows), rows.shape[0],
-                                  L.ptr(pipe.ovo.last_clip_embeds), pipe.D, L.ptr(pipe.acc), L.ptr(pipe.cnt), L.stream())); t = tick("scatter", t)
+                                  L.ptr(pipe.ovo.last_clip_embeds), pipe.D, L.ptr(pipe.dense_map.acc), L.ptr(pipe.dense_map.cnt), L.stream())); t = tick("scatter", t)
     table = pipe.ovo.get_objs_clips(); t = tick("gather", t)
     clip_utils.similarity(table, pipe.texts, want_argmax=True); t = tick("query_inst", t)
-    clip_utils.similarity(pipe.acc[:nn], pipe.texts, cnt=pipe.cnt[:nn], want_sim=False, want_argmax=True); t = tick("query_dense", t)
+    clip_utils.similarity(pipe.dense_map.acc[:nn], pipe.texts, cnt=pipe.dense_map.cnt[:nn], want_sim=False, want_argmax=True); t = tick("query_dense", t)
 torch.cuda.synchronize()
 total = time.perf_counter() - T0
 print({k: round(1e3 * v / N, 3) for k, v in acc.items()}, "host sum ms", round(1e3 * sum(acc.values()) / N, 2), "wall ms/frame", round(1e3 * total / N, 2))

@@ -37,10 +37,10 @@ for f in frames[3:38]:
     nn = pipe.slam._n
     rows = torch.tensor(pipe.ovo.last_mask_rows, dtype=torch.int32).to(dev)
     L.check(L.load().ovo_scatter_accum(L.ptr(pipe.ovo.last_point_seg), pipe.ovo.last_point_seg.shape[0], L.ptr(rows), rows.shape[0],
-                                       L.ptr(pipe.ovo.last_clip_embeds), pipe.D, L.ptr(pipe.acc), L.ptr(pipe.cnt), L.stream())); t = tick("scatter", t)
+                                       L.ptr(pipe.ovo.last_clip_embeds), pipe.D, L.ptr(pipe.dense_map.acc), L.ptr(pipe.dense_map.cnt), L.stream())); t = tick("scatter", t)
     table = pipe.ovo.get_objs_clips(); t = tick("gather", t)
     clip_utils.similarity(table, pipe.texts, want_argmax=True); t = tick("query_inst", t)
-    clip_utils.similarity(pipe.acc[:nn], pipe.texts, cnt=pipe.cnt[:nn], want_sim=False, want_argmax=True); t = tick("query_dense", t)
+    clip_utils.similarity(pipe.dense_map.acc[:nn], pipe.texts, cnt=pipe.dense_map.cnt[:nn], want_sim=False, want_argmax=True); t = tick("query_dense", t)
     steps.append({k: round(1e3 * (acc[k] - before.get(k, 0.0)), 2) for k in acc})
 worst = max(steps, key=lambda d: sum(d.values()))
 print('worst step', steps.index(worst), worst)

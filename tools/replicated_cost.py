@@ -6,7 +6,6 @@ usage: python tools/replicated_cost.py [frames] [round]        (round = 1: one k
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from ovo_amd import _lib as L
 from ovo_amd.pipeline import FramePipeline, synthetic_frames
 from ovo_amd.utils import geometry_utils as G
 dev = torch.device("cuda", 0)
@@ -17,7 +16,6 @@ pipe.prefetch = False
 if os.environ.get("HOST"):
     pipe.ovo.config["host_decisions"] = True
 frames = synthetic_frames(N + R, dev)
-lib = L.load()
 acc = {}
 def tick(name, t0):
     t = time.perf_counter(); acc[name] = acc.get(name, 0.0) + t - t0; return t
@@ -54,12 +52,7 @@ def round_(group, timed):
         if timed: t = tick("store+fuse", t)
         point_seg, mask_rows = pipe.ovo.last_point_seg, pipe.ovo.last_mask_rows
         rows = torch.tensor(mask_rows, dtype=torch.int32).to(dev, non_blocking=True)
-        k2 = pipe._touch_parity; pipe._touch_parity ^= 1
-        touched, n_cur, n_nxt = L.ptr(pipe.touched), pipe.n_touched[k2:].data_ptr(), pipe.n_touched[k2 ^ 1:].data_ptr()
-        L.check(lib.ovo_scatter_accum_touched(L.ptr(point_seg), point_seg.shape[0], L.ptr(rows), rows.shape[0], L.ptr(d), pipe.D, L.ptr(pipe.acc), L.ptr(pipe.cnt),
-                                              touched, n_cur, n_nxt, 0, 1, pipe.SHARD_BLOCK, L.stream()))
-        L.check(lib.ovo_similarity_rows(L.ptr(pipe.acc), 0, touched, n_cur, min(point_seg.shape[0], pipe.rows_local), pipe.D, L.ptr(pipe.texts), pipe.texts.shape[0],
-                                        L.ptr(pipe.cnt), 0, 0.0, 0.0, 0.0, L.ptr(pipe.dense_cls), L.ptr(pipe.dense_conf), L.stream()))
+        pipe.dense_map.apply(point_seg, rows, d, None)
         if timed: t = tick("dense scatter+query (launch)", t)
 round_(frames[:R], False)
 torch.cuda.synchronize()
