@@ -699,6 +699,49 @@ int ovo_dense_repack(const float *acc, const int32_t *cnt, const int64_t *cls, c
                      int shard_count, int shard_block, int64_t n_fill, int64_t empty_cls, float empty_conf, const int64_t *seg_src_host,
                      const int64_t *seg_dst_host, int K, void *ws, size_t ws_bytes, ovo_stream_t stream);
 
+/* =============================================================================================
+ * The map seen from a camera pose (ABI v18): what the reference's visualiser draws (ovo/entities/visualizer.py; _update_query_vis :165-181) without its
+ * GUI -- a z-buffered point splat into a view that has no depth image, the inverse of the tracking pass.
+ * ============================================================================================= */
+typedef struct {
+    float w2c[16];      /* inverse camera pose, row-major 4x4 (as ovo_camera_t.w2c) */
+    float K[9];         /* intrinsics, row-major 3x3 */
+    float near, far;    /* kept camera-frame depths, both inclusive: 0 < near <= far (far may be +inf) */
+    int32_t h, w;       /* image size, h * w <= 2^26 */
+    int32_t radius;     /* a point covers the (2 radius + 1)^2 pixels around its own, 0 .. 4 */
+} ovo_view_t;
+
+/* ovo_render_points: xyz f32[n,3] -> row i32[h,w], depth f32[h,w].
+ * For point i, (zc, u, v) are computed by exactly the arithmetic of ovo_project_points (left-to-right FMA chains, IEEE divisions, half-to-even
+ * rounding, truncation to int with INT_MIN when unrepresentable); zc is the un-normalised camera-frame z.  The point CONTRIBUTES iff
+ *   zc >= near && zc <= far && u >= -radius && u < w + radius && v >= -radius && v < h + radius
+ * (NaN fails every comparison, INT_MIN fails them too) and then covers the pixels (x, y) with |x - u| <= radius, |y - v| <= radius inside the image.
+ * Pixel (y, x) takes the covering point with the smallest 64-bit key (u64)float_bits(zc) << 32 | (u32)i -- near > 0, so the bits order like the
+ * values: the nearest point, the smallest row among equal depths -- and row[y,x] = i, depth[y,x] = zc of that point; a pixel nothing covers gets
+ * row = -1, depth = 0 (the convention for "no depth").  The result is a pure function of the inputs: bit-identical from launch to launch,
+ * whatever order the atomics arrive in.
+ * Three launches: fill the key image, one grid-stride pass over the map with one 64-bit atomic minimum per covered pixel, decode.  ws: device
+ * scratch of ovo_render_workspace_bytes(h, w) = 8 h w bytes (8-byte aligned).  Everything is checked before anything is queued -- null view / row /
+ * depth / ws, xyz null with n > 0, h, w >= 1, h * w <= 2^26, 0 <= radius <= 4, near > 0, far >= near (neither NaN), 0 <= n < 2^31, ws_bytes -- a
+ * violation returns OVO_E_ARG with nothing launched.  n == 0 is valid: an empty image. */
+size_t ovo_render_workspace_bytes(int h, int w);
+int ovo_render_points(const float *xyz, int64_t n, const ovo_view_t *view, int32_t *row, float *depth, void *ws, size_t ws_bytes,
+                      ovo_stream_t stream);
+
+/* ovo_render_resolve: a row image i32[h,w] (entries outside [0, n) are empty pixels) -> whatever the caller asks for, one launch over the pixels,
+ * pure gather (f32 values travel as their bits).  Every source and output pointer may be NULL; an output needs its source.
+ *   per point     point_ins i32[n] -> out_ins i32[h,w], -1 on empty pixels;   point_rgb u8[n,3] -> out_rgb u8[h,w,3], `background`
+ *                 (0x00BBGGRR) on empty pixels;   point_cls i64[n] / point_conf f32[n] (the dense map's resident arrays) -> out_cls i64[h,w] /
+ *                 out_conf f32[h,w], fill_cls / fill_val on empty pixels
+ *   per instance  tables over n_slots instance ids, indexed by point_ins[row]:  ins_cls i64[n_slots] -> out_ins_cls i64[h,w];   ins_val
+ *                 f32[n_slots] -> out_val f32[h,w];   empty pixels, unassigned points (id < 0) and ids >= n_slots get fill_cls / fill_val
+ * Checked before anything is queued: row, h, w >= 1, h * w <= 2^26, 0 <= n < 2^31, n_slots >= 0, a per-instance table given without point_ins, an
+ * output given without its source. */
+int ovo_render_resolve(const int32_t *row, int h, int w, int64_t n, const int32_t *point_ins, const uint8_t *point_rgb, uint32_t background,
+                       const int64_t *point_cls, const float *point_conf, const int64_t *ins_cls, const float *ins_val, int n_slots,
+                       int64_t fill_cls, float fill_val, int32_t *out_ins, uint8_t *out_rgb, int64_t *out_cls, float *out_conf,
+                       int64_t *out_ins_cls, float *out_val, ovo_stream_t stream);
+
 
 /* =============================================================================================
  * The keyframe chain without host round trips (MI355X extension of a6 / a9; what the reference does with a `.sum()` / vstack

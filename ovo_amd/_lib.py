@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "lib", "libovo_hip.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 E_UNSUPPORTED = -3          # OVO_E_UNSUPPORTED: the entry point does not cover this shape; the caller takes its general path
 
 
@@ -131,6 +131,12 @@ class EvalGrid(C.Structure):
     _fields_ = [("lo", C.c_float * 3), ("dim", C.c_int32 * 3), ("h", C.c_double)]
 
 
+class View(C.Structure):
+    """ovo_view_t"""
+    _fields_ = [("w2c", C.c_float * 16), ("K", C.c_float * 9), ("near", C.c_float), ("far", C.c_float),
+                ("h", C.c_int32), ("w", C.c_int32), ("radius", C.c_int32)]
+
+
 DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.uint8: 3}
 
 _SIGNATURES = {
@@ -224,6 +230,9 @@ _SIGNATURES = {
     "ovo_map_reanchor": (_I32, [_P, _P, _P, _P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _I32, _P, _SZ, _P]),
     "ovo_dense_repack_workspace_bytes": (_SZ, [_I32]),
     "ovo_dense_repack": (_I32, [_P, _P, _P, _P, _I32, _I32, _I64, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I64, _I64, _F32, _P, _P, _I32, _P, _SZ, _P]),
+    "ovo_render_workspace_bytes": (_SZ, [_I32, _I32]),
+    "ovo_render_points": (_I32, [_P, _I64, C.POINTER(View), _P, _P, _P, _SZ, _P]),
+    "ovo_render_resolve": (_I32, [_P, _I32, _I32, _I64, _P, _P, C.c_uint32, _P, _P, _P, _P, _I32, _I64, _F32, _P, _P, _P, _P, _P, _P, _P]),
     "ovo_sam_i2t_attention": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_sam_t2i_attention": (_I32, [_P, _P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_paint_segmap": (_I32, [_P, _I32, _I64, _P, _P]),

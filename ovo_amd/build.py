@@ -26,7 +26,8 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno
 # gemm8p.hip: no SLP vectorisation either, for speed -- its epilogues hold a value's table entry / bias / accumulator in registers that do not pair up, and the
 # packed form pays two v_mov per v_pk_fma to line them up: FC1 + GELU (57344, 1792, 448) 135.1 -> 131.1 us, (16156, 4096, 1024) 133.6 -> 131.0, the other
 # epilogues unchanged (two alternating rounds of both builds in one session, tools/gemm_bench.py); results are bit-identical (the same IEEE operations)
-EXTRA = {"geometry.hip": ["-ffp-contract=off"], "evalknn.hip": ["-ffp-contract=off"], "mlp_stream.hip": ["-fno-slp-vectorize"], "gemm_stream.hip": ["-fno-slp-vectorize"],
+EXTRA = {"geometry.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=off"],   # render.hip shares geometry.hip's projection (csrc/projection.h)
+         "evalknn.hip": ["-ffp-contract=off"], "mlp_stream.hip": ["-fno-slp-vectorize"], "gemm_stream.hip": ["-fno-slp-vectorize"],
          "winattn.hip": ["-fno-slp-vectorize"], "gemm8p.hip": ["-fno-slp-vectorize"],
          "neck_stream.hip": ["-fno-slp-vectorize"],  # mlp_stream.hip's sibling: the same flags
          "merger.hip": ["-fno-slp-vectorize"]}       # k_merge_clips takes a row's sum of squares and shares its CU: the same treatment as the LayerNorm files

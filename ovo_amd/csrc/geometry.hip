@@ -9,27 +9,9 @@
 
 #include "common.h"
 #include "depth_filter.h"
+#include "projection.h"      // dot3 / dot4 / f2i / project(w2c, K, ...): shared with render.hip
 
 namespace {
-
-__device__ __forceinline__ float dot3(const float *m, float x, float y, float z) {
-    float a = __fmul_rn(m[0], x);
-    a = __fmaf_rn(m[1], y, a);
-    a = __fmaf_rn(m[2], z, a);
-    return a;
-}
-__device__ __forceinline__ float dot4(const float *m, float x, float y, float z, float w) {
-    float a = __fmul_rn(m[0], x);
-    a = __fmaf_rn(m[1], y, a);
-    a = __fmaf_rn(m[2], z, a);
-    a = __fmaf_rn(m[3], w, a);
-    return a;
-}
-// tensor.int() of the reference's CPU path: truncation, INT_MIN when unrepresentable.
-__device__ __forceinline__ int f2i(float v) {
-    if (!(v > -2147483904.0f && v < 2147483648.0f)) return INT_MIN;
-    return (int)v;
-}
 
 __device__ __forceinline__ bool in_frustum(const ovo_camera_t &c, float x, float y, float z) {
     if (!(x >= c.aabb[0] && x <= c.aabb[3] && y >= c.aabb[1] && y <= c.aabb[4] && z >= c.aabb[2] && z <= c.aabb[5]))
@@ -42,13 +24,7 @@ __device__ __forceinline__ bool in_frustum(const ovo_camera_t &c, float x, float
 
 __device__ __forceinline__ void project(const ovo_camera_t &c, float x, float y, float z, float w, float &zc,
                                         int &u, int &v) {
-    float lx = dot4(c.w2c, x, y, z, w), ly = dot4(c.w2c + 4, x, y, z, w);
-    float lz = dot4(c.w2c + 8, x, y, z, w), lw = dot4(c.w2c + 12, x, y, z, w);
-    zc = lz;
-    float cx = __fdiv_rn(lx, lw), cy = __fdiv_rn(ly, lw), cz = __fdiv_rn(lz, lw);
-    float pu = dot3(c.K, cx, cy, cz), pv = dot3(c.K + 3, cx, cy, cz), pw = dot3(c.K + 6, cx, cy, cz);
-    u = f2i(rintf(__fdiv_rn(pu, pw)));
-    v = f2i(rintf(__fdiv_rn(pv, pw)));
+    ::project(c.w2c, c.K, x, y, z, w, zc, u, v);
 }
 
 __device__ __forceinline__ bool depth_match(const ovo_camera_t &c, const float *__restrict__ depth, float zc, int u,

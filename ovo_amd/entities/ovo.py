@@ -769,6 +769,60 @@ class OVO:
         cls, conf = self.clip_generator.classify(self.get_objs_clips(), classes, templates=template, th=th)
         return {"classes": cls.cpu().numpy(), "conf": conf.cpu().numpy()}
 
+    # ------------------------------------------------------------------ view rendering (no reference counterpart but its GUI: visualizer.py:165-181)
+    def _instance_tables(self, device, *columns):
+        """Per-instance values (rows in `self.objects` order, as `get_objs_clips` returns them) as tables on `device` indexed by instance id;
+        ids without an entry hold -1 (integer columns) / 0 (float columns)."""
+        ids = torch.tensor(list(self.objects), dtype=torch.int64, device=device)
+        n_slots = max(self.objects) + 1 if self.objects else 0
+        tables = []
+        for col in columns:
+            col = torch.as_tensor(col).to(device)
+            t = torch.zeros(n_slots, dtype=torch.float32, device=device) if col.is_floating_point() \
+                else torch.full((n_slots,), -1, dtype=torch.int64, device=device)
+            t[ids] = col.to(t.dtype)
+            tables.append(t)
+        return tables
+
+    @torch.no_grad()
+    def render_view(self, map_data, c2w, hw, K=None, radius: int = 1, near: float = 0.05, far: float = float("inf"), colors=None,
+                    classes: Optional[List[str]] = None, template="This is a photo of a {}", th: float = 0.0,
+                    query: Optional[str] = None, context=(), query_th: float = 0.0) -> Dict[str, torch.Tensor]:
+        """The map seen from the pose `c2w` as images of `hw` = (h, w) pixels (utils/render_utils.py: a z-buffered splat of the points, a point
+        covering (2 radius + 1)^2 pixels, depths in [near, far]).  `map_data`: what `slam.get_map()` returns; `K`: the view's intrinsics (default:
+        the ones this OVO was built with).  Always returns
+          "row"   i32[h,w]  the visible map row per pixel, -1 where no point lands        "depth"  f32[h,w]  its camera-frame depth, 0 there
+          "ins"   i32[h,w]  its instance id, -1 where there is no point or it is unassigned
+        and, when asked for,
+          "rgb"   u8[h,w,3]            `colors` given: the mapper's `pcd_colors`, black where no point lands
+          "cls" i64 / "conf" f32       `classes` given: `classify_instances(classes, template, th)` of the pixel's instance (-1 / 0 without one)
+          "heat"  f32[h,w]             `query` given: column 0 of `self.query([query] + list(context))` of the pixel's instance, instances with
+                                       heat <= query_th written as 0 -- the `heat > th` picture of the reference's `_update_query_vis`."""
+        from ..utils import render_utils as R
+        K = self._K_host if K is None else K
+        if K is None:
+            raise ValueError("render_view: no intrinsics (pass K=, or build OVO with cam_intrinsics)")
+        view = R.make_view(c2w, K, int(hw[0]), int(hw[1]), radius=radius, near=near, far=far)
+        pcd, point_ins = map_data[0], map_data[2].reshape(-1)
+        row, depth = R.render_rows(pcd, view)
+        out = {"row": row, "depth": depth}
+        ins_cls = ins_conf = None
+        if classes is not None:
+            info = self.classify_instances(classes, template=template, th=th)
+            ins_cls, ins_conf = self._instance_tables(row.device, info["classes"].astype(np.int64), info["conf"].astype(np.float32))
+        res = R.resolve(row, point_ins=point_ins, point_rgb=colors, ins_cls=ins_cls, ins_val=ins_conf, fill_cls=-1, fill_val=0.0)
+        out["ins"] = res["ins"]
+        if colors is not None:
+            out["rgb"] = res["rgb"]
+        if classes is not None:
+            out["cls"], out["conf"] = res["ins_cls"], res["val"]
+        if query is not None:
+            sim = self.query([query] + list(context))[:, 0].float()
+            heat = torch.where(sim > query_th, sim, torch.zeros_like(sim))           # (NaN -- an instance without a descriptor -- is not > th)
+            table, = self._instance_tables(row.device, heat)
+            out["heat"] = R.resolve(row, point_ins=point_ins, ins_val=table, fill_val=0.0)["val"]
+        return out
+
     # ------------------------------------------------------------------ checkpoint (ovo.py:529-575)
     def capture_dict(self, debug_info: bool) -> Dict[str, Any]:
         scene = {"ins_3d_ids": np.asarray(list(self.objects.keys()))}

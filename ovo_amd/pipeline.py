@@ -606,6 +606,35 @@ class FramePipeline:
         return {"n_points": n_new, "n_dropped": sum(v["pcd_idxs"][1] - v["pcd_idxs"][0] for k, v in old_kfs.items() if k not in self.kfs),
                 "n_keyframes": len(self.kfs), "n_pruned_keyframes": n_pruned}
 
+    # ------------------------------------------------------------------ view rendering
+    def render_view(self, c2w, hw=None, radius: int = 1, dense: bool = True, **kw) -> Dict[str, torch.Tensor]:
+        """`OVO.render_view` of the pipeline's own map from the pose `c2w`, the mapper settled first as `close_loop` settles it: "row", "depth",
+        "ins", "rgb" (the mapper's colours unless `colors=` says otherwise) and whatever `kw` asks for (`classes=`, `query=`, `K=`, `near=`, ...).
+        `hw` defaults to the depth frame size.  `dense` (on a pipeline built with `dense`): also "dense_cls" i64[h,w] / "dense_conf" f32[h,w], the
+        resident dense class map (`DenseMap.dense_cls` / `dense_conf`) read by row, -1 / 0 where no point lands.
+        Several ranks: the map and the instance tables are replicated, so the instance-level outputs work on every rank; the dense arrays are
+        sharded by point, and a sharded dense render is not done -- `dense=True` raises there (render `DenseMap.gather`'s arrays instead).
+        Not with a round pre-queued and not under `emulate`, as `close_loop`."""
+        if self._queued:
+            raise L.OvoHipError("render_view: a round is pre-queued -- step it (or drain()) before the map is rendered")
+        if self.emulate:
+            raise L.OvoHipError("render_view: not under emulate= (a timing stand-in holds no real map)")
+        dense = bool(dense) and self.dense_map is not None
+        if dense and self.world > 1:
+            raise ValueError("render_view: the dense class map is sharded over the ranks -- pass dense=False, or resolve the row image "
+                             "against DenseMap.gather's arrays")
+        from .utils import render_utils as R
+        self.join()
+        self.slam.settle()
+        kw.setdefault("colors", self.slam.pcd_colors)
+        hw = syn.scannet_depth_hw(self.scale) if hw is None else hw
+        out = self.ovo.render_view(self.slam.get_map(), c2w, hw, radius=radius, **kw)
+        if dense:
+            cls, conf = self.dense_map.result(self.slam._n)
+            res = R.resolve(out["row"], point_cls=cls, point_conf=conf, fill_cls=-1, fill_val=0.0)
+            out["dense_cls"], out["dense_conf"] = res["cls"], res["conf"]
+        return out
+
     # ------------------------------------------------------------------ dense map
     @property
     def incremental_query(self) -> bool:
