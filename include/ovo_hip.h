@@ -742,6 +742,62 @@ int ovo_render_resolve(const int32_t *row, int h, int w, int64_t n, const int32_
                        int64_t fill_cls, float fill_val, int32_t *out_ins, uint8_t *out_rgb, int64_t *out_cls, float *out_conf,
                        int64_t *out_ins_cls, float *out_val, ovo_stream_t stream);
 
+/* =============================================================================================
+ * Where the instances are (ABI v19): per-instance extent and moments of the map in one pass, and the boxes of the reference's viewer
+ * (ovo/utils/vis_utils.py:72-87, get_obb / get_obj_and_obb) drawn into a rendered view.
+ * ============================================================================================= */
+
+/* ovo_instance_geometry: xyz f32[n,3], ins i32[n] -> per slot s in [0, n_slots), every output optional (NULL):
+ *   cnt   i32[n_slots]     rows that contribute
+ *   lo,hi f32[n_slots,3]   per-axis minimum / maximum of the contributing rows; +inf / -inf for a slot without one
+ *   sums  f64[n_slots,3]   sum of x, y, z
+ *   prods f64[n_slots,6]   sum of xx, xy, xz, yy, yz, zz, each product taken in f64 of the f32 values (53 >= 2 * 24 bits: exact)
+ * Row i CONTRIBUTES iff 0 <= ins[i] < n_slots and x, y, z are all finite; every other row touches nothing.  Whatever is given is zeroed /
+ * initialised here.
+ * axes f32[n_slots,9] (optional; three row vectors per slot): lo / hi are then taken over c_k = dot3(axes[slot] + 3 k, x, y, z), the left-to-right
+ * chain fl(fl(fl(a0 x) + a1 y) + a2 z) with fused multiply-adds (as ovo_project_points) instead of over the coordinates; cnt, sums and prods do
+ * not change.  axes == NULL: the raw coordinates, no arithmetic on them.
+ * Minima and maxima are taken in the total order of the sign-flipped integer image of the float's bits (b ^ 0x80000000 for b >= 0, ~b otherwise:
+ * -0.0 < +0.0; a NaN that an overflowing chain produces sorts beyond the infinities of its sign) with unsigned integer atomics; cnt is an integer
+ * sum.  cnt, lo and hi are a pure function of the inputs, bit-identical from launch to launch.  (The two images with all payload bits set mark the
+ * empty slot and read back as +inf / -inf; the chain never produces them.)
+ * sums and prods are f64 atomic sums: they depend on the order the partial sums arrive in, in their last bits.  Each is a sum of the slot's n_slot
+ * exact terms in SOME order, so |error| <= (n_slot - 1) * 2^-53 * sum |term| to first order; sums of values that are exact in f64 in every order
+ * (a lattice) are exact and reproducible.
+ * One pass (plus a launch that initialises and one that decodes lo / hi): every workgroup walks a contiguous share of the rows, a lane keeps a
+ * run of equal ids in registers, a workgroup-private LDS table serves the slots below 1024, and every workgroup then issues one atomic per touched
+ * slot and quantity; slots from 1024 on go to global atomics run by run.
+ * Checked before anything is queued (OVO_E_ARG, nothing launched): 0 <= n < 2^31, 1 <= n_slots <= 2^20, xyz / ins null with n > 0, axes given
+ * with neither lo nor hi.  All outputs NULL: a successful no-op.  n == 0 is valid: empty slots. */
+int ovo_instance_geometry(const float *xyz, const int32_t *ins, int64_t n, int n_slots, const float *axes, int32_t *cnt, float *lo, float *hi,
+                          double *sums, double *prods, ovo_stream_t stream);
+
+/* ovo_render_boxes: the 12 edges of each of m boxes as lines of half-width `half_width` pixels -> out_id i32[h,w], out_depth f32[h,w] (optional).
+ *   corners f32[m,8,3] in the world: corner c takes the box's high value on axis k iff bit k of c is set (an oriented box is just other corners)
+ *   box_id i32[m]: what a pixel of box b is written as (any values).   view: w2c, K, near, h, w are used; radius and far are not.
+ * Edges of box b: the pairs (c, c | 1 << a) with bit a clear in c, a-major (a = 0: c = 0, 2, 4, 6; a = 1: c = 0, 1, 4, 5; a = 2: c = 0, 1, 2, 3);
+ * edge index = 12 b + e.  In f32, products and sums rounded one by one except the dot chains:
+ *   endpoints    p = (dot4(w2c row 0, x, y, z, 1), dot4(row 1, ...), dot4(row 2, ...)), camera-frame depth z = p[2]
+ *   near clip    an end is in front iff z >= near (NaN is not).  Neither in front: the edge is dropped.  One in front: the other end becomes
+ *                p0 + t (p1 - p0) with t = (near - z0) / (z1 - z0), all three components
+ *   screen       (X, Y) = (pu / pw, pv / pw), pu, pv, pw = dot3 of K's rows with p: project() without the rounding to pixels;  W = 1 / z
+ *   coverage     pixel (x, y), d = (x - X0, y - Y0), e = (X1 - X0, Y1 - Y0), s = clamp((d . e) / (e . e), 0, 1), s = 0 when e . e == 0;
+ *                covered iff |d - s e|^2 <= half_width^2  (a comparison that NaN fails)
+ *   depth there  z = 1 / (W0 + s (W1 - W0)): perspective-correct
+ *   visible      scene_depth == NULL, or scene_depth[y,x] == 0 (an empty pixel of ovo_render_points), or z <= scene_depth[y,x] + depth_slack
+ * Pixel (y, x) takes the visible covering edge with the smallest key (u64)float_bits(z) << 32 | edge index (z > 0: the nearest edge, the smallest
+ * index among equal depths) and writes out_id = box_id[edge / 12], out_depth = z; with no such edge -1 and 0.  No atomics: the result is a pure
+ * function of the pixel, bit-identical from launch to launch.
+ * Two launches: one thread per edge writes the edge table (screen ends, inverse depths, 2D bounds grown by half_width and a margin, so that they
+ * only ever skip work) into ws; one over 16 x 16 pixel tiles stages the table through LDS 256 edges at a time, keeping the edges whose bounds
+ * meet the tile.  ws: device scratch of ovo_render_boxes_workspace_bytes(m) = 576 m bytes, 16-byte aligned (0 for m outside 1 .. 1024).
+ * Checked before anything is queued (OVO_E_ARG, nothing launched): null view / out_id, h, w >= 1, h * w <= 2^26, h <= 16 * 65535, near > 0,
+ * 0 <= m <= 1024, corners / box_id null with m > 0, 0.5 <= half_width <= 8, depth_slack >= 0 (neither NaN), ws with m > 0.  m == 0 is valid: an
+ * empty image. */
+size_t ovo_render_boxes_workspace_bytes(int m);
+int ovo_render_boxes(const float *corners, const int32_t *box_id, int m, const ovo_view_t *view, float half_width, const float *scene_depth,
+                     float depth_slack, int32_t *out_id, float *out_depth, void *ws, size_t ws_bytes, ovo_stream_t stream);
+
 
 /* =============================================================================================
  * The keyframe chain without host round trips (MI355X extension of a6 / a9; what the reference does with a `.sum()` / vstack

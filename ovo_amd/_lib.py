@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "lib", "libovo_hip.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 E_UNSUPPORTED = -3          # OVO_E_UNSUPPORTED: the entry point does not cover this shape; the caller takes its general path
 
 
@@ -233,6 +233,9 @@ _SIGNATURES = {
     "ovo_render_workspace_bytes": (_SZ, [_I32, _I32]),
     "ovo_render_points": (_I32, [_P, _I64, C.POINTER(View), _P, _P, _P, _SZ, _P]),
     "ovo_render_resolve": (_I32, [_P, _I32, _I32, _I64, _P, _P, C.c_uint32, _P, _P, _P, _P, _I32, _I64, _F32, _P, _P, _P, _P, _P, _P, _P]),
+    "ovo_instance_geometry": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "ovo_render_boxes_workspace_bytes": (_SZ, [_I32]),
+    "ovo_render_boxes": (_I32, [_P, _P, _I32, C.POINTER(View), _F32, _P, _F32, _P, _P, _P, _SZ, _P]),
     "ovo_sam_i2t_attention": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_sam_t2i_attention": (_I32, [_P, _P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_paint_segmap": (_I32, [_P, _I32, _I64, _P, _P]),

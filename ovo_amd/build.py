@@ -27,6 +27,7 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno
 # packed form pays two v_mov per v_pk_fma to line them up: FC1 + GELU (57344, 1792, 448) 135.1 -> 131.1 us, (16156, 4096, 1024) 133.6 -> 131.0, the other
 # epilogues unchanged (two alternating rounds of both builds in one session, tools/gemm_bench.py); results are bit-identical (the same IEEE operations)
 EXTRA = {"geometry.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=off"],   # render.hip shares geometry.hip's projection (csrc/projection.h)
+         "insgeo.hip": ["-ffp-contract=off"],      # f64 products of f32 values are exact and stay products; the axis chains are projection.h's
          "evalknn.hip": ["-ffp-contract=off"], "mlp_stream.hip": ["-fno-slp-vectorize"], "gemm_stream.hip": ["-fno-slp-vectorize"],
          "winattn.hip": ["-fno-slp-vectorize"], "gemm8p.hip": ["-fno-slp-vectorize"],
          "neck_stream.hip": ["-fno-slp-vectorize"],  # mlp_stream.hip's sibling: the same flags

@@ -6,6 +6,7 @@
 //                     (2 r + 1)^2 footprint touches the image, atomicMin(key[pixel], float_bits(zc) << 32 | row) over the footprint
 //   k_render_decode   key image -> row i32[h,w] (-1: empty) and depth f32[h,w] (0: empty)
 //   k_render_resolve  row image -> per-point / per-instance attributes, a pure gather
+//   k_box_edges       the 12 edges of every box -> a table of clipped screen segments;   k_box_pixels  per pixel the nearest visible edge (no atomics)
 // zc >= near > 0, so the float's bits order like its value: the smallest key is the nearest point, the smallest row among equal depths.  The
 // minimum does not depend on the order the atomics arrive in: the result is a pure function of the inputs, bit-identical from launch to launch.
 // This file is compiled with -ffp-contract=off (projection.h).
@@ -107,7 +108,139 @@ int render_grid(int64_t n) {
     return ovo_grid((n + RENDER_ROWS - 1) / RENDER_ROWS, 256, cap > 0 ? cap : 256 * 8);
 }
 
+// ---- boxes: the 12 edges of every box as thick lines, depth-tested against a rendered view (ovo_render_boxes) ----
+constexpr int BOX_MAX = 1024;
+constexpr int BOX_CHUNK = 256;                            // edges staged through LDS at a time: one per thread of a tile
+constexpr int BOX_TILE_W = 16, BOX_TILE_H = 16;           // a workgroup's pixels; a wave covers a 16 x 4 strip of them
+
+// One edge after the set-up launch: the screen segment from (x0, y0) along (ex, ey), the inverse depths at its ends, and the bounds that every
+// pixel within half_width of it lies inside.  A dropped edge has bounds that no tile meets (bx0 > bx1).
+struct BoxEdge { float x0, y0, w0, ex, ey, dw, ee, bx0, by0, bx1, by1, pad; };
+
+__global__ void __launch_bounds__(256) k_box_edges(const float *__restrict__ corners, int m, ovo_view_t vw, float half_width, BoxEdge *__restrict__ table) {
+    const int edge = blockIdx.x * blockDim.x + threadIdx.x;
+    if (edge >= 12 * m) return;
+    const int box = edge / 12, e = edge % 12, axis = e / 4, j = e % 4;
+    const int low = j & ((1 << axis) - 1), c0 = ((j - low) << 1) | low, c1 = c0 | (1 << axis);      // the j-th corner with bit `axis` clear, and its partner
+    float p[2][3];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const float *q = corners + 24 * (int64_t)box + 3 * (s ? c1 : c0);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[s][k] = dot4(vw.w2c + 4 * k, q[0], q[1], q[2], 1.0f);
+    }
+    BoxEdge out;
+    out.bx0 = out.by0 = 1.0f; out.bx1 = out.by1 = -1.0f;                                            // (dropped until proven otherwise)
+    out.x0 = out.y0 = out.w0 = out.ex = out.ey = out.dw = out.ee = out.pad = 0.0f;
+    const bool in0 = p[0][2] >= vw.near, in1 = p[1][2] >= vw.near;                                  // (NaN is not in front)
+    if (in0 || in1) {
+        if (!(in0 && in1)) {                                                                        // cut at the near plane
+            const int s = in0 ? 1 : 0;                                                              // the end that is behind it
+            const float t = (vw.near - p[0][2]) / (p[1][2] - p[0][2]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) p[s][k] = p[0][k] + t * (p[1][k] - p[0][k]);
+        }
+        float sx[2], sy[2], iw[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const float pu = dot3(vw.K, p[s][0], p[s][1], p[s][2]), pv = dot3(vw.K + 3, p[s][0], p[s][1], p[s][2]);
+            const float pw = dot3(vw.K + 6, p[s][0], p[s][1], p[s][2]);
+            sx[s] = pu / pw; sy[s] = pv / pw; iw[s] = 1.0f / p[s][2];
+        }
+        out.x0 = sx[0]; out.y0 = sy[0]; out.w0 = iw[0];
+        out.ex = sx[1] - sx[0]; out.ey = sy[1] - sy[0]; out.dw = iw[1] - iw[0];
+        out.ee = out.ex * out.ex + out.ey * out.ey;
+        // grown by half_width, one pixel and a rounding's worth more: the bounds only ever skip work, never a covered pixel
+        const float g = half_width + 1.0f;
+        float lo_x = fminf(sx[0], sx[1]) - g, hi_x = fmaxf(sx[0], sx[1]) + g, lo_y = fminf(sy[0], sy[1]) - g, hi_y = fmaxf(sy[0], sy[1]) + g;
+        out.bx0 = lo_x - fabsf(lo_x) * 1e-6f; out.bx1 = hi_x + fabsf(hi_x) * 1e-6f;
+        out.by0 = lo_y - fabsf(lo_y) * 1e-6f; out.by1 = hi_y + fabsf(hi_y) * 1e-6f;
+        if (!(out.bx0 <= out.bx1 && out.by0 <= out.by1)) { out.bx0 = out.by0 = 1.0f; out.bx1 = out.by1 = -1.0f; }      // NaN: covers nothing anyway
+    }
+    table[edge] = out;
+}
+
+// One pixel per thread, 16 x 16 pixels per workgroup.  The table is staged through LDS BOX_CHUNK edges at a time, only the edges whose bounds
+// meet the tile; every wave then walks the same short list.  The order of the list does not matter: the pixel keeps the smallest key.
+__global__ void __launch_bounds__(256) k_box_pixels(const BoxEdge *__restrict__ table, int n_edges, const int32_t *__restrict__ box_id, int h, int w,
+                                                    float hw2, const float *__restrict__ scene, float slack, int32_t *__restrict__ out_id,
+                                                    float *__restrict__ out_depth) {
+    __shared__ BoxEdge s_edge[BOX_CHUNK];
+    __shared__ int s_index[BOX_CHUNK];
+    __shared__ int s_count;
+    const int tid = threadIdx.x;
+    const int tx0 = blockIdx.x * BOX_TILE_W, ty0 = blockIdx.y * BOX_TILE_H;
+    const int x = tx0 + (tid & 15), y = ty0 + (tid >> 4);
+    const bool inside = x < w && y < h;
+    const float fx = (float)x, fy = (float)y;
+    const float tile_x0 = (float)tx0, tile_x1 = (float)(tx0 + BOX_TILE_W - 1), tile_y0 = (float)ty0, tile_y1 = (float)(ty0 + BOX_TILE_H - 1);
+    const float sc = inside && scene ? scene[(int64_t)y * w + x] : 0.0f;
+    const bool open = !scene || sc == 0.0f;                                      // nothing to be hidden behind
+    const float limit = sc + slack;
+    unsigned long long best = KEY_EMPTY;
+    for (int base = 0; base < n_edges; base += BOX_CHUNK) {
+        __syncthreads();                                                         // (the previous chunk has been read)
+        if (tid == 0) s_count = 0;
+        __syncthreads();
+        if (base + tid < n_edges) {
+            const BoxEdge e = table[base + tid];
+            if (e.bx0 <= tile_x1 && e.bx1 >= tile_x0 && e.by0 <= tile_y1 && e.by1 >= tile_y0) {
+                const int k = atomicAdd(&s_count, 1);
+                s_edge[k] = e; s_index[k] = base + tid;
+            }
+        }
+        __syncthreads();
+        const int count = s_count;
+        for (int k = 0; k < count; ++k) {
+            const BoxEdge &e = s_edge[k];
+            const float dx = fx - e.x0, dy = fy - e.y0;
+            float s = e.ee > 0.0f ? (dx * e.ex + dy * e.ey) / e.ee : 0.0f;
+            s = s < 0.0f ? 0.0f : (s > 1.0f ? 1.0f : s);
+            const float rx = dx - s * e.ex, ry = dy - s * e.ey;
+            if (!(rx * rx + ry * ry <= hw2)) continue;
+            const float z = 1.0f / (e.w0 + s * e.dw);
+            if (!(open || z <= limit)) continue;
+            const unsigned long long key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned int)s_index[k];
+            best = key < best ? key : best;
+        }
+    }
+    if (!inside) return;
+    const bool hit = best != KEY_EMPTY;
+    out_id[(int64_t)y * w + x] = hit ? box_id[(unsigned int)best / 12u] : -1;
+    if (out_depth) out_depth[(int64_t)y * w + x] = hit ? __uint_as_float((unsigned int)(best >> 32)) : 0.0f;
+}
+
 }  // namespace
+
+extern "C" size_t ovo_render_boxes_workspace_bytes(int m) {
+    return m > 0 && m <= BOX_MAX ? sizeof(BoxEdge) * 12 * (size_t)m : 0;
+}
+
+extern "C" int ovo_render_boxes(const float *corners, const int32_t *box_id, int m, const ovo_view_t *view, float half_width, const float *scene_depth,
+                                float depth_slack, int32_t *out_id, float *out_depth, void *ws, size_t ws_bytes, ovo_stream_t stream) {
+    // everything is checked HERE, before anything is queued
+    OVO_REQUIRE(view && out_id, "null pointer");
+    const ovo_view_t vw = *view;
+    OVO_REQUIRE(vw.h >= 1 && vw.w >= 1 && (int64_t)vw.h * vw.w <= RENDER_MAX_PIXELS, "image size outside 1 .. 2^26 pixels");
+    OVO_REQUIRE(vw.h <= BOX_TILE_H * 65535, "image higher than 16 * 65535 rows");                   // (grid.y)
+    OVO_REQUIRE(vw.near > 0.0f, "near must be > 0");                                                // (NaN fails)
+    OVO_REQUIRE(m >= 0 && m <= BOX_MAX, "m outside 0 .. 1024");
+    OVO_REQUIRE(m == 0 || (corners && box_id), "null corners or box_id");
+    OVO_REQUIRE(half_width >= 0.5f && half_width <= 8.0f, "half_width outside 0.5 .. 8");
+    OVO_REQUIRE(depth_slack >= 0.0f, "depth_slack must be >= 0");
+    OVO_REQUIRE(m == 0 || (ws && ws_bytes >= ovo_render_boxes_workspace_bytes(m) && ((uintptr_t)ws & 15) == 0),
+                "workspace missing, too small or not 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    BoxEdge *table = (BoxEdge *)ws;
+    if (m > 0) {
+        k_box_edges<<<(12 * m + 255) / 256, 256, 0, st>>>(corners, m, vw, half_width, table);
+        OVO_CHECK_LAUNCH();
+    }
+    const dim3 grid((vw.w + BOX_TILE_W - 1) / BOX_TILE_W, (vw.h + BOX_TILE_H - 1) / BOX_TILE_H);
+    k_box_pixels<<<grid, 256, 0, st>>>(table, 12 * m, box_id, vw.h, vw.w, half_width * half_width, scene_depth, depth_slack, out_id, out_depth);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
 
 extern "C" size_t ovo_render_workspace_bytes(int h, int w) {
     return h > 0 && w > 0 ? sizeof(unsigned long long) * (size_t)h * (size_t)w : 0;

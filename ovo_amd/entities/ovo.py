@@ -787,7 +787,8 @@ class OVO:
     @torch.no_grad()
     def render_view(self, map_data, c2w, hw, K=None, radius: int = 1, near: float = 0.05, far: float = float("inf"), colors=None,
                     classes: Optional[List[str]] = None, template="This is a photo of a {}", th: float = 0.0,
-                    query: Optional[str] = None, context=(), query_th: float = 0.0) -> Dict[str, torch.Tensor]:
+                    query: Optional[str] = None, context=(), query_th: float = 0.0, boxes=None, box_width: float = 1.0, oriented: bool = False,
+                    depth_slack: float = 0.02) -> Dict[str, torch.Tensor]:
         """The map seen from the pose `c2w` as images of `hw` = (h, w) pixels (utils/render_utils.py: a z-buffered splat of the points, a point
         covering (2 radius + 1)^2 pixels, depths in [near, far]).  `map_data`: what `slam.get_map()` returns; `K`: the view's intrinsics (default:
         the ones this OVO was built with).  Always returns
@@ -797,7 +798,12 @@ class OVO:
           "rgb"   u8[h,w,3]            `colors` given: the mapper's `pcd_colors`, black where no point lands
           "cls" i64 / "conf" f32       `classes` given: `classify_instances(classes, template, th)` of the pixel's instance (-1 / 0 without one)
           "heat"  f32[h,w]             `query` given: column 0 of `self.query([query] + list(context))` of the pixel's instance, instances with
-                                       heat <= query_th written as 0 -- the `heat > th` picture of the reference's `_update_query_vis`."""
+                                       heat <= query_th written as 0 -- the `heat > th` picture of the reference's `_update_query_vis`.
+          "box" i32[h,w] / "box_depth" f32[h,w]   `boxes` given: the 12 edges of the instances' boxes (`instance_boxes`; `oriented`: the PCA-aligned
+                                       ones), `2 box_width` pixels wide -- the instance id of the nearest visible edge (-1: none) and its depth (0).
+                                       `boxes`: "all", "query" (the instances whose heat is > query_th; needs `query=`) or a list of instance ids;
+                                       instances without points have no box.  An edge is hidden where it lies more than `depth_slack` behind
+                                       the view's own "depth", so a box hugging its object's surface shows through the splat."""
         from ..utils import render_utils as R
         K = self._K_host if K is None else K
         if K is None:
@@ -816,12 +822,87 @@ class OVO:
             out["rgb"] = res["rgb"]
         if classes is not None:
             out["cls"], out["conf"] = res["ins_cls"], res["val"]
+        if boxes is not None and isinstance(boxes, str) and boxes not in ("all", "query"):
+            raise ValueError(f"render_view: boxes={boxes!r} (\"all\", \"query\" or a list of instance ids)")
+        if isinstance(boxes, str) and boxes == "query" and query is None:
+            raise ValueError("render_view: boxes=\"query\" needs query=")
+        sim = None
         if query is not None:
             sim = self.query([query] + list(context))[:, 0].float()
             heat = torch.where(sim > query_th, sim, torch.zeros_like(sim))           # (NaN -- an instance without a descriptor -- is not > th)
             table, = self._instance_tables(row.device, heat)
             out["heat"] = R.resolve(row, point_ins=point_ins, ins_val=table, fill_val=0.0)["val"]
+        if boxes is not None:
+            from ..utils import instance_geometry as IG
+            geo = self.instance_boxes(map_data, oriented=oriented)
+            ids = geo["ids"]
+            if isinstance(boxes, str):
+                want = torch.ones_like(ids, dtype=torch.bool) if boxes == "all" else (sim > query_th).to(ids.device)
+            else:
+                want = torch.isin(ids, torch.as_tensor(list(boxes), dtype=torch.int64, device=ids.device))
+            keep = want & (geo["count"] > 0)
+            corners = IG.box_corners(geo["min"][keep], geo["max"][keep], geo["R"][keep] if oriented else None)
+            out["box"], out["box_depth"] = R.render_boxes(corners, ids[keep].to(torch.int32), view, half_width=box_width, scene_depth=depth,
+                                                          depth_slack=depth_slack)
         return out
+
+    # ------------------------------------------------------------------ where the instances are (the viewer's boxes: vis_utils.py:72-87)
+    @torch.no_grad()
+    def instance_boxes(self, map_data, oriented: bool = False) -> Dict[str, torch.Tensor]:
+        """The box of every instance, rows in `self.objects` order (the row order of `get_objs_clips`), on the map's device: "ids" i64[N], "count"
+        i32[N] map points of the instance, "center" f32[N,3] (the middle of the box), "min" / "max" f32[N,3] and, with `oriented`, "R" f32[N,3,3] --
+        rows the PCA axes of the instance's points (`instance_geometry.pca_axes`); "min" / "max" are then extents along them and "center" is back
+        in the world -- and "extent" f32[N,3] = max - min.  An instance without points has count 0 and NaN boxes.  One pass over the map
+        (`ovo_instance_geometry`), two when oriented."""
+        from ..utils import instance_geometry as IG
+        pcd, point_ins = map_data[0], map_data[2].reshape(-1)
+        dev = pcd.device
+        ids = torch.tensor(list(self.objects), dtype=torch.int64, device=dev)
+        if not self.objects:
+            empty = torch.zeros((0, 3), dtype=torch.float32, device=dev)
+            out = {"ids": ids, "count": torch.zeros(0, dtype=torch.int32, device=dev), "center": empty, "min": empty.clone(), "max": empty.clone()}
+            if oriented:
+                out.update(R=torch.zeros((0, 3, 3), dtype=torch.float32, device=dev), extent=empty.clone())
+            return out
+        n_slots = max(self.objects) + 1
+        if oriented:
+            g = IG.instance_geometry(pcd, point_ins, n_slots, oriented=True)
+            lo, hi, R = g["min_o"][ids], g["max_o"][ids], g["R"][ids]
+        else:
+            g = IG.geometry_pass(pcd, point_ins, n_slots, moments=False)
+            lo, hi, R = g["min"][ids], g["max"][ids], None
+        count = g["count"][ids]
+        nan = torch.full_like(lo, float("nan"))
+        has = (count > 0)[:, None]
+        lo, hi = torch.where(has, lo, nan), torch.where(has, hi, nan)
+        mid = (lo + hi) * 0.5
+        out = {"ids": ids, "count": count, "center": mid if R is None else (mid[:, :, None] * R).sum(1), "min": lo, "max": hi}
+        if oriented:
+            out.update(R=R, extent=hi - lo)
+        return out
+
+    @torch.no_grad()
+    def locate(self, map_data, queries: List[str], templates=['{}'], top_k: int = 5, th: float = 0.0, oriented: bool = False):
+        """"Where is the X?": per query a list of at most `top_k` dicts {"ins_id", "score", "center", "min", "max", "n_points"} (+ "R", "extent" with
+        `oriented`; boxes as `instance_boxes` returns them, as numpy) of the instances whose `self.query(queries, templates)` score is > th, by
+        descending score, ties to the smaller id.  An instance without a descriptor (NaN score) or without map points is never listed."""
+        sim = self.query(list(queries), templates=templates).float().cpu().numpy()
+        geo = {k: v.cpu().numpy() for k, v in self.instance_boxes(map_data, oriented=oriented).items()}
+        ids, found = geo["ids"], []
+        for q in range(len(queries)):
+            score = sim[:, q]
+            with np.errstate(invalid="ignore"):
+                ok = np.nonzero((score > th) & (geo["count"] > 0))[0]               # (NaN is not > th)
+            ok = ok[np.lexsort((ids[ok], -score[ok]))][:max(int(top_k), 0)]
+            hits = []
+            for r in ok:
+                hit = {"ins_id": int(ids[r]), "score": float(score[r]), "center": geo["center"][r], "min": geo["min"][r], "max": geo["max"][r],
+                       "n_points": int(geo["count"][r])}
+                if oriented:
+                    hit.update(R=geo["R"][r], extent=geo["extent"][r])
+                hits.append(hit)
+            found.append(hits)
+        return found
 
     # ------------------------------------------------------------------ checkpoint (ovo.py:529-575)
     def capture_dict(self, debug_info: bool) -> Dict[str, Any]:

@@ -610,6 +610,7 @@ class FramePipeline:
     def render_view(self, c2w, hw=None, radius: int = 1, dense: bool = True, **kw) -> Dict[str, torch.Tensor]:
         """`OVO.render_view` of the pipeline's own map from the pose `c2w`, the mapper settled first as `close_loop` settles it: "row", "depth",
         "ins", "rgb" (the mapper's colours unless `colors=` says otherwise) and whatever `kw` asks for (`classes=`, `query=`, `K=`, `near=`, ...).
+        `boxes=` / `box_width=` / `oriented=` draw the instances' boxes ("box", "box_depth").
         `hw` defaults to the depth frame size.  `dense` (on a pipeline built with `dense`): also "dense_cls" i64[h,w] / "dense_conf" f32[h,w], the
         resident dense class map (`DenseMap.dense_cls` / `dense_conf`) read by row, -1 / 0 where no point lands.
         Several ranks: the map and the instance tables are replicated, so the instance-level outputs work on every rank; the dense arrays are
@@ -634,6 +635,25 @@ class FramePipeline:
             res = R.resolve(out["row"], point_cls=cls, point_conf=conf, fill_cls=-1, fill_val=0.0)
             out["dense_cls"], out["dense_conf"] = res["cls"], res["conf"]
         return out
+
+    def _settled_map(self, what: str):
+        """`slam.get_map()` with the mapper settled first, as `render_view` settles it, and with the same refusals."""
+        if self._queued:
+            raise L.OvoHipError(f"{what}: a round is pre-queued -- step it (or drain()) before the map is read")
+        if self.emulate:
+            raise L.OvoHipError(f"{what}: not under emulate= (a timing stand-in holds no real map)")
+        self.join()
+        self.slam.settle()
+        return self.slam.get_map()
+
+    def instance_boxes(self, oriented: bool = False) -> Dict[str, torch.Tensor]:
+        """`OVO.instance_boxes` of the pipeline's own map.  The map and the instance tables are replicated: works on every rank.  Not with a round
+        pre-queued and not under `emulate`, as `render_view`."""
+        return self.ovo.instance_boxes(self._settled_map("instance_boxes"), oriented=oriented)
+
+    def locate(self, queries, **kw):
+        """`OVO.locate` of the pipeline's own map (`templates=`, `top_k=`, `th=`, `oriented=`); on every rank, with `instance_boxes`' refusals."""
+        return self.ovo.locate(self._settled_map("locate"), queries, **kw)
 
     # ------------------------------------------------------------------ dense map
     @property

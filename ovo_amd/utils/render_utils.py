@@ -89,3 +89,31 @@ def resolve(row: torch.Tensor, *, point_ins: Optional[torch.Tensor] = None, poin
                                         L.ptr(out.get("rgb")), L.ptr(out.get("cls")), L.ptr(out.get("conf")), L.ptr(out.get("ins_cls")),
                                         L.ptr(out.get("val")), L.stream()))
     return out
+
+
+def render_boxes(corners: torch.Tensor, box_id: torch.Tensor, view: L.View, half_width: float = 1.0, scene_depth: Optional[torch.Tensor] = None,
+                 depth_slack: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(box i32[h,w], box_depth f32[h,w]) of the 12 edges of every box, drawn `2 half_width` pixels wide into `view` (`ovo_render_boxes`; its
+    `radius` and `far` are not used): per pixel the `box_id` of the nearest visible edge (-1: none) and its depth (0: none).  corners
+    f32[m,8,3] in the world, in the order of `instance_geometry.box_corners`; box_id i32[m].  `scene_depth` f32[h,w] (the "depth" of
+    `render_rows` through the same view): an edge is hidden where it lies more than `depth_slack` behind a non-empty scene pixel."""
+    corners = L.dev(corners, torch.float32, "corners")
+    if corners.dim() != 3 or tuple(corners.shape[1:]) != (8, 3):
+        raise L.OvoHipError(f"corners must be [m, 8, 3] (got {tuple(corners.shape)})")
+    box_id = L.dev(box_id.reshape(-1), torch.int32, "box_id")
+    m, dev = corners.shape[0], corners.device
+    if box_id.shape[0] != m or box_id.device != dev:
+        raise L.OvoHipError(f"box_id: {box_id.shape[0]} ids on {box_id.device} for {m} boxes on {dev}")
+    h, w = int(view.h), int(view.w)
+    if scene_depth is not None:
+        scene_depth = L.dev(scene_depth, torch.float32, "scene_depth")
+        if tuple(scene_depth.shape) != (h, w) or scene_depth.device != dev:
+            raise L.OvoHipError(f"scene_depth must be [{h}, {w}] on {dev} (got {tuple(scene_depth.shape)} on {scene_depth.device})")
+    lib = L.load()
+    nb = int(lib.ovo_render_boxes_workspace_bytes(m))
+    out_id = torch.empty((max(h, 0), max(w, 0)), dtype=torch.int32, device=dev)
+    out_depth = torch.empty((max(h, 0), max(w, 0)), dtype=torch.float32, device=dev)
+    ws = L.workspace(nb, dev) if nb else None
+    L.check(lib.ovo_render_boxes(L.ptr(corners), L.ptr(box_id), m, C.byref(view), float(half_width), L.ptr(scene_depth), float(depth_slack),
+                                 L.ptr(out_id), L.ptr(out_depth), L.ptr(ws), nb, L.stream()))
+    return out_id, out_depth
