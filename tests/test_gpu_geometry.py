@@ -2,6 +2,8 @@
 
 Integer and index outputs (and fp32 coordinates produced by the FMA chain) are compared bit-exactly.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -246,29 +248,54 @@ def test_many_masks_per_keyframe_device_vs_host_decisions(mode):
     assert max(n_masks) > 64, n_masks
 
 
-def _small_keyframe(call):
-    """One keyframe of 30 x 36 depth pixels (1080: not a multiple of 16, so `ovo_keyframe_step` hands it to the single steps) at ds = 1 over a map of 356
-    points in front of the camera, those of the top ten rows on the depth surface; 3 masks (a 1 x 3 grid seg map), no binary masks.  The two steps are filled
-    the way `VanillaMapper.map_launch(defer=True)` and `OVO.track_launch(defer=True)` fill them and handed to `call`; returns every output."""
+@functools.lru_cache(maxsize=None)
+def _small_keyframe_inputs(h=30, w=36, ds=1):
+    """The inputs of `_small_keyframe`, on the host: the 30 x 36 fixture, scaled with the frame so that the depth keeps its range, the camera its field
+    of view and the map a point on every third pixel -> (K, depth, rgb, map points, seg map)."""
+    K = np.array([[30 * w / 36, 0, (w - 1) / 2], [0, 30 * w / 36, (h - 1) / 2], [0, 0, 1]], np.float32)
+    v, u = np.mgrid[:h, :w]
+    depth = (2.0 + 0.02 * (u * (36 / w)) + 0.03 * (v * (30 / h))).astype(np.float32)
+    depth[4:7, 5:9] = 0                                                          # a hole
+    old = ((u + v) % 3 == 0) & (depth > 0)
+    z = depth[old] + np.where(v[old] < h // 3, 0.0, 0.3).astype(np.float32)
+    pts = np.stack([(u[old] - K[0, 2]) / K[0, 0] * z, (v[old] - K[1, 2]) / K[1, 1] * z, z], 1).astype(np.float32)
+    rgb = np.random.default_rng(2).integers(0, 256, (h, w, 3), dtype=np.uint8)
+    return K, depth, rgb, pts, np.minimum(u // (w // 3), 2).astype(np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def _small_keyframe_map_reference(h=30, w=36, ds=1):
+    """The oracle's map half of `_small_keyframe`: the pixels the fixture's own map points explain at 0.03 (frustum cull -> match), then the eroded,
+    sub-sampled back-projection -> (explained u8[h,w], appended xyz, appended colours)."""
+    from oracle import geometry as OG
+    K, depth, rgb, pts, _ = _small_keyframe_inputs(h, w, ds)
+    pose = np.eye(4, dtype=np.float32)
+    fids = OG.frustum_point_ids(pts, OG.frustum_corners(depth, pose, K))
+    _, uv = OG.match(depth, torch.linalg.inv(torch.from_numpy(pose)).numpy(), np.ascontiguousarray(pts[fids]), K, 0.03)
+    explained = np.zeros((h, w), np.uint8)
+    explained[uv[:, 1], uv[:, 0]] = 1
+    xyz, col = OG.backproject(depth, rgb, explained, K, pose, erode=True, ds=ds)
+    return explained, xyz, col
+
+
+def _small_keyframe(call, h=30, w=36, ds=1):
+    """One keyframe of h x w depth pixels (30 x 36 = 1080: not a multiple of 16, so `ovo_keyframe_step` hands it to the single steps) at stride ds over a map
+    with a point in front of every third pixel (356 at 30 x 36), those of the top third of the rows on the depth surface; 3 masks (a 1 x 3 grid seg map), no
+    binary masks.  The two steps are filled the way `VanillaMapper.map_launch(defer=True)` and `OVO.track_launch(defer=True)` fill them and handed to `call`;
+    returns every output."""
     from ovo_amd import _lib as L
     from ovo_amd.utils import geometry_utils as G
     lib = L.load()
-    h, w, n_masks, next_ins = 30, 36, 3, 3
-    K = np.array([[30, 0, 17.5], [0, 30, 14.5], [0, 0, 1]], np.float32)
-    v, u = np.mgrid[:h, :w]
-    depth = (2.0 + 0.02 * u + 0.03 * v).astype(np.float32)
-    depth[4:7, 5:9] = 0                                                          # a hole
-    old = ((u + v) % 3 == 0) & (depth > 0)
-    n0, n_sub = int(old.sum()), h * w
-    z = depth[old] + np.where(v[old] < 10, 0.0, 0.3).astype(np.float32)
-    pts = np.stack([(u[old] - K[0, 2]) / K[0, 0] * z, (v[old] - K[1, 2]) / K[1, 1] * z, z], 1).astype(np.float32)
+    n_masks, next_ins = 3, 3
+    K, depth, rgb, pts, seg_host = _small_keyframe_inputs(h, w, ds)
+    n0, n_sub = pts.shape[0], -(-h // ds) * -(-w // ds)
     cap = n0 + n_sub
     xyz, ids, ins = torch.zeros((cap, 3), device=DEV), torch.full((cap,), -1, dtype=torch.int32, device=DEV), torch.full((cap,), -1, dtype=torch.int32, device=DEV)
     rgb_out = torch.zeros((cap, 3), dtype=torch.uint8, device=DEV)
     xyz[:n0], ids[:n0] = _t(pts), torch.arange(n0, dtype=torch.int32, device=DEV)
     ins[:n0] = _t(np.where(np.arange(n0) % 4 == 0, -1, np.arange(n0) % next_ins).astype(np.int32))
     state = torch.tensor([n0, n0, 0, 0], dtype=torch.int64, device=DEV)          # {n, next point id, flags, ticket}
-    d_depth, d_rgb = _t(depth), _t(np.random.default_rng(2).integers(0, 256, (h, w, 3), dtype=np.uint8))
+    d_depth, d_rgb = _t(depth), _t(rgb)
     pose, K_host = torch.eye(4), torch.from_numpy(K)
     near, far = G.depth_range(depth)
     map_ring, track_ring = L.PinnedRing(4, np.int64, 4), L.PinnedRing(8 + 6 * n_masks, np.int32, 4)
@@ -279,7 +306,7 @@ def _small_keyframe(call):
     a.cam = G.frame_camera(near, far, h, w, pose, K_host, 0.03)
     a.K = (L.C.c_float * 9)(*K.reshape(-1).tolist())
     a.c2w[:] = pose.reshape(-1).tolist()
-    a.ds, a.erode, a.n_upper = 1, 1, n0
+    a.ds, a.erode, a.n_upper = ds, 1, n0
     explained = torch.empty(h * w, dtype=torch.uint8, device=DEV)
     map_ws = torch.empty(lib.ovo_compact_workspace_bytes(n_sub) + 8, dtype=torch.uint8, device=DEV)
     a.explained, a.ws, a.ws_bytes = explained.data_ptr(), map_ws.data_ptr(), map_ws.numel()
@@ -291,7 +318,7 @@ def _small_keyframe(call):
     t.cam = G.frame_camera(near, far, h, w, pose, K_host, 0.05)
     scratch = torch.empty(h * w, dtype=torch.float32, device=DEV)
     t.depth, t.filter_depth, t.depth_scratch = d_depth.data_ptr(), 1, scratch.data_ptr()
-    seg = _t((u // 12).astype(np.int32))
+    seg = _t(seg_host)
     t.seg_map, t.seg_h, t.seg_w = seg.data_ptr(), h, w
     t.masks, t.n_masks, t.pixels = None, n_masks, 0
     t.ratio = L.Ratio(0, 1.0, 1.0, 0)
@@ -305,7 +332,7 @@ def _small_keyframe(call):
     t.seq, t.result_host = track_ring.next()
     call(lib, a, t)
     torch.cuda.synchronize()
-    return {"xyz": xyz.cpu(), "ids": ids.cpu(), "ins": ins.cpu(), "rgb": rgb_out.cpu(), "point_seg": point_seg.cpu(), "state": state.cpu(),
+    return {"xyz": xyz.cpu(), "ids": ids.cpu(), "ins": ins.cpu(), "rgb": rgb_out.cpu(), "point_seg": point_seg.cpu(), "state": state.cpu(), "explained": explained.cpu(),
             "next_ins": d_next.cpu(), "map_result": torch.from_numpy(map_ring.wait(a.seq).copy()), "track_result": torch.from_numpy(track_ring.wait(t.seq).copy())}
 
 
@@ -327,6 +354,46 @@ def test_keyframe_step_on_a_shape_it_hands_on_equals_the_two_single_steps():
     res = two["track_result"]
     assert int(res[0]) == 1 and int(res[8::6].sum()) > 150 and (res[12::6] >= 0).all()       # every mask matched points and got an instance
     assert (two["ins"][356:n_after] >= 0).sum() > 100                                            # ... which the new points received
+    _assert_map_half_equals_oracle(two, 30, 36, 1)                                               # and not only each other: the oracle's explained pixels and append
+
+
+def _assert_map_half_equals_oracle(out, h, w, ds):
+    """The map half of `_small_keyframe`'s outputs against `_small_keyframe_map_reference`: explained pixels, appended rows, ids, colours, state, result block;
+    the map's old rows and the rows past the append are untouched."""
+    _, _, _, pts, _ = _small_keyframe_inputs(h, w, ds)
+    explained, ref_xyz, ref_rgb = _small_keyframe_map_reference(h, w, ds)
+    n0, m = pts.shape[0], ref_xyz.shape[0]
+    assert out["map_result"].tolist() == [1, m, n0 + m, n0 + m] and out["state"].tolist() == [n0 + m, n0 + m, 0, 0]
+    assert np.array_equal(out["explained"].numpy().reshape(h, w), explained)
+    assert np.array_equal(out["xyz"][:n0].numpy(), pts) and np.array_equal(out["xyz"][n0:n0 + m].numpy(), ref_xyz) and not out["xyz"][n0 + m:].any()
+    assert np.array_equal(out["ids"].numpy(), np.concatenate([np.arange(n0 + m), np.full(out["ids"].shape[0] - n0 - m, -1)]).astype(np.int32))
+    assert np.array_equal(out["rgb"][n0:n0 + m].numpy(), ref_rgb) and not out["rgb"][:n0].any() and not out["rgb"][n0 + m:].any()
+    assert (out["ins"][n0 + m:] == -1).all()
+
+
+@pytest.mark.parametrize("h, w", [(256, 512), (258, 512)])
+def test_keyframe_step_at_the_scan_boundary_equals_single_steps_and_oracle(h, w):
+    """ds = 1.  256 x 512: 131 072 sub-sampled pixels, exactly the 2048 flag words `k_kf_emit` scans in LDS, and a multiple of 16 pixels: the merged form.
+    258 x 512: 2064 words: `ovo_keyframe_step` hands on to the single steps, whose scan takes three launches.  (The library does not report which form ran.)
+    Either way: == `ovo_map_step` + `ovo_track_step` on fresh copies == the oracle's map half."""
+    from ovo_amd import _lib as L
+
+    def single(lib, a, t):
+        L.check(lib.ovo_map_step(L.C.byref(a), L.stream()))
+        L.check(lib.ovo_track_step(L.C.byref(t), L.stream()))
+
+    one = _small_keyframe(lambda lib, a, t: L.check(lib.ovo_keyframe_step(L.C.byref(a), L.C.byref(t), L.stream())), h, w, 1)
+    two = _small_keyframe(single, h, w, 1)
+    for k in one:
+        assert torch.equal(one[k], two[k]), k
+    for out in (one, two):
+        _assert_map_half_equals_oracle(out, h, w, 1)
+    explained, ref_xyz, _ = _small_keyframe_map_reference(h, w, 1)
+    n0, m, scale = _small_keyframe_inputs(h, w, 1)[3].shape[0], ref_xyz.shape[0], (h * w) // 1080
+    assert 100 * scale < m < h * w and explained.sum() > 100 * scale          # the surface points explain their pixels, the rest of the frame is appended
+    res = two["track_result"]
+    assert int(res[0]) == 1 and int(res[8::6].sum()) > 150 * scale and (res[12::6] >= 0).all()
+    assert (two["ins"][n0:n0 + m] >= 0).sum() > 100 * scale
 
 
 # ------------------------------------------------------------------ oracle at full size

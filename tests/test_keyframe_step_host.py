@@ -91,6 +91,24 @@ def test_keyframe_step_checks_both_halves_before_any_launch(h, w, case, kw):
     _failed(lib, lib.ovo_keyframe_step(L.C.byref(a), L.C.byref(t), None), b"ovo_keyframe_step", case)
 
 
+def test_round_chain_refuses_a_frame_past_the_one_workgroup_scan():
+    """258 x 512 at ds = 1: 2064 flag words, 16 more than the single workgroup of the one-launch form scans.  `ovo_round_chain` answers OVO_E_UNSUPPORTED (the
+    caller then goes keyframe by keyframe) before it writes a parameter slot or launches: the addresses here are made up.  A production build carries no
+    one-launch form at all and says so with the same code."""
+    from ovo_amd import _lib as L
+    lib = L.load()
+    h, w = 258, 512
+    a = _map_step(L, lib, h=h, w=w, ds=1, cap=N_UPPER + h * w, ws_bytes=lib.ovo_compact_workspace_bytes(h * w) + 8)
+    ctx = L.RoundChain(0x200000, 0x210000, 0, 0, 0)
+    rc = lib.ovo_round_chain(L.C.byref(ctx), (L.MapStep * 1)(a), (L.TrackStep * 1)(_track_step(L, lib)), 1, None)
+    assert rc == L.E_UNSUPPORTED == -3
+    if lib.ovo_round_chain_params_bytes() == 0:
+        assert lib.ovo_hip_last_error().startswith(b"ovo_round_chain: not in this build")
+    else:
+        assert lib.ovo_hip_last_error() == b"ovo_round_chain: frame too large for the one-workgroup scan"
+        assert (ctx.next_slot, ctx.arrivals) == (0, 0)
+
+
 @pytest.mark.parametrize("n", [1, 2, 3, 168, 1024, 8192])
 @pytest.mark.parametrize("c", [1, 2, 3, 64, 257])
 def test_track_workspace_bytes(n, c):
