@@ -798,6 +798,61 @@ size_t ovo_render_boxes_workspace_bytes(int m);
 int ovo_render_boxes(const float *corners, const int32_t *box_id, int m, const ovo_view_t *view, float half_width, const float *scene_depth,
                      float depth_slack, int32_t *out_id, float *out_depth, void *ws, size_t ws_bytes, ovo_stream_t stream);
 
+/* =============================================================================================
+ * Following the camera (ABI v20): multi-scale projective point-to-plane ICP, frame to keyframe -- the geometry-only pose the reference takes from
+ * Open3D's rgbd_odometry_multi_scale in its Gaussian-SLAM back end (ovo/submodules/gaussian_slam/entities/visual_odometer.py), stated as this
+ * project's own contract.
+ * ============================================================================================= */
+typedef struct {
+    int32_t h, w;               /* level 0; level l is (h >> l) x (w >> l) */
+    int32_t levels;             /* 1 .. 4, the coarsest level 3 x 3 or larger */
+    float fx, fy, cx, cy;       /* level 0; level l + 1 has fx / 2, fy / 2, (cx + 0.5) / 2 - 0.5, (cy + 0.5) / 2 - 0.5 (f64 on the host, rounded to f32 once) */
+    float max_depth;            /* a depth is valid iff finite, > 0 and <= max_depth */
+    float depth_jump;           /* > 0: the largest depth difference that still counts as one surface */
+} ovo_icp_frame_t;
+
+typedef struct {
+    int32_t iters[4];           /* Gauss-Newton steps per level, COARSE TO FINE: iters[k] runs on level levels - 1 - k; each 0 .. 64, at least one in all */
+    float dist_th, cos_th;      /* a pair is kept iff |P - q|^2 <= dist_th^2 and dot(N, nq) >= cos_th */
+    int32_t min_pairs;          /* LOST below this many pairs on level 0, below min_pairs >> 2l on level l (a quarter of the pixels per level) */
+    float min_pivot_ratio;      /* LOST when a Cholesky pivot <= min_pivot_ratio * the largest diagonal entry of J^T J; [0, 1) */
+    int64_t seq;                /* sequence word of the result block, != 0 */
+} ovo_icp_align_t;
+
+/* ovo_icp_prepare: depth f32[h,w] (metres, 0 = invalid) -> a pyramid of vertex and normal maps in `pyramid` (device, 16-byte aligned,
+ * ovo_icp_pyramid_bytes(h, w, levels) = 32 bytes per pixel of every level; 0 for a size ovo_icp_prepare would refuse).  Level l starts
+ * 32 * sum_{k<l} (h >> k)(w >> k) bytes in; a pixel is float4 vertex (x, y, z, bit 0 of w: the depth is valid) and float4 normal (nx, ny, nz, bit 0
+ * of w: the normal is valid).  z is the level's depth as it stands (level 0: the input, NaN included); x = y = 0 where it is not valid.
+ *   level l + 1, pixel (v, u)   the 2 x 2 block at (2v, 2u) of level l (an odd last row / column is dropped): the valid values that are at most
+ *                               depth_jump above the block's smallest valid one, summed in f32 in the order 00, 01, 10, 11, divided by their count; 0 if none
+ *   vertex                      x = ((u - cx) * d) / fx, y = ((v - cy) * d) / fy, z = d: one rounding per operation, IEEE division
+ *   normal (interior pixels)    n = cross(V(u+1,v) - V(u-1,v), V(u,v+1) - V(u,v-1)) / its length, negated if dot(n, V) > 0; valid iff all five depths are
+ *                               valid, each neighbour's depth is within depth_jump of the centre's and the length is > 0.  Border pixels have none.
+ * 2 * levels launches.  OVO_E_ARG, nothing launched: a null pointer, a frame outside the limits above (h * w <= 2^26), a pyramid too small or misaligned. */
+size_t ovo_icp_pyramid_bytes(int h, int w, int levels);
+int ovo_icp_prepare(const float *depth, const ovo_icp_frame_t *frame, void *pyramid, size_t pyramid_bytes, ovo_stream_t stream);
+
+/* ovo_icp_align: the whole alignment of the current frame's pyramid to a reference (keyframe) pyramid, queued at once.  T: device f32[12], the top three
+ * rows of (reference camera <- current camera); read as the start value when the first launch runs, advanced on the device, the final value written back.
+ * Per level, coarse to fine, iters[k] Gauss-Newton steps.  Per current-level pixel with a valid normal (p, n):
+ *   P = R p + t, N = R n (f32 FMA chains, left to right);  dropped unless P.z > 0;  u = rint(fx * P.x / P.z + cx), v likewise, inside the reference level,
+ *   whose pixel (v, u) must have a valid normal (q, nq);  kept iff |P - q|^2 <= dist_th^2 and dot(N, nq) >= cos_th;
+ *   r = dot(nq, P - q),  J = [cross(P, nq), nq]  (rotation first), all f32.
+ * The 21 upper-triangle entries of J^T J (row-major), the 6 of J^T r, sum r^2 and the pair count are formed and summed in f64, in an order that depends on
+ * the level's size alone (not on the grid, not on arrival order: two calls give the same bits).  (J^T J) xi = -J^T r by Cholesky in f64, T <- exp(xi) T
+ * (Rodrigues and the SE(3) V matrix in f64, rounded to f32 on store).  LOST: fewer than min_pairs >> 2l pairs on level l or a pivot at or below the floor; T then keeps
+ * the value it had before the call and the remaining iterations do nothing.
+ * result_host (optional): pinned memory from ovo_host_alloc, 40 words of 8 bytes, word 0 written last:
+ *   0 seq | 1 state (2 OK, 3 LOST) | 2 pairs and 4 sum r^2 (f64) of the last executed iteration | 3 iterations executed (the one that found LOST included) |
+ *   5 .. 33 the 29 sums of the last executed iteration (f64) | 34 .. 39 the final T (12 f32)
+ * ws: device scratch of ovo_icp_align_workspace_bytes(), 16-byte aligned.  2 + 2 * (iterations) launches: reduce (one slab of partial sums per
+ * workgroup, plain stores) and a one-workgroup solve alternate; nothing crosses workgroups inside a launch.  OVO_E_ARG, nothing launched: a null pointer,
+ * an invalid frame, reference and current pyramid of different size or level count, iters outside 0 .. 64 or all 0, dist_th <= 0, cos_th outside [-1, 1],
+ * min_pairs < 0, min_pivot_ratio outside [0, 1), seq == 0 with a result block, a missing / small / misaligned workspace. */
+size_t ovo_icp_align_workspace_bytes(void);
+int ovo_icp_align(const void *ref_pyramid, const ovo_icp_frame_t *ref, const void *cur_pyramid, const ovo_icp_frame_t *cur, const ovo_icp_align_t *align,
+                  float *T, void *result_host, void *ws, size_t ws_bytes, ovo_stream_t stream);
+
 
 /* =============================================================================================
  * The keyframe chain without host round trips (MI355X extension of a6 / a9; what the reference does with a `.sum()` / vstack

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "lib", "libovo_hip.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 E_UNSUPPORTED = -3          # OVO_E_UNSUPPORTED: the entry point does not cover this shape; the caller takes its general path
 
 
@@ -137,6 +137,18 @@ class View(C.Structure):
                 ("h", C.c_int32), ("w", C.c_int32), ("radius", C.c_int32)]
 
 
+class IcpFrame(C.Structure):
+    """ovo_icp_frame_t"""
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("levels", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("max_depth", C.c_float), ("depth_jump", C.c_float)]
+
+
+class IcpAlign(C.Structure):
+    """ovo_icp_align_t"""
+    _fields_ = [("iters", C.c_int32 * 4), ("dist_th", C.c_float), ("cos_th", C.c_float), ("min_pairs", C.c_int32), ("min_pivot_ratio", C.c_float),
+                ("seq", C.c_int64)]
+
+
 DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.uint8: 3}
 
 _SIGNATURES = {
@@ -236,6 +248,10 @@ _SIGNATURES = {
     "ovo_instance_geometry": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "ovo_render_boxes_workspace_bytes": (_SZ, [_I32]),
     "ovo_render_boxes": (_I32, [_P, _P, _I32, C.POINTER(View), _F32, _P, _F32, _P, _P, _P, _SZ, _P]),
+    "ovo_icp_pyramid_bytes": (_SZ, [_I32, _I32, _I32]),
+    "ovo_icp_prepare": (_I32, [_P, C.POINTER(IcpFrame), _P, _SZ, _P]),
+    "ovo_icp_align_workspace_bytes": (_SZ, []),
+    "ovo_icp_align": (_I32, [_P, C.POINTER(IcpFrame), _P, C.POINTER(IcpFrame), C.POINTER(IcpAlign), _P, _P, _P, _SZ, _P]),
     "ovo_sam_i2t_attention": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_sam_t2i_attention": (_I32, [_P, _P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_paint_segmap": (_I32, [_P, _I32, _I64, _P, _P]),

@@ -9,7 +9,8 @@ What is different, on purpose:
     `(frame_id, image HxWx3 u8, depth HxW f32, c2w 4x4[, full-resolution image])` and carries `intrinsics`, `height`, `width`
     (+ `dataset_config`, `crop_edge` when colour and depth resolutions differ) works;
   * the `vanilla` back end, and the `orbslam*` wrapper around an INJECTED tracker (`tracker=`, `ok_state=`: slam/orbslam.py; the ORB-SLAM
-    binding itself and Gaussian-SLAM are out of scope); there is no Open3D visualiser process (`vis.stream` must be false);
+    binding itself and Gaussian-SLAM are out of scope), and `rgbd_icp`: the same wrapper around the package's own depth tracker
+    (slam/icp_tracker.py); there is no Open3D visualiser process (`vis.stream` must be false);
   * no autocast context: the kernels choose their own arithmetic (bf16 MFMA operands, fp32 accumulation);
   * when a frame is segmented, the mask-independent half of the next segmented frame's feature extraction is not started
     early here (a dataset may be a live camera); `ovo_amd.pipeline.FramePipeline` is the throughput-oriented driver that does.
@@ -37,9 +38,17 @@ def get_slam_backbone(config: Dict[str, Any], dataset, cam_intrinsics: torch.Ten
     if backbone.startswith("orbslam") and tracker is not None:
         from ..slam.orbslam import WrapperORBSLAM
         return WrapperORBSLAM(config, cam_intrinsics, world_ref=torch.from_numpy(dataset[0][3]), tracker=tracker, ok_state=ok_state)      # :23-25
+    if backbone == "rgbd_icp":                             # the package's own tracker behind the same seam (slam/icp_tracker.py)
+        from ..slam.icp_tracker import IcpTracker
+        from ..slam.orbslam import WrapperORBSLAM
+        if tracker is None:
+            tracker = IcpTracker(cam_intrinsics, device=config.get("device", "cuda"), **config["slam"].get("icp", {}))
+        first = np.asarray(dataset[0][3], dtype=np.float32) if len(dataset[0]) > 3 and dataset[0][3] is not None else None
+        world_ref = torch.from_numpy(first.copy()) if first is not None and first.shape == (4, 4) and np.isfinite(first).all() else torch.eye(4)
+        return WrapperORBSLAM(config, cam_intrinsics, world_ref=world_ref, tracker=tracker, ok_state=ok_state)
     if backbone != "vanilla":
-        raise NotImplementedError(f"slam_module {backbone!r}: only the ground-truth-pose 'vanilla' mapper is built here, and the 'orbslam*' "
-                                  "wrapper around an injected tracker= (Gaussian-SLAM and the ORB-SLAM binding itself are out of scope, SURVEY.md §2)")
+        raise NotImplementedError(f"slam_module {backbone!r}: only the ground-truth-pose 'vanilla' mapper is built here, the 'orbslam*' wrapper "
+                                  "around an injected tracker= and 'rgbd_icp' (Gaussian-SLAM and the ORB-SLAM binding itself are out of scope, SURVEY.md §2)")
     return VanillaMapper(config, cam_intrinsics)
 
 

@@ -46,7 +46,7 @@ class VanillaMapper:
         self._n_known = 0                                  # exact when nothing is in flight
         self._pending: deque = deque()                     # (sequence number, sub-sampled pixels) of map_launch calls not read back yet
         self._state = torch.zeros(4, dtype=torch.int64, device=self.device)       # {n, next point id, flags, ticket}
-        self._ring = L.PinnedRing(4, np.int64, 64)
+        self._ring_obj = None                              # the result blocks (pinned memory): made with the first use, so that a host without a GPU can construct the class
         self._deferred = 0                                 # map steps built with defer=True and not handed to a launcher yet
         self.last_seq = 0                                  # sequence number of the newest map step (its result block holds the map's size after it)
         self._explained = None
@@ -55,6 +55,16 @@ class VanillaMapper:
         self._cap = 0
         self._xyz = self._ids = self._ins = self._rgb = None
         self._reserve(1 << 16)
+
+    @property
+    def _ring(self) -> L.PinnedRing:
+        if self._ring_obj is None:
+            self._ring_obj = L.PinnedRing(4, np.int64, 64)
+        return self._ring_obj
+
+    @_ring.setter
+    def _ring(self, ring: L.PinnedRing) -> None:
+        self._ring_obj = ring
 
     # ------------------------------------------------------------------ size of the map (device-resident, mirrored lazily)
     def settle(self) -> None:
