@@ -84,7 +84,8 @@ def test_mask_decoder_batch_invariance():
 
 
 def test_amg_filters_vs_oracle():
-    """Stability / area / box statistics and binarisation on the on-the-fly bilinear upsampling == torch's interpolate."""
+    """Stability / area / box statistics and binarisation on the on-the-fly bilinear upsampling == torch's interpolate.
+    (One shape, loose bounds; tests/test_gpu_image_kernels.py pins both kernels exactly at the shapes, thresholds and edges this one leaves out.)"""
     from oracle import sam2_amg as OA
     from oracle.features import masks_to_boxes
     from ovo_amd import _lib as L
