@@ -853,6 +853,22 @@ size_t ovo_icp_align_workspace_bytes(void);
 int ovo_icp_align(const void *ref_pyramid, const ovo_icp_frame_t *ref, const void *cur_pyramid, const ovo_icp_frame_t *cur, const ovo_icp_align_t *align,
                   float *T, void *result_host, void *ws, size_t ws_bytes, ovo_stream_t stream);
 
+/* ovo_icp_align_batch (ABI v21): ONE current frame aligned against m reference pyramids in the same launches -- what a loop
+ * closure's verification needs (a new keyframe against several old ones).  ref_pyramids: a HOST array of m device pointers (read during the call and
+ * carried to the device in the kernel arguments: no device table, no copy), all described by `ref`; the same pointer may appear twice.
+ * T: device f32[m][12], entry k's start value in and its final value out; result_host (optional): m blocks of OVO_ICP_RESULT_WORDS words one behind the
+ * other, each laid out as above and each carrying align->seq in its word 0, written last.
+ * Entry k's T and result block are BIT-EQUAL to what ovo_icp_align gives alone with ref_pyramids[k] and the start value T[k] (ovo_icp_align is the m = 1
+ * case of the same kernels).  A LOST entry stops on its own -- its T restored, its workgroups return at once -- and the others go on.
+ * 2 + 2 * (iterations) launches whatever m is: the batch is blockIdx.y of the reduce pass and blockIdx.x of init, solve and publish; every entry has its
+ * own state and slabs, ovo_icp_align_workspace_bytes() apart in ws (ovo_icp_align_batch_workspace_bytes(m) in all; 0 for an m outside 1 .. 16).
+ * OVO_E_ARG, nothing launched: m outside 1 .. OVO_ICP_MAX_BATCH, a null or misaligned entry of ref_pyramids, and everything ovo_icp_align refuses. */
+#define OVO_ICP_MAX_BATCH 16
+#define OVO_ICP_RESULT_WORDS 40
+size_t ovo_icp_align_batch_workspace_bytes(int m);
+int ovo_icp_align_batch(const void *const *ref_pyramids, const ovo_icp_frame_t *ref, const void *cur_pyramid, const ovo_icp_frame_t *cur,
+                        const ovo_icp_align_t *align, int m, float *T, void *result_host, void *ws, size_t ws_bytes, ovo_stream_t stream);
+
 
 /* =============================================================================================
  * The keyframe chain without host round trips (MI355X extension of a6 / a9; what the reference does with a `.sum()` / vstack

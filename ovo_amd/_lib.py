@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "lib", "libovo_hip.so")
-ABI_VERSION = 20
+ABI_VERSION = 21
 E_UNSUPPORTED = -3          # OVO_E_UNSUPPORTED: the entry point does not cover this shape; the caller takes its general path
 
 
@@ -252,6 +252,8 @@ _SIGNATURES = {
     "ovo_icp_prepare": (_I32, [_P, C.POINTER(IcpFrame), _P, _SZ, _P]),
     "ovo_icp_align_workspace_bytes": (_SZ, []),
     "ovo_icp_align": (_I32, [_P, C.POINTER(IcpFrame), _P, C.POINTER(IcpFrame), C.POINTER(IcpAlign), _P, _P, _P, _SZ, _P]),
+    "ovo_icp_align_batch_workspace_bytes": (_SZ, [_I32]),
+    "ovo_icp_align_batch": (_I32, [_P, C.POINTER(IcpFrame), _P, C.POINTER(IcpFrame), C.POINTER(IcpAlign), _I32, _P, _P, _P, _SZ, _P]),
     "ovo_sam_i2t_attention": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_sam_t2i_attention": (_I32, [_P, _P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_paint_segmap": (_I32, [_P, _I32, _I64, _P, _P]),

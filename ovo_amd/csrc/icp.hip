@@ -4,6 +4,9 @@
 //       k_icp_vertex0   level 0 from the depth image          k_icp_down   level l + 1 from the 2 x 2 blocks of level l
 //       k_icp_normals   a level's normals from its vertices (reads .v, writes .n: nobody writes what another reads)
 //   ovo_icp_align     the whole coarse-to-fine alignment queued at once; pose, sums and the LOST flag stay on the device (IcpState in the workspace)
+//   ovo_icp_align_batch  m alignments of ONE current frame against m references in the same launches: entry k is blockIdx.y
+//                     of the reduce pass and blockIdx.x of the other three kernels, with its own IcpState and slabs ICP_ENTRY_BYTES apart in the
+//                     workspace.  ovo_icp_align is the m = 1 case: one set of kernels, one per-pixel arithmetic, the same bits.
 //       k_icp_init      state := (T0, not lost, 0 iterations)
 //       k_icp_reduce    one pass over the current level: associate, residual and Jacobian row in f32, the 29 sums in f64 -> one slab per VIRTUAL workgroup
 //       k_icp_solve     one workgroup: the slabs summed in a fixed order, 6 x 6 Cholesky in f64, T <- exp(xi) T, or LOST
@@ -37,6 +40,12 @@ struct IcpState {
     int lost, iterations, pad[2];
     double sums[ICP_SLAB];
 };
+
+// Entry k of a batch lives at ws + k * ICP_ENTRY_BYTES: its state, then its slabs.
+constexpr size_t ICP_ENTRY_BYTES = sizeof(IcpState) + sizeof(double) * ICP_SLAB * ICP_MAX_SLABS;
+static_assert(ICP_ENTRY_BYTES % 16 == 0, "every entry as aligned as the workspace");
+__device__ __forceinline__ IcpState *icp_state(void *ws, int k) { return (IcpState *)((char *)ws + (size_t)k * ICP_ENTRY_BYTES); }
+__device__ __forceinline__ double *icp_slabs(void *ws, int k) { return (double *)((char *)ws + (size_t)k * ICP_ENTRY_BYTES + sizeof(IcpState)); }
 
 __device__ __forceinline__ bool depth_valid(float d, float max_depth) { return d > 0.0f && d <= max_depth; }      // (NaN and +inf fail)
 __device__ __forceinline__ bool flagged(float w) { return (__float_as_uint(w) & 1u) != 0; }
@@ -95,8 +104,9 @@ __global__ void __launch_bounds__(256) k_icp_normals(IcpPixel *lvl, int h, int w
     }
 }
 
-__global__ void k_icp_init(IcpState *st, const float *T) {
-    if (threadIdx.x < 12) { const float t = T[threadIdx.x]; st->T[threadIdx.x] = t; st->T0[threadIdx.x] = t; }
+__global__ void k_icp_init(void *ws, const float *T) {
+    IcpState *st = icp_state(ws, blockIdx.x);
+    if (threadIdx.x < 12) { const float t = T[12 * blockIdx.x + threadIdx.x]; st->T[threadIdx.x] = t; st->T0[threadIdx.x] = t; }
     if (threadIdx.x < ICP_SLAB) st->sums[threadIdx.x] = 0.0;
     if (threadIdx.x == 0) { st->lost = 0; st->iterations = 0; }
 }
@@ -106,11 +116,11 @@ __global__ void k_icp_init(IcpState *st, const float *T) {
 #define ICP_PIN(f) asm volatile("" : "+v"((f).x), "+v"((f).y), "+v"((f).z), "+v"((f).w))
 
 struct IcpReduce {
-    const IcpPixel *ref, *cur;
+    const IcpPixel *ref[OVO_ICP_MAX_BATCH];                 // this level of every entry's reference: the table travels in the kernel arguments
+    const IcpPixel *cur;
     IcpLevel lv;
     float dist2_th, cos_th;
-    const IcpState *st;
-    double *slabs;
+    void *ws;
     int n_virtual;
 };
 
@@ -118,10 +128,13 @@ struct IcpReduce {
 // reference pixel is a gather (the projection decides it); its two halves are loaded for all ICP_ROWS pixels before any of them is used.
 __global__ void __launch_bounds__(256) k_icp_reduce(const IcpReduce a) {
     __shared__ double s_part[4][ICP_SLAB];
-    if (a.st->lost) return;                                 // (the same word for every workgroup, written a kernel boundary ago)
+    const IcpState *st = icp_state(a.ws, blockIdx.y);
+    if (st->lost) return;                                   // (the same word for every workgroup of the entry, written a kernel boundary ago)
+    const IcpPixel *ref = a.ref[blockIdx.y];
+    double *slabs = icp_slabs(a.ws, blockIdx.y);
     float T[12];
 #pragma unroll
-    for (int i = 0; i < 12; ++i) T[i] = a.st->T[i];
+    for (int i = 0; i < 12; ++i) T[i] = st->T[i];
     const int64_t pixels = (int64_t)a.lv.h * a.lv.w, step = (int64_t)a.n_virtual * 256;
     const float u_max = (float)(a.lv.w - 1), v_max = (float)(a.lv.h - 1);
     for (int vb = blockIdx.x; vb < a.n_virtual; vb += gridDim.x) {
@@ -154,7 +167,7 @@ __global__ void __launch_bounds__(256) k_icp_reduce(const IcpReduce a) {
             }
 #pragma unroll
             for (int k = 0; k < ICP_ROWS; ++k) {
-                const IcpPixel *q = a.ref + (at[k] >= 0 ? at[k] : 0);      // (a dropped pixel reads pixel 0 and is dropped again below)
+                const IcpPixel *q = ref + (at[k] >= 0 ? at[k] : 0);      // (a dropped pixel reads pixel 0 and is dropped again below)
                 rv[k] = q->v; rn[k] = q->n;
             }
 #pragma unroll
@@ -194,7 +207,7 @@ __global__ void __launch_bounds__(256) k_icp_reduce(const IcpReduce a) {
         }
         __syncthreads();
         if (threadIdx.x < ICP_SUMS)
-            a.slabs[(int64_t)vb * ICP_SLAB + threadIdx.x] = ((s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + s_part[2][threadIdx.x]) + s_part[3][threadIdx.x];
+            slabs[(int64_t)vb * ICP_SLAB + threadIdx.x] = ((s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + s_part[2][threadIdx.x]) + s_part[3][threadIdx.x];
     }
 }
 
@@ -226,12 +239,14 @@ __device__ void se3_advance(const double *xi, float *T) {
     for (int i = 0; i < 12; ++i) T[i] = (float)out[i];
 }
 
-// One workgroup.  The slabs are summed in an order that depends on their number alone: thread (g, t) takes entry t of the slabs [32 g, 32 g + 32), all 32
+// One workgroup per entry.  The slabs are summed in an order that depends on their number alone: thread (g, t) takes entry t of the slabs [32 g, 32 g + 32), all 32
 // loads issued before the first addition (a missing slab adds 0.0), and entry t's eight partial sums are added in the order of g.
 // LOST: fewer than min_pairs pairs, or a Cholesky pivot <= min_pivot_ratio * the largest diagonal entry of J^T J (NaN included).
 static_assert(ICP_MAX_SLABS == 8 * 32 && ICP_SLAB == 32, "k_icp_solve: 8 groups of 32 slabs, 32 entries each");
-__global__ void __launch_bounds__(256) k_icp_solve(IcpState *st, const double *__restrict__ slabs, int n_virtual, int min_pairs, double min_pivot_ratio) {
+__global__ void __launch_bounds__(256) k_icp_solve(void *ws, int n_virtual, int min_pairs, double min_pivot_ratio) {
     __shared__ double s_part[8][ICP_SLAB], s_sum[ICP_SLAB], s_A[36], s_x[6];
+    IcpState *st = icp_state(ws, blockIdx.x);
+    const double *__restrict__ slabs = icp_slabs(ws, blockIdx.x);
     if (st->lost) return;
     {
         const int t = threadIdx.x & 31, g = threadIdx.x >> 5;
@@ -293,10 +308,12 @@ __global__ void __launch_bounds__(256) k_icp_solve(IcpState *st, const double *_
 }
 
 // words (8 bytes each): 0 sequence | 1 state (2 OK, 3 LOST) | 2 pairs | 3 iterations run | 4 sum r^2 (f64) | 5..33 the 29 sums (f64) | 34..39 T (12 f32)
-__global__ void __launch_bounds__(64) k_icp_publish(const IcpState *st, float *T, volatile long long *host, long long seq) {
+__global__ void __launch_bounds__(64) k_icp_publish(void *ws, float *T, volatile long long *host, long long seq) {
     const int t = threadIdx.x;
-    if (t < 12) T[t] = st->T[t];
+    const IcpState *st = icp_state(ws, blockIdx.x);
+    if (t < 12) T[12 * blockIdx.x + t] = st->T[t];
     if (!host) return;
+    host += OVO_ICP_RESULT_WORDS * blockIdx.x;
     if (t == 1) host[1] = st->lost ? 3 : 2;
     if (t == 2) host[2] = (long long)st->sums[28];
     if (t == 3) host[3] = st->iterations;
@@ -342,7 +359,9 @@ extern "C" size_t ovo_icp_pyramid_bytes(int h, int w, int levels) {
     return pixels * sizeof(IcpPixel);
 }
 
-extern "C" size_t ovo_icp_align_workspace_bytes(void) { return sizeof(IcpState) + sizeof(double) * ICP_SLAB * ICP_MAX_SLABS; }
+extern "C" size_t ovo_icp_align_workspace_bytes(void) { return ICP_ENTRY_BYTES; }
+
+extern "C" size_t ovo_icp_align_batch_workspace_bytes(int m) { return m >= 1 && m <= OVO_ICP_MAX_BATCH ? (size_t)m * ICP_ENTRY_BYTES : 0; }
 
 extern "C" int ovo_icp_prepare(const float *depth, const ovo_icp_frame_t *frame, void *pyramid, size_t pyramid_bytes, ovo_stream_t stream) {
     // everything is checked HERE, before anything is queued
@@ -366,46 +385,72 @@ extern "C" int ovo_icp_prepare(const float *depth, const ovo_icp_frame_t *frame,
     return OVO_OK;
 }
 
-extern "C" int ovo_icp_align(const void *ref_pyramid, const ovo_icp_frame_t *ref, const void *cur_pyramid, const ovo_icp_frame_t *cur,
-                             const ovo_icp_align_t *align, float *T, void *result_host, void *ws, size_t ws_bytes, ovo_stream_t stream) {
-    // everything is checked HERE, before anything is queued
-    OVO_REQUIRE(ref_pyramid && ref && cur_pyramid && cur && align && T, "null pointer");
-    const ovo_icp_frame_t fr = *ref, fc = *cur;
-    const ovo_icp_align_t a = *align;
+namespace {
+
+// Both entry points: everything is checked HERE, before anything is queued (the text of what is wrong, or null), then m alignments are queued.
+const char *icp_align_check(const void *const *refs, const ovo_icp_frame_t *ref, const void *cur_pyramid, const ovo_icp_frame_t *cur,
+                            const ovo_icp_align_t *align, int m, const float *T, const void *result_host, const void *ws, size_t ws_bytes) {
+    if (!(m >= 1 && m <= OVO_ICP_MAX_BATCH)) return "m outside 1 .. 16";
+    if (!(refs && ref && cur_pyramid && cur && align && T)) return "null pointer";
     IcpLevel lv[ICP_MAX_LEVELS], lc[ICP_MAX_LEVELS];
-    OVO_REQUIRE(icp_levels(fr, lv) && icp_levels(fc, lc), "h, w >= 1, h * w <= 2^26, 1 <= levels <= 4 with a coarsest level of 3 x 3 or more, fx, fy, max_depth, depth_jump > 0");
-    OVO_REQUIRE(fr.h == fc.h && fr.w == fc.w && fr.levels == fc.levels, "reference and current pyramid differ in size");
-    OVO_REQUIRE((((uintptr_t)ref_pyramid | (uintptr_t)cur_pyramid) & 15) == 0 && ((uintptr_t)T & 3) == 0, "pyramid not 16-byte aligned");
+    if (!(icp_levels(*ref, lv) && icp_levels(*cur, lc)))
+        return "h, w >= 1, h * w <= 2^26, 1 <= levels <= 4 with a coarsest level of 3 x 3 or more, fx, fy, max_depth, depth_jump > 0";
+    if (!(ref->h == cur->h && ref->w == cur->w && ref->levels == cur->levels)) return "reference and current pyramid differ in size";
+    for (int k = 0; k < m; ++k)
+        if (!refs[k] || ((uintptr_t)refs[k] & 15) != 0) return "reference pyramid null or not 16-byte aligned";
+    if (((uintptr_t)cur_pyramid & 15) != 0 || ((uintptr_t)T & 3) != 0) return "pyramid not 16-byte aligned";
     int total = 0;
-    for (int k = 0; k < fr.levels; ++k) {
-        OVO_REQUIRE(a.iters[k] >= 0 && a.iters[k] <= ICP_MAX_ITERS, "iters outside 0 .. 64");
-        total += a.iters[k];
+    for (int k = 0; k < ref->levels; ++k) {
+        if (!(align->iters[k] >= 0 && align->iters[k] <= ICP_MAX_ITERS)) return "iters outside 0 .. 64";
+        total += align->iters[k];
     }
-    OVO_REQUIRE(total >= 1, "no iteration asked for");
-    OVO_REQUIRE(a.dist_th > 0.0f && a.dist_th < INFINITY && a.cos_th >= -1.0f && a.cos_th <= 1.0f, "dist_th must be > 0 and cos_th in [-1, 1]");
-    OVO_REQUIRE(a.min_pairs >= 0 && a.min_pivot_ratio >= 0.0f && a.min_pivot_ratio < 1.0f, "min_pairs must be >= 0 and min_pivot_ratio in [0, 1)");
-    OVO_REQUIRE(!result_host || (((uintptr_t)result_host & 7) == 0 && a.seq != 0), "result block not 8-byte aligned, or sequence number 0");
-    OVO_REQUIRE(ws && ws_bytes >= ovo_icp_align_workspace_bytes() && ((uintptr_t)ws & 15) == 0, "workspace missing, too small or not 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    IcpState *state = (IcpState *)ws;
-    double *slabs = (double *)((char *)ws + sizeof(IcpState));
-    k_icp_init<<<1, 64, 0, st>>>(state, T);
+    if (total < 1) return "no iteration asked for";
+    if (!(align->dist_th > 0.0f && align->dist_th < INFINITY && align->cos_th >= -1.0f && align->cos_th <= 1.0f)) return "dist_th must be > 0 and cos_th in [-1, 1]";
+    if (!(align->min_pairs >= 0 && align->min_pivot_ratio >= 0.0f && align->min_pivot_ratio < 1.0f)) return "min_pairs must be >= 0 and min_pivot_ratio in [0, 1)";
+    if (result_host && !(((uintptr_t)result_host & 7) == 0 && align->seq != 0)) return "result block not 8-byte aligned, or sequence number 0";
+    if (!(ws && ws_bytes >= (size_t)m * ICP_ENTRY_BYTES && ((uintptr_t)ws & 15) == 0)) return "workspace missing, too small or not 16-byte aligned";
+    return nullptr;
+}
+
+int icp_align_queue(const void *const *refs, const ovo_icp_frame_t &fr, const void *cur_pyramid, const ovo_icp_align_t &a, int m, float *T,
+                    void *result_host, void *ws, hipStream_t st) {
+    IcpLevel lv[ICP_MAX_LEVELS];
+    icp_levels(fr, lv);                                     // (reference and current frame have the same levels: checked)
+    k_icp_init<<<m, 64, 0, st>>>(ws, T);
     OVO_CHECK_LAUNCH();
     for (int k = 0; k < fr.levels; ++k) {                   // coarse to fine
         const int l = fr.levels - 1 - k;
         IcpReduce r;
-        r.ref = (const IcpPixel *)ref_pyramid + lv[l].first; r.cur = (const IcpPixel *)cur_pyramid + lc[l].first;
-        r.lv = lv[l]; r.dist2_th = a.dist_th * a.dist_th; r.cos_th = a.cos_th; r.st = state; r.slabs = slabs;
+        for (int e = 0; e < OVO_ICP_MAX_BATCH; ++e) r.ref[e] = e < m ? (const IcpPixel *)refs[e] + lv[l].first : nullptr;
+        r.cur = (const IcpPixel *)cur_pyramid + lv[l].first;
+        r.lv = lv[l]; r.dist2_th = a.dist_th * a.dist_th; r.cos_th = a.cos_th; r.ws = ws;
         r.n_virtual = icp_virtual((int64_t)lv[l].h * lv[l].w);
-        const int grid = icp_grid(r.n_virtual);
+        const dim3 grid(icp_grid(r.n_virtual), m);
         for (int it = 0; it < a.iters[k]; ++it) {
             k_icp_reduce<<<grid, 256, 0, st>>>(r);
             OVO_CHECK_LAUNCH();
-            k_icp_solve<<<1, 256, 0, st>>>(state, slabs, r.n_virtual, a.min_pairs >> (2 * l), (double)a.min_pivot_ratio);      // a level has a quarter of the pixels below it
+            k_icp_solve<<<m, 256, 0, st>>>(ws, r.n_virtual, a.min_pairs >> (2 * l), (double)a.min_pivot_ratio);      // a level has a quarter of the pixels below it
             OVO_CHECK_LAUNCH();
         }
     }
-    k_icp_publish<<<1, 64, 0, st>>>(state, T, (volatile long long *)result_host, (long long)a.seq);
+    k_icp_publish<<<m, 64, 0, st>>>(ws, T, (volatile long long *)result_host, (long long)a.seq);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
+}
+
+}  // namespace
+
+extern "C" int ovo_icp_align(const void *ref_pyramid, const ovo_icp_frame_t *ref, const void *cur_pyramid, const ovo_icp_frame_t *cur,
+                             const ovo_icp_align_t *align, float *T, void *result_host, void *ws, size_t ws_bytes, ovo_stream_t stream) {
+    OVO_REQUIRE(ref_pyramid, "null pointer");
+    const char *wrong = icp_align_check(&ref_pyramid, ref, cur_pyramid, cur, align, 1, T, result_host, ws, ws_bytes);
+    OVO_REQUIRE(!wrong, wrong);
+    return icp_align_queue(&ref_pyramid, *ref, cur_pyramid, *align, 1, T, result_host, ws, (hipStream_t)stream);
+}
+
+extern "C" int ovo_icp_align_batch(const void *const *ref_pyramids, const ovo_icp_frame_t *ref, const void *cur_pyramid, const ovo_icp_frame_t *cur,
+                                   const ovo_icp_align_t *align, int m, float *T, void *result_host, void *ws, size_t ws_bytes, ovo_stream_t stream) {
+    const char *wrong = icp_align_check(ref_pyramids, ref, cur_pyramid, cur, align, m, T, result_host, ws, ws_bytes);
+    OVO_REQUIRE(!wrong, wrong);
+    return icp_align_queue(ref_pyramids, *ref, cur_pyramid, *align, m, T, result_host, ws, (hipStream_t)stream);
 }

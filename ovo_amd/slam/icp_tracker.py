@@ -4,15 +4,21 @@ odometry in its Gaussian-SLAM back end (ovo/submodules/gaussian_slam/entities/vi
 pose device-resident, and the host reads one pinned result block per frame.
 
 The seven methods follow `ReplayTracker`'s conventions: a trajectory / keyframe row is 13 f32 -- the frame's time stamp, then the top three rows
-of its pose (camera to the FIRST frame's camera; `WrapperORBSLAM` puts `world_ref` in front)."""
+of its pose (camera to the FIRST frame's camera; `WrapperORBSLAM` puts `world_ref` in front).
+
+`close_loops=True` adds loop detection, verification and correction on keyframes: the new keyframe is aligned against
+the old keyframes its own pose estimate puts nearby -- all of them in the launches of one alignment (`ovo_icp_align_batch`) -- the ones that
+pass become edges of a pose graph (slam/pose_graph.py), and when the optimised graph moves a keyframe the keyframe rows are replaced and the
+big-change index goes up, which is what `WrapperORBSLAM.map` re-anchors its map on."""
 from __future__ import annotations
 
-from typing import Any, List, Optional
+from typing import Any, Dict, List, Optional
 
 import numpy as np
 import torch
 
 from ..utils import icp_utils as U
+from . import pose_graph
 
 
 class IcpTracker:
@@ -21,8 +27,20 @@ class IcpTracker:
 
     def __init__(self, K, levels: int = 3, iters=(10, 5, 4), dist_th: float = 0.1, normal_th_deg: float = 30.0, max_depth: float = 10.0,
                  depth_jump: float = 0.1, min_pairs_frac: float = 0.05, min_pivot_ratio: float = 1e-6, kf_translation: float = 0.15,
-                 kf_rotation_deg: float = 10.0, kf_min_overlap: float = 0.5, device="cuda") -> None:
-        """No GPU work happens here: buffers are made with the first frame."""
+                 kf_rotation_deg: float = 10.0, kf_min_overlap: float = 0.5, device="cuda", close_loops: bool = False, loop_min_gap: int = 10,
+                 loop_radius: float = 0.5, loop_angle_deg: float = 30.0, loop_max_candidates: int = 8, loop_iters=None, loop_dist_th: float = 0.2,
+                 loop_min_overlap: float = 0.3, loop_max_rms: float = 0.02, loop_max_correction=(0.3, 10.0), loop_min_shift=(0.01, 0.2),
+                 loop_max_keyframes: int = 256) -> None:
+        """No GPU work happens here: buffers are made with the first frame.
+
+        close_loops: every new keyframe n (its position in the keyframe list) is verified against the kept keyframes k <= n - loop_min_gap whose
+        guess X_k^-1 X_n lies within loop_radius (m) and loop_angle_deg -- the loop_max_candidates (<= 16) nearest, one `ovo_icp_align_batch` call
+        with loop_iters (default: iters) and loop_dist_th, one extra host wait on such a keyframe and none on any other frame.  An entry becomes
+        a loop edge when it is OK, has pairs >= loop_min_overlap * pixels and rms <= loop_max_rms, and lies within loop_max_correction (m, deg)
+        of its guess.  The graph is optimised when an edge was added and applied when some keyframe moves by more than loop_min_shift (m or deg).
+        The loop_* defaults are JUDGEMENT, not measurement: no real sequence was available when they were chosen.
+        Memory: the pyramids of the last loop_max_keyframes keyframes stay on the device, 11.8 MB each at 456 x 616 with 3 levels (3 GB at the
+        default 256); an older keyframe leaves the candidate set but stays a node of the graph."""
         self.K = np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, dtype=np.float32)[:3, :3].copy()
         self.levels, self.iters = int(levels), tuple(int(i) for i in iters)
         if not 1 <= self.levels <= U.MAX_LEVELS or len(self.iters) != self.levels:
@@ -30,6 +48,21 @@ class IcpTracker:
         self.dist_th, self.normal_th_deg, self.max_depth, self.depth_jump = float(dist_th), float(normal_th_deg), float(max_depth), float(depth_jump)
         self.min_pairs_frac, self.min_pivot_ratio = float(min_pairs_frac), float(min_pivot_ratio)
         self.kf_translation, self.kf_rotation_deg, self.kf_min_overlap = float(kf_translation), float(kf_rotation_deg), float(kf_min_overlap)
+        self.close_loops = bool(close_loops)
+        self.loop_min_gap, self.loop_max_candidates, self.loop_max_keyframes = int(loop_min_gap), int(loop_max_candidates), int(loop_max_keyframes)
+        self.loop_radius, self.loop_angle_deg, self.loop_dist_th = float(loop_radius), float(loop_angle_deg), float(loop_dist_th)
+        self.loop_iters = self.iters if loop_iters is None else tuple(int(i) for i in loop_iters)
+        self.loop_min_overlap, self.loop_max_rms = float(loop_min_overlap), float(loop_max_rms)
+        self.loop_max_correction = tuple(float(x) for x in loop_max_correction)
+        self.loop_min_shift = tuple(float(x) for x in loop_min_shift)
+        if not (self.loop_min_gap >= 1 and 1 <= self.loop_max_candidates <= U.MAX_BATCH and self.loop_max_keyframes >= 1):
+            raise ValueError(f"IcpTracker: loop_min_gap and loop_max_keyframes must be >= 1 and loop_max_candidates 1 .. {U.MAX_BATCH}")
+        if len(self.loop_iters) != self.levels or min(self.loop_iters) < 0 or sum(self.loop_iters) < 1:
+            raise ValueError("IcpTracker: loop_iters needs one entry per level, coarse to fine, none negative and not all 0")
+        if len(self.loop_max_correction) != 2 or len(self.loop_min_shift) != 2 or min(self.loop_max_correction) <= 0 or min(self.loop_min_shift) < 0:
+            raise ValueError("IcpTracker: loop_max_correction (> 0) and loop_min_shift (>= 0) are (metres, degrees)")
+        if not (self.loop_radius > 0 and self.loop_angle_deg > 0 and self.loop_dist_th > 0 and 0 <= self.loop_min_overlap <= 1 and self.loop_max_rms > 0):
+            raise ValueError("IcpTracker: loop_radius, loop_angle_deg, loop_dist_th and loop_max_rms must be > 0 and loop_min_overlap in [0, 1]")
         self.device = device
         self._aligner: Optional[U.Aligner] = None
         self._kf: Optional[U.Frame] = None                 # the last keyframe's pyramid
@@ -42,6 +75,14 @@ class IcpTracker:
         self._keyframes: List[np.ndarray] = []
         self.last: Any = None                              # the last alignment's result (None for a keyframe-initialising first frame)
         self.closed = False
+        # close_loops: the pose graph (f64), the kept pyramids by keyframe index (oldest first), what the last closure did
+        self._batch: Optional[U.BatchAligner] = None
+        self._X: List[np.ndarray] = [np.eye(4)]
+        self._edges: List[Any] = []
+        self._db: Dict[int, U.Frame] = {}
+        self._big_change = 0
+        self.loop_edges: List[Any] = []                    # (reference keyframe index, current keyframe index) of every accepted edge
+        self.last_loop: Any = None                         # the last verification: {"n", "candidates", "results", "accepted", "applied", "graph"}
 
     def _row_of(self, t, c2w: np.ndarray) -> np.ndarray:
         return np.concatenate([np.asarray([t], dtype=np.float32), np.asarray(c2w, dtype=np.float32)[:3].reshape(12)])
@@ -78,12 +119,54 @@ class IcpTracker:
         self._c2w = (self._kf_c2w @ res["T"]).astype(np.float32)
         self._row = self._row_of(t, self._c2w)
         if U.keyframe_decision(res["T"], res["pairs"], pixels, self.kf_translation, self.kf_rotation_deg, self.kf_min_overlap):
-            self._spare = self._kf.pyramid                 # (stream order: the next prepare is queued behind this frame's alignment)
+            old = self._kf
             self._kf, self._kf_c2w, self._is_kf = cur, self._c2w, True
             self._aligner.set_pose(np.eye(4, dtype=np.float32))
             self._keyframes.append(self._row)
+            if self.close_loops:
+                self._close_loop(old, cur, res, pixels)
+            else:
+                self._spare = old.pyramid                  # (stream order: the next prepare is queued behind this frame's alignment)
         else:
             self._spare = cur.pyramid
+
+    def _close_loop(self, old: U.Frame, cur: U.Frame, res, pixels: int) -> None:
+        """The new keyframe `cur` (aligned to the outgoing keyframe `old` with result `res`): extend the graph, keep `old`'s pyramid, verify the
+        candidates in one batch, and apply the optimised graph if it moves a keyframe."""
+        n = len(self._keyframes) - 1
+        self._X.append(self._X[n - 1] @ res["T"].astype(np.float64))
+        self._edges.append((n - 1, n, res["T"].astype(np.float64), U.information(res["sums"])))
+        self._db[n - 1] = old
+        if len(self._db) > self.loop_max_keyframes:       # the oldest leaves the candidate set (it stays a node); its buffer takes the next frame
+            self._spare = self._db.pop(next(iter(self._db))).pyramid
+        candidates = U.select_candidates(self._X, n, list(self._db), self.loop_min_gap, self.loop_radius, self.loop_angle_deg, self.loop_max_candidates)
+        self.last_loop = {"n": n, "candidates": [k for k, _ in candidates], "results": [], "accepted": [], "applied": False, "graph": None}
+        if not candidates:
+            return
+        if self._batch is None:
+            self._batch = U.BatchAligner(cur.pyramid.device)
+        seq = self._batch.queue([self._db[k] for k, _ in candidates], cur, [G for _, G in candidates], self.loop_iters, self.loop_dist_th,
+                                self.normal_th_deg, int(np.ceil(self.min_pairs_frac * pixels)), self.min_pivot_ratio)
+        results = self._batch.wait(seq)                    # the one extra host wait of such a keyframe
+        self.last_loop["results"] = results
+        for (k, G), r in zip(candidates, results):
+            if U.accept_loop(r, G, pixels, self.loop_min_overlap, self.loop_max_rms, self.loop_max_correction):
+                self._edges.append((k, n, r["T"].astype(np.float64), U.information(r["sums"])))
+                self.loop_edges.append((k, n))
+                self.last_loop["accepted"].append(k)
+        if not self.last_loop["accepted"]:
+            return
+        X, info = pose_graph.optimise(self._X, self._edges)
+        self.last_loop["graph"] = info
+        shifts = [U.pose_offset(U.rigid_inverse(a) @ b) for a, b in zip(self._X, X)]
+        if not (info["improved"] and any(t > self.loop_min_shift[0] or a > self.loop_min_shift[1] for t, a in shifts)):
+            return                                         # the edges stay in the graph; nothing else changes
+        self._X = X
+        self._keyframes = [self._row_of(row[0], x) for row, x in zip(self._keyframes, X)]      # rounded to f32
+        self._kf_c2w = self._c2w = X[n].astype(np.float32)
+        self._row = self._keyframes[n]
+        self._big_change += 1
+        self.last_loop["applied"] = True
 
     def _need_frame(self) -> None:
         if self._row is None:
@@ -102,11 +185,12 @@ class IcpTracker:
         return self._is_kf
 
     def get_last_big_change_idx(self) -> int:
-        return 0                                           # no loop closing: the map is never re-anchored
+        return self._big_change                            # goes up when a closure moved the keyframes (always 0 without close_loops)
 
     def get_keyframe_points(self):
         return list(self._keyframes)
 
     def shutdown(self) -> None:
-        self._aligner = self._kf = self._spare = None
+        self._aligner = self._kf = self._spare = self._batch = None
+        self._db = {}
         self.closed = True
