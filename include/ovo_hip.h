@@ -869,6 +869,58 @@ size_t ovo_icp_align_batch_workspace_bytes(int m);
 int ovo_icp_align_batch(const void *const *ref_pyramids, const ovo_icp_frame_t *ref, const void *cur_pyramid, const ovo_icp_frame_t *cur,
                         const ovo_icp_align_t *align, int m, float *T, void *result_host, void *ws, size_t ws_bytes, ovo_stream_t stream);
 
+/* =============================================================================================
+ * A fused geometric model (ABI v22): a dense truncated-signed-distance volume integrated from depth frames, and a ray caster
+ * that returns the model's depth image from any pose -- what IcpTracker(model="tsdf") aligns a frame to.  The reference's Gaussian-SLAM back end
+ * keeps a fused model for the same purpose; this is the project's own contract, every operation f32, one rounding each, IEEE division.
+ * ============================================================================================= */
+typedef struct {
+    int32_t nx, ny, nz;         /* each 2 .. 4096, nx * ny * nz <= 2^31 */
+    float voxel;                /* > 0: voxel (i, j, k) sits at origin[a] + voxel * index, the product rounded, then the sum */
+    float origin[3];
+    float trunc;                /* > 0 */
+    float max_weight;           /* >= 1 */
+} ovo_tsdf_volume_t;
+
+typedef struct {
+    float c2w[12];              /* top three rows of camera -> volume frame, row-major */
+    float w2c[12];              /* its rigid inverse, formed on the host in f64 and rounded once */
+    float fx, fy, cx, cy;
+    int32_t h, w;               /* h, w >= 1, h * w <= 2^26 */
+    float near, far;            /* 0 < near <= far */
+} ovo_tsdf_camera_t;
+
+/* The volume: device float2 [nz][ny][nx] = (F, W), x fastest, 16-byte aligned; all-zero bytes mean "unobserved".  ovo_tsdf_volume_bytes: its size,
+ * or 0 for a descriptor the entry points would refuse.
+ *
+ * ovo_tsdf_integrate: one launch over the half-open index box [lo, hi) (host int32[3] each, inside the volume); nothing outside it is touched.
+ * Per voxel at (x, y, z):
+ *   P = (dot4(w2c row r, x, y, z, 1)), r = 0 .. 2 (f32 FMA chains, left to right);  skipped unless P.z > 0
+ *   u = rint(fx * P.x / P.z + cx), v likewise;  skipped unless (v, u) is inside the image
+ *   d = depth[v, u];  skipped unless d is finite and near <= d <= far
+ *   sdf = d - P.z;  skipped if sdf < -trunc;  f = min(1, sdf / trunc)
+ *   W1 = W + 1,  F <- (F * W + f) / W1,  W <- min(W1, max_weight)
+ * One thread owns a voxel: no atomics, the result is a pure function of the inputs, bit-equal from run to run, for any grid and for any box that
+ * holds the voxels a frame updates.
+ *
+ * ovo_tsdf_raycast: one launch, one thread per pixel (v, u) of depth_out f32[h,w]:
+ *   dir_c = ((u - cx) / fx, (v - cy) / fy, 1),  dir_w[r] = dot3(c2w row r, dir_c)
+ *   samples at z_k = near + (float)k * dz, k = 0 .. kmax, kmax = ceil((far - near) / dz) in f64 (refused above 4096)
+ *   pos = c2w translation + z_k * dir_w  (z is the camera-frame depth: a hit needs no normalisation)
+ *   g = (pos - origin) / voxel,  b = floor(g),  t = g - b
+ *   VALID iff 0 <= b[a] <= n[a] - 2 on all three axes and all eight corners have W > 0; its value is the trilinear blend of F with
+ *   lerp(p, q, t) = p + t * (q - p):  along x first (four blends, t[0]), then along y (two, t[1]), then along z (one, t[2])
+ *   the march keeps the previous sample: an invalid sample only forgets it;  a valid f_k <= 0 after a valid f_prev > 0 is a hit, depth
+ *   z_{k-1} + dz * (f_prev / (f_prev - f_k)), and the march stops;  a valid f_k > 0 after a valid f_prev <= 0 is a back face, the march stops
+ *   without a hit;  a pixel without a hit gets 0.
+ * Ranges of k whose samples are provably outside the volume are skipped; the result is that of the full march.
+ * OVO_E_ARG, nothing launched (both): a null pointer, a descriptor outside the limits above, fx or fy <= 0, near <= 0 or near > far or NaN,
+ * a volume not 16-byte aligned; integrate: a box outside the volume or with lo >= hi on an axis; raycast: dz <= 0, far not finite, kmax > 4096. */
+size_t ovo_tsdf_volume_bytes(const ovo_tsdf_volume_t *desc);
+int ovo_tsdf_integrate(void *vol, const ovo_tsdf_volume_t *desc, const float *depth, const ovo_tsdf_camera_t *cam, const int32_t *lo, const int32_t *hi,
+                       ovo_stream_t stream);
+int ovo_tsdf_raycast(const void *vol, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, float *depth_out, ovo_stream_t stream);
+
 
 /* =============================================================================================
  * The keyframe chain without host round trips (MI355X extension of a6 / a9; what the reference does with a `.sum()` / vstack

@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "lib", "libovo_hip.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 E_UNSUPPORTED = -3          # OVO_E_UNSUPPORTED: the entry point does not cover this shape; the caller takes its general path
 
 
@@ -149,6 +149,18 @@ class IcpAlign(C.Structure):
                 ("seq", C.c_int64)]
 
 
+class TsdfVolume(C.Structure):
+    """ovo_tsdf_volume_t"""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("voxel", C.c_float), ("origin", C.c_float * 3), ("trunc", C.c_float),
+                ("max_weight", C.c_float)]
+
+
+class TsdfCamera(C.Structure):
+    """ovo_tsdf_camera_t"""
+    _fields_ = [("c2w", C.c_float * 12), ("w2c", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("h", C.c_int32), ("w", C.c_int32), ("near", C.c_float), ("far", C.c_float)]
+
+
 DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.uint8: 3}
 
 _SIGNATURES = {
@@ -254,6 +266,9 @@ _SIGNATURES = {
     "ovo_icp_align": (_I32, [_P, C.POINTER(IcpFrame), _P, C.POINTER(IcpFrame), C.POINTER(IcpAlign), _P, _P, _P, _SZ, _P]),
     "ovo_icp_align_batch_workspace_bytes": (_SZ, [_I32]),
     "ovo_icp_align_batch": (_I32, [_P, C.POINTER(IcpFrame), _P, C.POINTER(IcpFrame), C.POINTER(IcpAlign), _I32, _P, _P, _P, _SZ, _P]),
+    "ovo_tsdf_volume_bytes": (_SZ, [C.POINTER(TsdfVolume)]),
+    "ovo_tsdf_integrate": (_I32, [_P, C.POINTER(TsdfVolume), _P, C.POINTER(TsdfCamera), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "ovo_tsdf_raycast": (_I32, [_P, C.POINTER(TsdfVolume), C.POINTER(TsdfCamera), _F32, _P, _P]),
     "ovo_sam_i2t_attention": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_sam_t2i_attention": (_I32, [_P, _P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_paint_segmap": (_I32, [_P, _I32, _I64, _P, _P]),

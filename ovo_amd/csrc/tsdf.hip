@@ -1,0 +1,235 @@
+// tsdf.hip -- a fused geometric model: a dense truncated-signed-distance volume integrated from depth frames, and the ray caster that turns it back
+// into a depth image from any pose.  IcpTracker(model="tsdf") aligns every frame to that image instead of the keyframe's.
+//   ovo_tsdf_integrate   k_tsdf_integrate<V>   one launch over the index box [lo, hi): one thread owns a voxel (V = 1, 8 bytes) or two x-neighbours
+//                                              (V = 2, 16 bytes, volumes with an even nx: every pair is 16-byte aligned), lanes along x
+//   ovo_tsdf_raycast     k_tsdf_raycast        one launch, one thread per pixel, 16 x 16 pixel tiles: a fixed-step march, trilinear samples
+// The volume is float2 [nz][ny][nx] = (F, W), x fastest; all-zero bytes are "unobserved".  No atomics, no cross-thread traffic: both results are pure
+// functions of their inputs, bit-equal from run to run and whatever OVO_TSDF_GRID_CAP says (it only changes which workgroup visits a voxel).
+// Every volume index is in range by construction: integrate's box is checked against the volume on the host, the ray caster tests a sample's base
+// cell against [0, n - 2] on all three axes BEFORE it forms an address, and issues no load for a sample that fails.
+// This file is compiled with -ffp-contract=off (projection.h): f32 operations are single IEEE operations in the order written, except the dot3 / dot4 chains.
+#include <math.h>
+
+#include "common.h"
+#include "projection.h"
+
+namespace {
+
+constexpr int64_t TSDF_MAX_VOXELS = (int64_t)1 << 31;
+constexpr int64_t TSDF_MAX_PIXELS = (int64_t)1 << 26;
+constexpr int TSDF_MAX_DIM = 4096;
+constexpr int TSDF_MAX_STEPS = 4096;                       // the largest kmax of a march
+constexpr int TSDF_TILE = 16;                              // ray-cast pixel tiles: a wave is 4 rows of 16 pixels
+
+struct TsdfVol { int nx, ny, nz; float voxel, ox, oy, oz, trunc, max_weight; };
+struct TsdfCam { float c2w[12], w2c[12], fx, fy, cx, cy; int h, w; float near, far; };
+struct TsdfBox { int x0, y0, z0, x1, y1, z1; };
+
+// What one depth frame says about the voxel at (i, j, k): false = nothing (the voxel keeps its bits), true = the sample f in [-1, 1].
+__device__ __forceinline__ bool tsdf_sample(const TsdfVol &v, const TsdfCam &c, const float *__restrict__ depth, int i, int j, int k, float &f) {
+    const float x = __fadd_rn(v.ox, __fmul_rn(v.voxel, (float)i)), y = __fadd_rn(v.oy, __fmul_rn(v.voxel, (float)j));
+    const float z = __fadd_rn(v.oz, __fmul_rn(v.voxel, (float)k));
+    const float px = dot4(c.w2c, x, y, z, 1.0f), py = dot4(c.w2c + 4, x, y, z, 1.0f), pz = dot4(c.w2c + 8, x, y, z, 1.0f);
+    if (!(pz > 0.0f)) return false;
+    const float uf = rintf(c.fx * px / pz + c.cx), vf = rintf(c.fy * py / pz + c.cy);
+    if (!(uf >= 0.0f && uf <= (float)(c.w - 1) && vf >= 0.0f && vf <= (float)(c.h - 1))) return false;      // (NaN fails)
+    const float d = depth[(int64_t)(int)vf * c.w + (int)uf];
+    if (!(fabsf(d) < INFINITY && d >= c.near && d <= c.far)) return false;                                  // (NaN fails)
+    const float sdf = d - pz;
+    if (sdf < -v.trunc) return false;
+    f = fminf(1.0f, sdf / v.trunc);
+    return true;
+}
+
+__device__ __forceinline__ void tsdf_update(float &F, float &W, float f, float max_weight) {
+    const float W1 = W + 1.0f;
+    F = (F * W + f) / W1;
+    W = fminf(W1, max_weight);
+}
+
+// Items are dealt lane by lane along x, then y, then z of the box: item -> (x item, row) with one 32-bit division, row -> (j, k) with another.
+// V = 2: x item q is the voxel pair (2 q, 2 q + 1); a pair with one voxel outside the box touches only the other one, with an 8-byte access.
+template <int V>
+__global__ void __launch_bounds__(256) k_tsdf_integrate(float2 *__restrict__ vol, const TsdfVol v, const float *__restrict__ depth, const TsdfCam c,
+                                                        const TsdfBox b) {
+    const uint32_t q0 = (uint32_t)(b.x0 / V), nq = (uint32_t)((b.x1 - 1) / V) - q0 + 1, by = (uint32_t)(b.y1 - b.y0);
+    const uint64_t items = (uint64_t)nq * by * (uint32_t)(b.z1 - b.z0);                          // <= 2^31
+    for (uint64_t it = (uint64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (uint64_t)gridDim.x * 256) {
+        const uint32_t row = (uint32_t)it / nq, q = (uint32_t)it - row * nq;                     // (it < 2^32)
+        const uint32_t kk = row / by, jj = row - kk * by;
+        const int i = (int)(q0 + q) * V, j = b.y0 + (int)jj, k = b.z0 + (int)kk;
+        float2 *p = vol + ((int64_t)k * v.ny + j) * v.nx + i;
+        if (V == 2) {
+            const bool in0 = i >= b.x0, in1 = i + 1 < b.x1;                                      // (at least one of them)
+            float f0 = 0.0f, f1 = 0.0f;
+            const bool up0 = in0 && tsdf_sample(v, c, depth, i, j, k, f0), up1 = in1 && tsdf_sample(v, c, depth, i + 1, j, k, f1);
+            if (!(up0 || up1)) continue;
+            if (in0 && in1) {
+                float4 a = *(float4 *)p;
+                if (up0) tsdf_update(a.x, a.y, f0, v.max_weight);
+                if (up1) tsdf_update(a.z, a.w, f1, v.max_weight);
+                *(float4 *)p = a;
+            } else {
+                float2 *one = p + (in0 ? 0 : 1);
+                float2 a = *one;
+                tsdf_update(a.x, a.y, in0 ? f0 : f1, v.max_weight);
+                *one = a;
+            }
+        } else {
+            float f = 0.0f;
+            if (!tsdf_sample(v, c, depth, i, j, k, f)) continue;
+            float2 a = *p;
+            tsdf_update(a.x, a.y, f, v.max_weight);
+            *p = a;
+        }
+    }
+}
+
+__device__ __forceinline__ float lerp1(float a, float b, float t) { return a + t * (b - a); }      // three operations, three roundings
+
+// The samples of pixel (v, u) lie at z_k = near + k dz, k = 0 .. kmax.  [k0, k1] is a range outside of which every sample is provably outside the volume
+// (slabs of the box grown by a voxel and a relative margin, two steps added at each end); inside it the validity test decides, as it would for every k.
+__global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const float2 *__restrict__ vol, const TsdfVol v, const TsdfCam c, float dz, int kmax,
+                                                                        int tiles_x, float *__restrict__ out) {
+    const int tile = blockIdx.x, ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int pu = tx * TSDF_TILE + (threadIdx.x & (TSDF_TILE - 1)), pv = ty * TSDF_TILE + (threadIdx.x / TSDF_TILE);
+    if (pu >= c.w || pv >= c.h) return;
+    const float dc[3] = {((float)pu - c.cx) / c.fx, ((float)pv - c.cy) / c.fy, 1.0f};
+    float dw[3], t0[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { dw[r] = dot3(c.c2w + 4 * r, dc[0], dc[1], dc[2]); t0[r] = c.c2w[4 * r + 3]; }
+    const float org[3] = {v.ox, v.oy, v.oz};
+    const int n[3] = {v.nx, v.ny, v.nz};
+    // ---- the clip: only ever skips samples that are outside the volume
+    float z_lo = c.near, z_hi = c.far + dz;
+    bool any = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float ext = v.voxel * (float)n[a];
+        const float margin = v.voxel + 1e-5f * (fabsf(org[a]) + fabsf(t0[a]) + ext + c.far * fabsf(dw[a]));
+        const float lo = org[a] - margin, hi = org[a] + ext + margin;
+        if (dw[a] == 0.0f) { any = any && t0[a] >= lo && t0[a] <= hi; continue; }
+        const float za = (lo - t0[a]) / dw[a], zb = (hi - t0[a]) / dw[a];
+        z_lo = fmaxf(z_lo, fminf(za, zb));                   // (fmaxf / fminf drop a NaN: the range then only grows)
+        z_hi = fminf(z_hi, fmaxf(za, zb));
+    }
+    int k0 = 0, k1 = -1;
+    if (any && z_lo <= z_hi) {                               // (finite: both lie within [near, far + dz])
+        const float s0 = floorf((z_lo - c.near) / dz) - 2.0f, s1 = ceilf((z_hi - c.near) / dz) + 2.0f;
+        k0 = (int)fmaxf(s0, 0.0f);
+        k1 = (int)fminf(s1, (float)kmax);
+    }
+    // ---- the march
+    float depth = 0.0f, f_prev = 0.0f;
+    bool valid_prev = false;
+    for (int k = k0; k <= k1; ++k) {
+        const float zk = c.near + (float)k * dz;
+        float bf[3], tt[3];
+        bool inside = true;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float pos = t0[a] + zk * dw[a];
+            const float g = (pos - org[a]) / v.voxel;
+            bf[a] = floorf(g);
+            tt[a] = g - bf[a];
+            inside = inside && bf[a] >= 0.0f && bf[a] <= (float)(n[a] - 2);      // (NaN and the infinities fail)
+        }
+        if (!inside) { valid_prev = false; continue; }      // no address is formed for such a sample
+        const float2 *p = vol + ((int64_t)(int)bf[2] * v.ny + (int)bf[1]) * v.nx + (int)bf[0];
+        const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
+        const float2 c000 = p[0], c100 = p[1], c010 = p[sy], c110 = p[sy + 1], c001 = p[sz], c101 = p[sz + 1], c011 = p[sz + sy], c111 = p[sz + sy + 1];
+        if (!(c000.y > 0.0f && c100.y > 0.0f && c010.y > 0.0f && c110.y > 0.0f && c001.y > 0.0f && c101.y > 0.0f && c011.y > 0.0f && c111.y > 0.0f)) {
+            valid_prev = false;
+            continue;
+        }
+        // along x, then y, then z
+        const float f = lerp1(lerp1(lerp1(c000.x, c100.x, tt[0]), lerp1(c010.x, c110.x, tt[0]), tt[1]),
+                              lerp1(lerp1(c001.x, c101.x, tt[0]), lerp1(c011.x, c111.x, tt[0]), tt[1]), tt[2]);
+        if (valid_prev) {
+            if (f_prev > 0.0f && f <= 0.0f) { depth = (c.near + (float)(k - 1) * dz) + dz * (f_prev / (f_prev - f)); break; }
+            if (f_prev <= 0.0f && f > 0.0f) break;           // a back face: no hit
+        }
+        f_prev = f;
+        valid_prev = true;
+    }
+    out[(int64_t)pv * c.w + pu] = depth;
+}
+
+bool finite_f(float x) { return fabsf(x) < INFINITY; }     // (NaN fails)
+
+const char *tsdf_volume_check(const ovo_tsdf_volume_t *d) {
+    if (!d) return "null pointer";
+    if (!(d->nx >= 2 && d->nx <= TSDF_MAX_DIM && d->ny >= 2 && d->ny <= TSDF_MAX_DIM && d->nz >= 2 && d->nz <= TSDF_MAX_DIM))
+        return "every dimension of the volume must be 2 .. 4096";
+    if ((int64_t)d->nx * d->ny * d->nz > TSDF_MAX_VOXELS) return "more than 2^31 voxels";
+    if (!(d->voxel > 0.0f && finite_f(d->voxel) && d->trunc > 0.0f && finite_f(d->trunc) && d->max_weight >= 1.0f && finite_f(d->max_weight)))
+        return "voxel and trunc must be > 0 and max_weight >= 1";
+    if (!(finite_f(d->origin[0]) && finite_f(d->origin[1]) && finite_f(d->origin[2]))) return "origin not finite";
+    return nullptr;
+}
+
+const char *tsdf_camera_check(const ovo_tsdf_camera_t *c) {
+    if (!c) return "null pointer";
+    if (!(c->h >= 1 && c->w >= 1 && (int64_t)c->h * c->w <= TSDF_MAX_PIXELS)) return "h, w >= 1 and h * w <= 2^26";
+    if (!(c->fx > 0.0f && c->fy > 0.0f && finite_f(c->fx) && finite_f(c->fy) && finite_f(c->cx) && finite_f(c->cy))) return "fx, fy > 0, all four finite";
+    if (!(c->near > 0.0f && c->near <= c->far)) return "0 < near <= far (NaN refused)";
+    return nullptr;
+}
+
+TsdfVol tsdf_vol(const ovo_tsdf_volume_t &d) { return TsdfVol{d.nx, d.ny, d.nz, d.voxel, d.origin[0], d.origin[1], d.origin[2], d.trunc, d.max_weight}; }
+
+TsdfCam tsdf_cam(const ovo_tsdf_camera_t &s) {
+    TsdfCam c;
+    for (int i = 0; i < 12; ++i) { c.c2w[i] = s.c2w[i]; c.w2c[i] = s.w2c[i]; }
+    c.fx = s.fx; c.fy = s.fy; c.cx = s.cx; c.cy = s.cy; c.h = s.h; c.w = s.w; c.near = s.near; c.far = s.far;
+    return c;
+}
+
+}  // namespace
+
+extern "C" size_t ovo_tsdf_volume_bytes(const ovo_tsdf_volume_t *desc) {
+    return tsdf_volume_check(desc) ? 0 : (size_t)desc->nx * (size_t)desc->ny * (size_t)desc->nz * sizeof(float2);
+}
+
+extern "C" int ovo_tsdf_integrate(void *vol, const ovo_tsdf_volume_t *desc, const float *depth, const ovo_tsdf_camera_t *cam, const int32_t *lo,
+                                  const int32_t *hi, ovo_stream_t stream) {
+    // everything is checked HERE, before anything is queued
+    OVO_REQUIRE(vol && desc && depth && cam && lo && hi, "null pointer");
+    const char *wrong = tsdf_volume_check(desc);
+    OVO_REQUIRE(!wrong, wrong);
+    wrong = tsdf_camera_check(cam);
+    OVO_REQUIRE(!wrong, wrong);
+    OVO_REQUIRE(((uintptr_t)vol & 15) == 0 && ((uintptr_t)depth & 3) == 0, "volume not 16-byte aligned (depth: 4)");
+    const int n[3] = {desc->nx, desc->ny, desc->nz};
+    for (int a = 0; a < 3; ++a) OVO_REQUIRE(lo[a] >= 0 && lo[a] < hi[a] && hi[a] <= n[a], "the box must lie inside the volume with lo < hi on every axis");
+    const TsdfBox b{lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
+    const bool pairs = (desc->nx & 1) == 0;                 // an even nx: every pair (2 q, 2 q + 1) of every row starts on a 16-byte boundary
+    const int64_t nq = pairs ? (int64_t)((b.x1 - 1) / 2 - b.x0 / 2 + 1) : (int64_t)(b.x1 - b.x0);
+    const int64_t items = nq * (b.y1 - b.y0) * (b.z1 - b.z0);
+    const int cap = ovo_knob_int("OVO_TSDF_GRID_CAP", 256 * 16);      // (tests: 2, so that every workgroup loops)
+    const int grid = ovo_grid(items, 256, cap > 0 ? cap : 256 * 16);
+    if (pairs) k_tsdf_integrate<2><<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, tsdf_vol(*desc), depth, tsdf_cam(*cam), b);
+    else k_tsdf_integrate<1><<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, tsdf_vol(*desc), depth, tsdf_cam(*cam), b);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
+
+extern "C" int ovo_tsdf_raycast(const void *vol, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, float *depth_out,
+                                ovo_stream_t stream) {
+    // everything is checked HERE, before anything is queued
+    OVO_REQUIRE(vol && desc && cam && depth_out, "null pointer");
+    const char *wrong = tsdf_volume_check(desc);
+    OVO_REQUIRE(!wrong, wrong);
+    wrong = tsdf_camera_check(cam);
+    OVO_REQUIRE(!wrong, wrong);
+    OVO_REQUIRE(finite_f(cam->far), "far must be finite for a march");
+    OVO_REQUIRE(((uintptr_t)vol & 15) == 0 && ((uintptr_t)depth_out & 3) == 0, "volume not 16-byte aligned (depth_out: 4)");
+    OVO_REQUIRE(dz > 0.0f && finite_f(dz), "dz must be > 0");
+    const double steps = ceil(((double)cam->far - (double)cam->near) / (double)dz);
+    OVO_REQUIRE(steps <= (double)TSDF_MAX_STEPS, "more than 4096 steps between near and far");
+    const int tiles_x = (cam->w + TSDF_TILE - 1) / TSDF_TILE, tiles_y = (cam->h + TSDF_TILE - 1) / TSDF_TILE;      // (tiles_x * tiles_y < 2^27)
+    k_tsdf_raycast<<<tiles_x * tiles_y, TSDF_TILE * TSDF_TILE, 0, (hipStream_t)stream>>>((const float2 *)vol, tsdf_vol(*desc), tsdf_cam(*cam), dz, (int)steps,
+                                                                                        tiles_x, depth_out);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}

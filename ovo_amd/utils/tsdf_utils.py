@@ -1,0 +1,127 @@
+"""A fused geometric model on the GPU: `TsdfVolume`, a dense truncated-signed-distance volume integrated from depth frames (`ovo_tsdf_integrate`)
+and ray-cast back into a depth image from any pose (`ovo_tsdf_raycast`): csrc/tsdf.hip, DESIGN.md section 17.  `frustum_box`, `rigid_inverse_f32`
+and `volume_desc` / `camera_desc` are pure numpy / ctypes and need no GPU."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .. import _lib as L
+
+Box = Tuple[Tuple[int, int, int], Tuple[int, int, int]]
+
+
+def _np(a, dtype) -> np.ndarray:
+    return np.asarray(a.detach().cpu() if isinstance(a, torch.Tensor) else a, dtype=dtype)
+
+
+def rigid_inverse_f32(c2w) -> np.ndarray:
+    """The rigid inverse of an f32 pose, formed in f64 (R^T, -R^T t) and rounded to f32 once: 4 x 4."""
+    m = _np(c2w, np.float32).astype(np.float64)
+    out = np.eye(4)
+    out[:3, :3] = m[:3, :3].T
+    out[:3, 3] = -(m[:3, :3].T @ m[:3, 3])
+    return out.astype(np.float32)
+
+
+def volume_desc(dims: Sequence[int], voxel: float, origin: Sequence[float], trunc: float, max_weight: float) -> L.TsdfVolume:
+    nx, ny, nz = (int(d) for d in dims)
+    return L.TsdfVolume(nx, ny, nz, float(voxel), (C.c_float * 3)(*(float(o) for o in origin)), float(trunc), float(max_weight))
+
+
+def camera_desc(K, h: int, w: int, c2w, near: float, far: float) -> L.TsdfCamera:
+    K, pose = _np(K, np.float32), np.eye(4, dtype=np.float32)
+    pose[:3] = _np(c2w, np.float32)[:3]
+    return L.TsdfCamera((C.c_float * 12)(*pose[:3].reshape(12)), (C.c_float * 12)(*rigid_inverse_f32(pose)[:3].reshape(12)), float(K[0, 0]), float(K[1, 1]),
+                        float(K[0, 2]), float(K[1, 2]), int(h), int(w), float(near), float(far))
+
+
+def frustum_box(dims: Sequence[int], voxel: float, origin: Sequence[float], trunc: float, K, h: int, w: int, c2w, near: float,
+                far: float) -> Optional[Box]:
+    """The index box (lo, hi), half-open, that holds every voxel a frame at `c2w` can update, or None when it misses the volume.  Host, f64: the
+    bounding box of the eight corners of the view frustum (the pixel square [-0.5, w - 0.5] x [-0.5, h - 0.5] at depth `near` and at depth
+    `far + trunc`: a voxel is updated up to `trunc` behind the deepest surface) and of the camera centre (a voxel in front of `near` is free space
+    and is updated too), grown by `trunc` plus one voxel, clipped to the volume."""
+    K, pose = _np(K, np.float32).astype(np.float64), _np(c2w, np.float32).astype(np.float64)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    f32 = lambda x: float(np.float32(x))
+    near, far, trunc, voxel = f32(near), f32(far), f32(trunc), f32(voxel)
+    pts = [pose[:3, 3]]
+    for z in (near, far + trunc):
+        for u in (-0.5, w - 0.5):
+            for v in (-0.5, h - 0.5):
+                pts.append(pose[:3, :3] @ np.array([(u - cx) / fx * z, (v - cy) / fy * z, z]) + pose[:3, 3])
+    pts = np.stack(pts)
+    if not np.isfinite(pts).all():
+        raise L.OvoHipError("frustum_box: pose or intrinsics not finite")
+    grow = trunc + voxel
+    org = np.array([f32(o) for o in origin], dtype=np.float64)
+    lo = np.floor((pts.min(0) - grow - org) / voxel).astype(np.int64)
+    hi = np.ceil((pts.max(0) + grow - org) / voxel).astype(np.int64) + 1
+    lo, hi = np.maximum(lo, 0), np.minimum(hi, np.asarray([int(d) for d in dims], dtype=np.int64))
+    if (lo >= hi).any():
+        return None
+    return tuple(int(x) for x in lo), tuple(int(x) for x in hi)
+
+
+class TsdfVolume:
+    """A dense TSDF volume on the device: `vol` is f32[nz, ny, nx, 2] = (F, W), zero = unobserved.  dims = (nx, ny, nz); voxel (i, j, k) sits at
+    origin + voxel * (i, j, k) in the frame the poses are given in.  512^3 is 1 GB."""
+
+    def __init__(self, dims: Sequence[int], voxel: float, origin: Sequence[float], trunc: float, max_weight: float = 64, device="cuda") -> None:
+        self.dims = tuple(int(d) for d in dims)
+        self.voxel, self.trunc, self.max_weight = float(voxel), float(trunc), float(max_weight)
+        self.origin = tuple(float(o) for o in origin)
+        if len(self.dims) != 3 or len(self.origin) != 3:
+            raise L.OvoHipError("TsdfVolume: dims and origin have three entries, x first")
+        self.desc = volume_desc(self.dims, self.voxel, self.origin, self.trunc, self.max_weight)
+        nbytes = int(L.load().ovo_tsdf_volume_bytes(C.byref(self.desc)))
+        if nbytes == 0:
+            raise L.OvoHipError(f"TsdfVolume: dims {self.dims} (each 2 .. 4096, at most 2^31 voxels), voxel {voxel}, trunc {trunc} (> 0) or "
+                                f"max_weight {max_weight} (>= 1) outside the limits")
+        nx, ny, nz = self.dims
+        self.vol = torch.zeros((nz, ny, nx, 2), dtype=torch.float32, device=device)
+        L.dev(self.vol, torch.float32, "volume")
+
+    def reset(self) -> None:
+        self.vol.zero_()
+
+    def frustum_box(self, K, h: int, w: int, c2w, near: float, far: float) -> Optional[Box]:
+        return frustum_box(self.dims, self.voxel, self.origin, self.trunc, K, h, w, c2w, near, far)
+
+    def integrate(self, depth: torch.Tensor, K, c2w, near: float = 0.05, far: float = 10.0, box: Optional[Box] = None) -> Optional[Box]:
+        """Fuses depth f32[h, w] (device) seen from `c2w` into the volume on the current stream; returns the box it visited (None: the frame's
+        frustum misses the volume and nothing was queued).  `box=None` visits `frustum_box(...)`, with the same bits as the whole volume."""
+        L.dev(depth, torch.float32, "depth")
+        if depth.dim() != 2:
+            raise L.OvoHipError(f"TsdfVolume.integrate: depth must be [h, w] (got {tuple(depth.shape)})")
+        h, w = int(depth.shape[0]), int(depth.shape[1])
+        if box is None:
+            box = self.frustum_box(K, h, w, c2w, near, far)
+            if box is None:
+                return None
+        cam = camera_desc(K, h, w, c2w, near, far)
+        lo, hi = (C.c_int32 * 3)(*(int(x) for x in box[0])), (C.c_int32 * 3)(*(int(x) for x in box[1]))
+        L.check(L.load().ovo_tsdf_integrate(L.ptr(self.vol), C.byref(self.desc), L.ptr(depth), C.byref(cam), lo, hi, L.stream()))
+        return box
+
+    def raycast(self, K, h: int, w: int, c2w, near: float, far: float, dz: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The model's depth image f32[h, w] from `c2w` on the current stream (0 = no surface); dz defaults to trunc / 2."""
+        dz = self.trunc / 2 if dz is None else float(dz)
+        if out is None:
+            out = torch.empty((int(h), int(w)), dtype=torch.float32, device=self.vol.device)
+        L.dev(out, torch.float32, "out")
+        if tuple(out.shape) != (int(h), int(w)):
+            raise L.OvoHipError(f"TsdfVolume.raycast: out must be [{h}, {w}] (got {tuple(out.shape)})")
+        cam = camera_desc(K, h, w, c2w, near, far)
+        L.check(L.load().ovo_tsdf_raycast(L.ptr(self.vol), C.byref(self.desc), C.byref(cam), dz, L.ptr(out), L.stream()))
+        return out
+
+
+def march_steps(near: float, far: float, dz: float) -> int:
+    """kmax of a ray cast: ceil((far - near) / dz) of the f32 values in f64."""
+    return int(math.ceil((float(np.float32(far)) - float(np.float32(near))) / float(np.float32(dz))))
