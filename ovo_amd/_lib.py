@@ -434,17 +434,19 @@ class PinnedRing:
     def next(self):
         """(sequence number, slot pointer) of the next call; the slot's sequence word is cleared first."""
         self.seq += 1
-        k = self.seq % self.slots
-        self.view[k, 0] = 0
-        return self.seq, self.base + k * self.slot_items * self.dtype.itemsize
+        self.view[self.seq % self.slots, 0] = 0
+        return self.seq, self.slot(self.seq)
+
+    def slot(self, seq: int) -> int:
+        """The address of the slot that call `seq` writes."""
+        return self.base + (seq % self.slots) * self.slot_items * self.dtype.itemsize
 
     def done(self, seq: int) -> bool:
         return int(self.view[seq % self.slots, 0]) == seq
 
     def wait(self, seq: int, timeout_us: int = 20_000_000):
-        k = seq % self.slots
-        check(self._wait(self.base + k * self.slot_items * self.dtype.itemsize, seq, timeout_us))
-        return self.view[k]
+        check(self._wait(self.slot(seq), seq, timeout_us))
+        return self.view[seq % self.slots]
 
     def __del__(self):
         try:

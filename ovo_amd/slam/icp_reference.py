@@ -1,0 +1,89 @@
+"""What `IcpTracker` aligns a frame to: the last keyframe's depth image (`KeyframeReference`, section 15) or a fused TSDF
+volume ray-cast at the last good pose (`TsdfReference`, section 17).  The tracker's frame loop is the same for both; a reference answers only what
+differs, through the same attributes and methods:
+
+    frame                    the prepared `Frame` the next alignment runs against
+    spare                    the pyramid buffer the next frame is written into (None: a new one); a LOST frame's own, set by the tracker
+    start(depth, aligner)    the first frame, at the identity pose
+    aim(aligner)             the device start pose before an alignment is queued
+    compose(c2w, kf_c2w, T)  an alignment's result T -> (the frame's pose, the pose relative to the keyframe that `keyframe_decision` takes)
+    tracked(cur, depth, c2w, is_kf, aligner)   after an OK frame at pose c2w; returns the outgoing keyframe's `Frame` when there is one
+
+`prepare(depth, out)` is the tracker's `prepare_frame` with its own intrinsics and thresholds.  The two forms of `compose` ARE the contract
+(tests/icp_restatement.py, tests/tsdf_restatement.py): each is kept one operation at a time, and they are not to be unified."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ..utils import icp_utils as U
+from ..utils import tsdf_utils
+
+EYE = np.eye(4, dtype=np.float32)
+
+
+class KeyframeReference:
+    """Every frame against the last keyframe's pyramid.  The device pose is carried from frame to frame (keyframe camera <- frame camera) and set
+    to the identity at a new keyframe; two pyramid buffers swap roles, unless the caller keeps the outgoing keyframe's and sets `spare` itself."""
+
+    def __init__(self, prepare) -> None:
+        self.prepare = prepare
+        self.frame = self.spare = None
+
+    def start(self, depth, aligner) -> None:
+        self.frame = self.prepare(depth, None)
+        aligner.set_pose(EYE)
+
+    def aim(self, aligner) -> None:
+        pass                                               # carried: the last alignment left its result there
+
+    def compose(self, c2w, kf_c2w, T):
+        return (kf_c2w @ T).astype(np.float32), T          # an f32 product; the keyframe is decided on T itself
+
+    def tracked(self, cur, depth, c2w, is_kf, aligner):
+        if not is_kf:
+            self.spare = cur.pyramid
+            return None
+        old, self.frame = self.frame, cur
+        aligner.set_pose(EYE)
+        self.spare = old.pyramid                           # (stream order: the next prepare is queued behind this frame's alignment)
+        return old
+
+
+class TsdfReference:
+    """Every frame, from the identity, against the volume ray-cast at the last good pose: an OK frame is fused at its pose and the model image
+    (`model_depth`) is cast again there; a LOST frame fuses nothing and the same image serves the next frame.  tsdf_origin None: the volume is
+    centred on the first camera, in the first camera's frame; tsdf_trunc None: 4 voxels; tsdf_far None: max_depth.  1 GB at 512^3."""
+
+    def __init__(self, prepare, K, max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far) -> None:
+        self.prepare, self.K = prepare, K
+        self.dims, self.voxel = tuple(int(d) for d in tsdf_dims), float(tsdf_voxel)
+        self.origin = tuple(-0.5 * self.voxel * (n - 1) for n in self.dims) if tsdf_origin is None else tuple(float(o) for o in tsdf_origin)
+        self.trunc = 4.0 * self.voxel if tsdf_trunc is None else float(tsdf_trunc)
+        self.max_weight, self.near = float(tsdf_max_weight), float(tsdf_near)
+        self.far = float(max_depth) if tsdf_far is None else float(tsdf_far)
+        self.volume = self.model_depth = self.frame = self.spare = self._eye = None
+
+    def start(self, depth, aligner) -> None:
+        self.volume = tsdf_utils.TsdfVolume(self.dims, self.voxel, self.origin, self.trunc, self.max_weight, device=depth.device)
+        self._eye = torch.eye(4, dtype=torch.float32, device=depth.device)[:3].reshape(12).contiguous()
+        self._fuse(depth, EYE)
+
+    def aim(self, aligner) -> None:
+        aligner.T.copy_(self._eye)                         # device to device: no host wait
+
+    def compose(self, c2w, kf_c2w, T):
+        c2w = (c2w.astype(np.float64) @ T.astype(np.float64)).astype(np.float32)      # an f64 product, rounded once
+        return c2w, U.rigid_inverse(kf_c2w) @ c2w.astype(np.float64)
+
+    def tracked(self, cur, depth, c2w, is_kf, aligner):
+        self.spare = cur.pyramid                           # (stream order: the next prepare is queued behind this frame's alignment)
+        self._fuse(depth, c2w)
+        return None
+
+    def _fuse(self, depth, c2w) -> None:
+        """Fuses a tracked frame at its pose and ray-casts the model there for the next frame: queued, not waited for."""
+        h, w = int(depth.shape[0]), int(depth.shape[1])
+        self.volume.integrate(depth, self.K, c2w, self.near, self.far)
+        self.model_depth = self.volume.raycast(self.K, h, w, c2w, self.near, self.far, out=self.model_depth)
+        self.frame = self.prepare(self.model_depth, None if self.frame is None else self.frame.pyramid)

@@ -1,27 +1,33 @@
 """A live tracker behind the seam `WrapperORBSLAM` calls (slam/orbslam.py): geometry-only pose from depth, multi-scale projective point-to-plane
-ICP of every frame against the last keyframe (csrc/icp.hip).  The reference gets the same capability from Open3D's RGB-D
+ICP of every frame against a reference model (csrc/icp.hip).  The reference gets the same capability from Open3D's RGB-D
 odometry in its Gaussian-SLAM back end (ovo/submodules/gaussian_slam/entities/visual_odometer.py); here the alignment runs on the GPU with the
 pose device-resident, and the host reads one pinned result block per frame.
 
 The seven methods follow `ReplayTracker`'s conventions: a trajectory / keyframe row is 13 f32 -- the frame's time stamp, then the top three rows
 of its pose (camera to the FIRST frame's camera; `WrapperORBSLAM` puts `world_ref` in front).
 
-`close_loops=True` adds loop detection, verification and correction on keyframes: the new keyframe is aligned against
-the old keyframes its own pose estimate puts nearby -- all of them in the launches of one alignment (`ovo_icp_align_batch`) -- the ones that
-pass become edges of a pose graph (slam/pose_graph.py), and when the optimised graph moves a keyframe the keyframe rows are replaced and the
-big-change index goes up, which is what `WrapperORBSLAM.map` re-anchors its map on.
+`process_image_rgbd` is the one frame loop: prepare the frame, queue one alignment and wait for it, LOST or a pose, the
+row, the keyframe decision, buffers handed back.  What a frame is aligned to is a reference model (slam/icp_reference.py), which answers only
+what differs between the two:
 
-`model="tsdf"` tracks frame to MODEL: every tracked frame is fused into a dense TSDF volume (utils/tsdf_utils.py,
-csrc/tsdf.hip), and a frame is aligned to the volume's ray-cast depth image from the last good pose instead of to the keyframe's raw image."""
+`model="keyframe"`: the last keyframe's depth image (`KeyframeReference`).
+`model="tsdf"`: frame to MODEL (`TsdfReference`) -- every tracked frame is fused into a dense TSDF volume
+(utils/tsdf_utils.py, csrc/tsdf.hip), and a frame is aligned to the volume's ray-cast depth image from the last good pose.
+
+`close_loops=True` adds loop detection, verification and correction on keyframes (`LoopCloser`, slam/loop_closer.py): the
+new keyframe is aligned against the old keyframes its own pose estimate puts nearby -- all of them in the launches of one alignment
+(`ovo_icp_align_batch`) -- the ones that pass become edges of a pose graph (slam/pose_graph.py), and when the optimised graph moves a keyframe
+the tracker replaces the keyframe rows and the big-change index goes up, which is what `WrapperORBSLAM.map` re-anchors its map on."""
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional
+from typing import Any, List, Optional
 
 import numpy as np
 import torch
 
 from ..utils import icp_utils as U
-from . import pose_graph
+from .icp_reference import KeyframeReference, TsdfReference
+from .loop_closer import LoopCloser
 
 
 class IcpTracker:
@@ -35,7 +41,8 @@ class IcpTracker:
                  loop_min_overlap: float = 0.3, loop_max_rms: float = 0.02, loop_max_correction=(0.3, 10.0), loop_min_shift=(0.01, 0.2),
                  loop_max_keyframes: int = 256, model: str = "keyframe", tsdf_dims=(512, 512, 512), tsdf_voxel: float = 0.02, tsdf_origin=None,
                  tsdf_trunc=None, tsdf_max_weight: float = 64, tsdf_near: float = 0.05, tsdf_far=None) -> None:
-        """No GPU work happens here: buffers are made with the first frame.
+        """No GPU work happens here: buffers are made with the first frame.  The loop_* parameters are read and checked by `LoopCloser`, the
+        tsdf_* parameters by `TsdfReference`, whichever mode is chosen.
 
         close_loops: every new keyframe n (its position in the keyframe list) is verified against the kept keyframes k <= n - loop_min_gap whose
         guess X_k^-1 X_n lies within loop_radius (m) and loop_angle_deg -- the loop_max_candidates (<= 16) nearest, one `ovo_icp_align_batch` call
@@ -62,54 +69,33 @@ class IcpTracker:
         self.min_pairs_frac, self.min_pivot_ratio = float(min_pairs_frac), float(min_pivot_ratio)
         self.kf_translation, self.kf_rotation_deg, self.kf_min_overlap = float(kf_translation), float(kf_rotation_deg), float(kf_min_overlap)
         self.close_loops = bool(close_loops)
-        self.loop_min_gap, self.loop_max_candidates, self.loop_max_keyframes = int(loop_min_gap), int(loop_max_candidates), int(loop_max_keyframes)
-        self.loop_radius, self.loop_angle_deg, self.loop_dist_th = float(loop_radius), float(loop_angle_deg), float(loop_dist_th)
-        self.loop_iters = self.iters if loop_iters is None else tuple(int(i) for i in loop_iters)
-        self.loop_min_overlap, self.loop_max_rms = float(loop_min_overlap), float(loop_max_rms)
-        self.loop_max_correction = tuple(float(x) for x in loop_max_correction)
-        self.loop_min_shift = tuple(float(x) for x in loop_min_shift)
-        if not (self.loop_min_gap >= 1 and 1 <= self.loop_max_candidates <= U.MAX_BATCH and self.loop_max_keyframes >= 1):
-            raise ValueError(f"IcpTracker: loop_min_gap and loop_max_keyframes must be >= 1 and loop_max_candidates 1 .. {U.MAX_BATCH}")
-        if len(self.loop_iters) != self.levels or min(self.loop_iters) < 0 or sum(self.loop_iters) < 1:
-            raise ValueError("IcpTracker: loop_iters needs one entry per level, coarse to fine, none negative and not all 0")
-        if len(self.loop_max_correction) != 2 or len(self.loop_min_shift) != 2 or min(self.loop_max_correction) <= 0 or min(self.loop_min_shift) < 0:
-            raise ValueError("IcpTracker: loop_max_correction (> 0) and loop_min_shift (>= 0) are (metres, degrees)")
-        if not (self.loop_radius > 0 and self.loop_angle_deg > 0 and self.loop_dist_th > 0 and 0 <= self.loop_min_overlap <= 1 and self.loop_max_rms > 0):
-            raise ValueError("IcpTracker: loop_radius, loop_angle_deg, loop_dist_th and loop_max_rms must be > 0 and loop_min_overlap in [0, 1]")
+        self._loops = LoopCloser(self.iters, self.normal_th_deg, self.min_pivot_ratio, loop_min_gap, loop_radius, loop_angle_deg, loop_max_candidates,
+                                 loop_iters, loop_dist_th, loop_min_overlap, loop_max_rms, loop_max_correction, loop_min_shift, loop_max_keyframes)
+        self.loop_iters = self._loops.iters
         self.model = str(model)
         if self.model not in ("keyframe", "tsdf"):
             raise ValueError(f"IcpTracker: model must be 'keyframe' or 'tsdf' (got {model!r})")
         if self.model == "tsdf" and self.close_loops:
             raise ValueError("IcpTracker: model='tsdf' with close_loops=True is not built: a corrected trajectory would need the volume fused again")
-        self.tsdf_dims, self.tsdf_voxel = tuple(int(d) for d in tsdf_dims), float(tsdf_voxel)
-        self.tsdf_origin = None if tsdf_origin is None else tuple(float(o) for o in tsdf_origin)
-        self.tsdf_trunc = 4.0 * self.tsdf_voxel if tsdf_trunc is None else float(tsdf_trunc)
-        self.tsdf_max_weight, self.tsdf_near = float(tsdf_max_weight), float(tsdf_near)
-        self.tsdf_far = self.max_depth if tsdf_far is None else float(tsdf_far)
-        self.volume: Any = None                            # model="tsdf": the TsdfVolume, made with the first frame
-        self.model_depth: Optional[torch.Tensor] = None    # model="tsdf": the last ray-cast image, what the next frame is aligned to
-        self._model: Optional[U.Frame] = None              # its pyramid
-        self._eye: Optional[torch.Tensor] = None           # the identity start pose, on the device
+        # (read in either mode, as the loop parameters are: tsdf_trunc and tsdf_far are the tracker's attributes whatever the model)
+        tsdf = TsdfReference(self._prepare, self.K, self.max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far)
+        self.tsdf_trunc, self.tsdf_far = tsdf.trunc, tsdf.far
+        self._ref = tsdf if self.model == "tsdf" else KeyframeReference(self._prepare)
         self.device = device
         self._aligner: Optional[U.Aligner] = None
-        self._kf: Optional[U.Frame] = None                 # the last keyframe's pyramid
-        self._spare: Optional[torch.Tensor] = None         # the buffer the next frame's pyramid is written into
         self._kf_c2w = np.eye(4, dtype=np.float32)
         self._c2w = np.eye(4, dtype=np.float32)            # the pose of the last good frame
         self._row = None
         self._state = self.LOST
         self._is_kf = False
         self._keyframes: List[np.ndarray] = []
-        self.last: Any = None                              # the last alignment's result (None for a keyframe-initialising first frame)
+        self.last: Any = None                              # the last alignment's result (None for the first frame)
         self.closed = False
-        # close_loops: the pose graph (f64), the kept pyramids by keyframe index (oldest first), what the last closure did
-        self._batch: Optional[U.BatchAligner] = None
-        self._X: List[np.ndarray] = [np.eye(4)]
-        self._edges: List[Any] = []
-        self._db: Dict[int, U.Frame] = {}
-        self._big_change = 0
-        self.loop_edges: List[Any] = []                    # (reference keyframe index, current keyframe index) of every accepted edge
-        self.last_loop: Any = None                         # the last verification: {"n", "candidates", "results", "accepted", "applied", "graph"}
+
+    volume = property(lambda self: getattr(self._ref, "volume", None))             # model="tsdf": the TsdfVolume, made with the first frame
+    model_depth = property(lambda self: getattr(self._ref, "model_depth", None))   # model="tsdf": the last ray-cast image, what the next frame is aligned to
+    loop_edges = property(lambda self: self._loops.loop_edges)                     # close_loops: see LoopCloser
+    last_loop = property(lambda self: self._loops.last_loop)
 
     def _row_of(self, t, c2w: np.ndarray) -> np.ndarray:
         return np.concatenate([np.asarray([t], dtype=np.float32), np.asarray(c2w, dtype=np.float32)[:3].reshape(12)])
@@ -119,126 +105,47 @@ class IcpTracker:
             depth = torch.from_numpy(np.ascontiguousarray(np.asarray(depth, dtype=np.float32)))
         return depth.to(device=self.device, dtype=torch.float32).contiguous()
 
+    def _prepare(self, depth: torch.Tensor, out: Optional[torch.Tensor]) -> U.Frame:
+        return U.prepare_frame(depth, self.K, self.levels, self.max_depth, self.depth_jump, out=out)
+
     def process_image_rgbd(self, rgb, depth, t) -> None:
-        """Tracks one frame (the colour image takes no part); returns when its pose is on the host: one host wait per frame."""
+        """Tracks one frame (the colour image takes no part); returns when its pose is on the host: one host wait per frame, and one more on a
+        keyframe whose loop candidates are verified."""
         if self.closed:
             raise RuntimeError("IcpTracker: shut down")
-        depth = self._depth(depth)
-        if self.model == "tsdf":
-            return self._process_model(depth, t)
-        cur = U.prepare_frame(depth, self.K, self.levels, self.max_depth, self.depth_jump, out=self._spare)
-        self._spare = None
-        if self._kf is None:                               # the first frame: the identity pose, a keyframe
+        depth, ref = self._depth(depth), self._ref
+        if self._aligner is None:                          # the first frame: the identity pose, a keyframe
             self._aligner = U.Aligner(depth.device)
-            self._aligner.set_pose(np.eye(4, dtype=np.float32))
-            self._kf, self._state, self._is_kf, self.last = cur, self.OK, True, None
-            self._row = self._row_of(t, self._c2w)
-            self._keyframes.append(self._row)
-            return
-        pixels = cur.h * cur.w
-        seq = self._aligner.queue(self._kf, cur, self.iters, self.dist_th, self.normal_th_deg, int(np.ceil(self.min_pairs_frac * pixels)),
-                                  self.min_pivot_ratio)
-        self.last = res = self._aligner.wait(seq)
-        self._is_kf = False
-        if res["state"] != U.OK:                           # the pose stays that of the last good frame; the device T kept its value too
-            self._state = self.LOST
-            self._spare = cur.pyramid
-            return
-        self._state = self.OK
-        self._c2w = (self._kf_c2w @ res["T"]).astype(np.float32)
-        self._row = self._row_of(t, self._c2w)
-        if U.keyframe_decision(res["T"], res["pairs"], pixels, self.kf_translation, self.kf_rotation_deg, self.kf_min_overlap):
-            old = self._kf
-            self._kf, self._kf_c2w, self._is_kf = cur, self._c2w, True
-            self._aligner.set_pose(np.eye(4, dtype=np.float32))
-            self._keyframes.append(self._row)
-            if self.close_loops:
-                self._close_loop(old, cur, res, pixels)
-            else:
-                self._spare = old.pyramid                  # (stream order: the next prepare is queued behind this frame's alignment)
-        else:
-            self._spare = cur.pyramid
-
-    def _process_model(self, depth: torch.Tensor, t) -> None:
-        """model="tsdf": one frame against the ray-cast model; one host wait."""
-        h, w = int(depth.shape[0]), int(depth.shape[1])
-        if self.volume is None:                            # the first frame: the identity pose, a keyframe, fused
-            from ..utils.tsdf_utils import TsdfVolume
-            origin = self.tsdf_origin
-            if origin is None:
-                origin = tuple(-0.5 * self.tsdf_voxel * (n - 1) for n in self.tsdf_dims)
-            self.volume = TsdfVolume(self.tsdf_dims, self.tsdf_voxel, origin, self.tsdf_trunc, self.tsdf_max_weight, device=depth.device)
-            self._aligner = U.Aligner(depth.device)
-            self._eye = torch.eye(4, dtype=torch.float32, device=depth.device)[:3].reshape(12).contiguous()
+            ref.start(depth, self._aligner)
             self._state, self._is_kf, self.last = self.OK, True, None
             self._row = self._row_of(t, self._c2w)
             self._keyframes.append(self._row)
-            self._fuse(depth, h, w)
             return
-        cur = U.prepare_frame(depth, self.K, self.levels, self.max_depth, self.depth_jump, out=self._spare)
-        self._spare = cur.pyramid                          # (stream order: the next prepare is queued behind this frame's alignment)
-        self._aligner.T.copy_(self._eye)                   # device to device: no host wait
-        pixels = h * w
-        seq = self._aligner.queue(self._model, cur, self.iters, self.dist_th, self.normal_th_deg, int(np.ceil(self.min_pairs_frac * pixels)),
-                                  self.min_pivot_ratio)
+        cur = self._prepare(depth, ref.spare)
+        ref.aim(self._aligner)
+        pixels = cur.h * cur.w
+        min_pairs = int(np.ceil(self.min_pairs_frac * pixels))
+        seq = self._aligner.queue(ref.frame, cur, self.iters, self.dist_th, self.normal_th_deg, min_pairs, self.min_pivot_ratio)
         self.last = res = self._aligner.wait(seq)
         self._is_kf = False
-        if res["state"] != U.OK:                           # pose, volume and model image stay
+        if res["state"] != U.OK:                           # the pose stays that of the last good frame, and the reference as it was
             self._state = self.LOST
+            ref.spare = cur.pyramid
             return
         self._state = self.OK
-        self._c2w = (self._c2w.astype(np.float64) @ res["T"].astype(np.float64)).astype(np.float32)
+        self._c2w, relative = ref.compose(self._c2w, self._kf_c2w, res["T"])
         self._row = self._row_of(t, self._c2w)
-        if U.keyframe_decision(U.rigid_inverse(self._kf_c2w) @ self._c2w.astype(np.float64), res["pairs"], pixels, self.kf_translation,
-                               self.kf_rotation_deg, self.kf_min_overlap):
+        if U.keyframe_decision(relative, res["pairs"], pixels, self.kf_translation, self.kf_rotation_deg, self.kf_min_overlap):
             self._kf_c2w, self._is_kf = self._c2w, True
             self._keyframes.append(self._row)
-        self._fuse(depth, h, w)
-
-    def _fuse(self, depth: torch.Tensor, h: int, w: int) -> None:
-        """Fuses a tracked frame at the current pose and ray-casts the model there for the next frame: queued, not waited for."""
-        self.volume.integrate(depth, self.K, self._c2w, self.tsdf_near, self.tsdf_far)
-        self.model_depth = self.volume.raycast(self.K, h, w, self._c2w, self.tsdf_near, self.tsdf_far, out=self.model_depth)
-        self._model = U.prepare_frame(self.model_depth, self.K, self.levels, self.max_depth, self.depth_jump,
-                                      out=None if self._model is None else self._model.pyramid)
-
-    def _close_loop(self, old: U.Frame, cur: U.Frame, res, pixels: int) -> None:
-        """The new keyframe `cur` (aligned to the outgoing keyframe `old` with result `res`): extend the graph, keep `old`'s pyramid, verify the
-        candidates in one batch, and apply the optimised graph if it moves a keyframe."""
-        n = len(self._keyframes) - 1
-        self._X.append(self._X[n - 1] @ res["T"].astype(np.float64))
-        self._edges.append((n - 1, n, res["T"].astype(np.float64), U.information(res["sums"])))
-        self._db[n - 1] = old
-        if len(self._db) > self.loop_max_keyframes:       # the oldest leaves the candidate set (it stays a node); its buffer takes the next frame
-            self._spare = self._db.pop(next(iter(self._db))).pyramid
-        candidates = U.select_candidates(self._X, n, list(self._db), self.loop_min_gap, self.loop_radius, self.loop_angle_deg, self.loop_max_candidates)
-        self.last_loop = {"n": n, "candidates": [k for k, _ in candidates], "results": [], "accepted": [], "applied": False, "graph": None}
-        if not candidates:
-            return
-        if self._batch is None:
-            self._batch = U.BatchAligner(cur.pyramid.device)
-        seq = self._batch.queue([self._db[k] for k, _ in candidates], cur, [G for _, G in candidates], self.loop_iters, self.loop_dist_th,
-                                self.normal_th_deg, int(np.ceil(self.min_pairs_frac * pixels)), self.min_pivot_ratio)
-        results = self._batch.wait(seq)                    # the one extra host wait of such a keyframe
-        self.last_loop["results"] = results
-        for (k, G), r in zip(candidates, results):
-            if U.accept_loop(r, G, pixels, self.loop_min_overlap, self.loop_max_rms, self.loop_max_correction):
-                self._edges.append((k, n, r["T"].astype(np.float64), U.information(r["sums"])))
-                self.loop_edges.append((k, n))
-                self.last_loop["accepted"].append(k)
-        if not self.last_loop["accepted"]:
-            return
-        X, info = pose_graph.optimise(self._X, self._edges)
-        self.last_loop["graph"] = info
-        shifts = [U.pose_offset(U.rigid_inverse(a) @ b) for a, b in zip(self._X, X)]
-        if not (info["improved"] and any(t > self.loop_min_shift[0] or a > self.loop_min_shift[1] for t, a in shifts)):
-            return                                         # the edges stay in the graph; nothing else changes
-        self._X = X
-        self._keyframes = [self._row_of(row[0], x) for row, x in zip(self._keyframes, X)]      # rounded to f32
-        self._kf_c2w = self._c2w = X[n].astype(np.float32)
-        self._row = self._keyframes[n]
-        self._big_change += 1
-        self.last_loop["applied"] = True
+        old = ref.tracked(cur, depth, self._c2w, self._is_kf, self._aligner)
+        if self._is_kf and self.close_loops:               # `old`'s pyramid is kept: the next frame takes the one that became free, or a new one
+            n = len(self._keyframes) - 1
+            X, ref.spare = self._loops.keyframe(n, old, cur, res, pixels, min_pairs)
+            if X is not None:                              # a closure moved the keyframes: their rows, rounded to f32, and this frame's pose
+                self._keyframes = [self._row_of(row[0], x) for row, x in zip(self._keyframes, X)]
+                self._kf_c2w = self._c2w = X[n].astype(np.float32)
+                self._row = self._keyframes[n]
 
     def _need_frame(self) -> None:
         if self._row is None:
@@ -257,13 +164,12 @@ class IcpTracker:
         return self._is_kf
 
     def get_last_big_change_idx(self) -> int:
-        return self._big_change                            # goes up when a closure moved the keyframes (always 0 without close_loops)
+        return self._loops.big_change                      # goes up when a closure moved the keyframes (always 0 without close_loops)
 
     def get_keyframe_points(self):
         return list(self._keyframes)
 
     def shutdown(self) -> None:
-        self._aligner = self._kf = self._spare = self._batch = None
-        self.volume = self.model_depth = self._model = self._eye = None
-        self._db = {}
+        self._aligner = self._ref = None                   # with the reference go the keyframe's pyramid, or the volume and its image
+        self._loops.release()
         self.closed = True

@@ -1,5 +1,7 @@
 """Point-to-plane ICP between two depth frames: `ovo_icp_prepare` / `ovo_icp_align` (csrc/icp.hip) and the host-side
-arithmetic around them, and `ovo_icp_align_batch` with the loop-closing rules of `IcpTracker(close_loops=True)`.  The host
+arithmetic around them, and `ovo_icp_align_batch` with the loop-closing rules that `LoopCloser` (slam/loop_closer.py) applies for
+`IcpTracker(close_loops=True)`.  `prepare_frame`, `Aligner` and `BatchAligner` are what the tracker's frame loop reaches on the
+device; it looks them up here when it calls them.  The host
 helpers (`se3_exp`, `se3_log`, `level_intrinsics`, `keyframe_decision`, `pose_offset`, `select_candidates`, `accept_loop`, `information`) are pure
 numpy and need no GPU."""
 from __future__ import annotations
@@ -253,7 +255,7 @@ class BatchAligner:
 
     def wait(self, seq: int) -> List[Dict[str, Any]]:
         m = self._m.pop(seq)
-        base = self.ring.base + (seq % self.ring.slots) * self.ring.slot_items * 8
+        base = self.ring.slot(seq)
         for k in range(m):                                 # the blocks are written by m workgroups in no particular order
             L.check(L.load().ovo_host_wait64(base + k * RESULT_WORDS * 8, seq, 20_000_000))
         blocks = self.ring.view[seq % self.ring.slots].reshape(MAX_BATCH, RESULT_WORDS)
