@@ -106,7 +106,10 @@ int ovo_depth_filter(const float *depth, int h, int w, int ksize, float sigma, f
  *   hist       i32[n_masks, hist_cols] (zeroed here): votes[mask][ins_id+1], column 0 = unassigned
  *              points; hist_cols must be > max instance id + 1            (ovo.py:257-264 inputs)
  *   counters   i64[2]: {points in frustum, points matched}  (zeroed here)
- * point_ins: i32[n] current instance id per point (-1 = none). */
+ * point_ins: i32[n] current instance id per point (-1 = none).
+ * What the kernel does with seg-map values it has no mask for (the reference indexes its tensors with them):
+ *   - a seg id >= n_masks counts as unlabelled: the point is matched, point_seg = -1, no vote, and the id's pixels add to no mask's area;
+ *   - a remapped pixel (u', v') outside [0, seg_w) x [0, seg_h) is not read: the point counts as matched and unlabelled (point_seg = -1). */
 int ovo_track_project(const float *pts, const int32_t *point_ins, int64_t n, const ovo_camera_t *cam,
                       const float *depth, const int32_t *seg_map, int seg_h, int seg_w, ovo_ratio_t ratio,
                       int16_t *point_seg, int32_t *hist, int n_masks, int hist_cols, int64_t *counters,
@@ -963,7 +966,10 @@ int ovo_map_step(const ovo_map_step_t *a, ovo_stream_t stream);
  *   [0] seq  [1] map points  [2] points in frustum  [3] points matched  [4] next instance id after  [5] before  [6..7] 0
  *   per mask: {matched points, of which assigned, mode id, seg-map area, target id (-1 none), fused area (-1: no other mask joined)}
  * point_seg i16[>= n_upper] as ovo_track_project writes it.  masks u8[n_masks, pixels] (pixels % 16 == 0) are fused IN PLACE;
- * NULL skips the fusion.  next_ins: device i32[1]; next_ins_host >= 0 = the host's exact copy (used instead), -1 = read it. */
+ * NULL skips the fusion.  next_ins: device i32[1]; next_ins_host >= 0 = the host's exact copy (used instead), -1 = read it; either way
+ * the device value is overwritten with the next id after this keyframe.  As in ovo_track_project, seg ids >= n_masks and remapped pixels
+ * outside the seg map count as unlabelled (-1): such points are in [3] "points matched" and in no mask's row, and are not listed in hits.
+ * With the map's size read on the device (map.n < 0), rows [state[0], n_upper) of xyz / ins / point_seg are neither read nor written. */
 typedef struct {
     ovo_map_ref_t map;
     const float *depth; int32_t filter_depth; float *depth_scratch;
