@@ -924,6 +924,45 @@ int ovo_tsdf_integrate(void *vol, const ovo_tsdf_volume_t *desc, const float *de
                        ovo_stream_t stream);
 int ovo_tsdf_raycast(const void *vol, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, float *depth_out, ovo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The volume's surface as a triangle mesh (ABI v23; restated in tests/mesh_restatement.py): marching tetrahedra on the
+ * Kuhn triangulation of every cell of the half-open index box [lo, hi) (host int32[3] each, hi - lo >= 2 on every axis).  The mesh is welded
+ * (indexed, shared vertices) and, where the surface does not run into unobserved space or the box, watertight.  Every floating-point step is one
+ * f32 IEEE operation.
+ *
+ * OBSERVED: a voxel with W >= min_weight and |F| <= 1 (a NaN fails).  INSIDE: observed and F < 0 (0 and -0 are outside).
+ * CELL (i, j, k): the corners base + {0,1}^3, all inside the box; VALID iff all eight are observed.  Only valid cells emit.
+ * TETRAHEDRA: six per cell; tetrahedron n belongs to the n-th permutation pi of the axes (0, 1, 2) in lexicographic order (axis 0 = x) and has
+ *   the corners c0 = (0,0,0), c1 = c0 + e_pi0, c2 = c1 + e_pi1, c3 = (1,1,1); its mask is m = sum [inside(c_r)] << r.  m = 0, 15: nothing.
+ *   One corner r alone on its side (either side): one triangle, its vertices on the edges from c_r to the other corners in increasing order of
+ *   the other corner.  Two against two: with {a0 < a1} the pair that holds corner 0 and {b0 < b1} the other, the quad (a0b0, a0b1, a1b1, a1b0)
+ *   cut into (q0, q1, q2) and (q0, q2, q3).
+ * WINDING: the last two vertices of a triangle are swapped if needed so that, corners at their integer offsets and edge vertices at the edge
+ *   midpoints, (v1 - v0) x (v2 - v0) . (mean of the outside corners - mean of the inside corners) > 0: normals point into free space.
+ *   The table of all 6 x 16 cases is computed from these words (tools/gen_mesh_table.py -> csrc/mesh_table.h), never typed.
+ * VERTICES: a voxel owns seven edge slots, from itself to + (1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1) in that order; every
+ *   edge of every tetrahedron is exactly one slot of one voxel.  A slot carries a vertex iff an emitted triangle uses it.  With p the owner
+ *   (volume indices) and q = p + offset:  t = F_p / (F_p - F_q),  g[a] = (float)p[a] + t * (float)(q[a] - p[a]),  pos[a] = origin[a] + voxel * g[a]
+ *   (the product rounded, then the sum).  Vertex order: owner voxel in linear order over the box (z slowest, x fastest), then slot.
+ * TRIANGLES: faces int32[T][3] index the vertex list; order: cell in the same linear order, then tetrahedron n, then triangle.  Degenerate
+ *   triangles (t = 0 at an outside corner with F == 0) are kept, so that the topology stays closed.
+ *
+ * ovo_tsdf_mesh_workspace_bytes: 256 + 8 bytes per x-row of the box + 8 bytes per voxel of the box, each part rounded up to 256; 0 for a
+ *   descriptor or box the other calls refuse.
+ * ovo_tsdf_mesh_plan: classifies the cells, marks the used slots and turns per-voxel vertex counts and per-cell triangle counts into offsets, all
+ *   in this library (a memset and three launches); writes counts int64[2] = (V, T), which may be device or pinned host memory.
+ * ovo_tsdf_mesh_emit: fills vertices f32[V][3] and faces i32[T][3] from the planned workspace (one launch) with the same vol, desc, lo, hi and
+ *   min_weight.  Before it queues anything it reads the plan's 32-byte head back from the workspace, which waits for the stream; a plan made
+ *   for another volume shape, box or min_weight, or whose (V, T) differ from the ones given, is refused.
+ * The result is a pure function of the inputs: bit-equal from run to run and for any grid (the only atomic is an OR into the slot flags).
+ * OVO_E_ARG, nothing launched (both): a null pointer, a descriptor outside its limits, a box outside the volume or thinner than 2, min_weight < 1
+ * or NaN, a volume or workspace not 16-byte aligned, ws_bytes too small; emit: V or T negative or above 2^31 - 1, or not the plan's. */
+size_t ovo_tsdf_mesh_workspace_bytes(const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi);
+int ovo_tsdf_mesh_plan(const void *vol, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight, void *ws, size_t ws_bytes,
+                       int64_t *counts, ovo_stream_t stream);
+int ovo_tsdf_mesh_emit(const void *vol, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight, const void *ws,
+                       size_t ws_bytes, float *vertices, int32_t *faces, int64_t V, int64_t T, ovo_stream_t stream);
+
 
 /* =============================================================================================
  * The keyframe chain without host round trips (MI355X extension of a6 / a9; what the reference does with a `.sum()` / vstack

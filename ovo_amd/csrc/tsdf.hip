@@ -12,16 +12,14 @@
 
 #include "common.h"
 #include "projection.h"
+#include "tsdf_desc.h"
 
 namespace {
 
-constexpr int64_t TSDF_MAX_VOXELS = (int64_t)1 << 31;
 constexpr int64_t TSDF_MAX_PIXELS = (int64_t)1 << 26;
-constexpr int TSDF_MAX_DIM = 4096;
 constexpr int TSDF_MAX_STEPS = 4096;                       // the largest kmax of a march
 constexpr int TSDF_TILE = 16;                              // ray-cast pixel tiles: a wave is 4 rows of 16 pixels
 
-struct TsdfVol { int nx, ny, nz; float voxel, ox, oy, oz, trunc, max_weight; };
 struct TsdfCam { float c2w[12], w2c[12], fx, fy, cx, cy; int h, w; float near, far; };
 struct TsdfBox { int x0, y0, z0, x1, y1, z1; };
 
@@ -155,19 +153,6 @@ __global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const flo
     out[(int64_t)pv * c.w + pu] = depth;
 }
 
-bool finite_f(float x) { return fabsf(x) < INFINITY; }     // (NaN fails)
-
-const char *tsdf_volume_check(const ovo_tsdf_volume_t *d) {
-    if (!d) return "null pointer";
-    if (!(d->nx >= 2 && d->nx <= TSDF_MAX_DIM && d->ny >= 2 && d->ny <= TSDF_MAX_DIM && d->nz >= 2 && d->nz <= TSDF_MAX_DIM))
-        return "every dimension of the volume must be 2 .. 4096";
-    if ((int64_t)d->nx * d->ny * d->nz > TSDF_MAX_VOXELS) return "more than 2^31 voxels";
-    if (!(d->voxel > 0.0f && finite_f(d->voxel) && d->trunc > 0.0f && finite_f(d->trunc) && d->max_weight >= 1.0f && finite_f(d->max_weight)))
-        return "voxel and trunc must be > 0 and max_weight >= 1";
-    if (!(finite_f(d->origin[0]) && finite_f(d->origin[1]) && finite_f(d->origin[2]))) return "origin not finite";
-    return nullptr;
-}
-
 const char *tsdf_camera_check(const ovo_tsdf_camera_t *c) {
     if (!c) return "null pointer";
     if (!(c->h >= 1 && c->w >= 1 && (int64_t)c->h * c->w <= TSDF_MAX_PIXELS)) return "h, w >= 1 and h * w <= 2^26";
@@ -175,8 +160,6 @@ const char *tsdf_camera_check(const ovo_tsdf_camera_t *c) {
     if (!(c->near > 0.0f && c->near <= c->far)) return "0 < near <= far (NaN refused)";
     return nullptr;
 }
-
-TsdfVol tsdf_vol(const ovo_tsdf_volume_t &d) { return TsdfVol{d.nx, d.ny, d.nz, d.voxel, d.origin[0], d.origin[1], d.origin[2], d.trunc, d.max_weight}; }
 
 TsdfCam tsdf_cam(const ovo_tsdf_camera_t &s) {
     TsdfCam c;

@@ -651,6 +651,11 @@ class FramePipeline:
         pre-queued and not under `emulate`, as `render_view`."""
         return self.ovo.instance_boxes(self._settled_map("instance_boxes"), oriented=oriented)
 
+    def semantic_mesh(self, vertices, faces, **kw):
+        """`OVO.semantic_mesh` of the pipeline's own map (`transform=`, `classes=`, `template=`, `th=`, `max_dist=`); on every rank, with
+        `instance_boxes`' refusals."""
+        return self.ovo.semantic_mesh(self._settled_map("semantic_mesh"), vertices, faces, **kw)
+
     def locate(self, queries, **kw):
         """`OVO.locate` of the pipeline's own map (`templates=`, `top_k=`, `th=`, `oriented=`); on every rank, with `instance_boxes`' refusals."""
         return self.ovo.locate(self._settled_map("locate"), queries, **kw)

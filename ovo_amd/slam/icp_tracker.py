@@ -169,6 +169,15 @@ class IcpTracker:
     def get_keyframe_points(self):
         return list(self._keyframes)
 
+    def extract_mesh(self, **kw):
+        """model="tsdf": `TsdfVolume.extract_mesh(**kw)` of the fused model, (vertices f32[V, 3], faces i32[T, 3]) on the device, in the tracker's
+        frame (that of the first camera: a world_ref is applied by whoever holds it, e.g. `OVO.semantic_mesh(transform=)`)."""
+        if self.model != "tsdf":
+            raise ValueError("IcpTracker.extract_mesh: model='keyframe' keeps no fused model (build the tracker with model='tsdf')")
+        if self.volume is None:
+            raise ValueError("IcpTracker.extract_mesh: no frame processed yet (the volume is made with the first frame)")
+        return self.volume.extract_mesh(**kw)
+
     def shutdown(self) -> None:
         self._aligner = self._ref = None                   # with the reference go the keyframe's pyramid, or the volume and its image
         self._loops.release()

@@ -1,5 +1,6 @@
 """A fused geometric model on the GPU: `TsdfVolume`, a dense truncated-signed-distance volume integrated from depth frames (`ovo_tsdf_integrate`)
-and ray-cast back into a depth image from any pose (`ovo_tsdf_raycast`): csrc/tsdf.hip, DESIGN.md section 17.  `frustum_box`, `rigid_inverse_f32`
+ray-cast back into a depth image from any pose (`ovo_tsdf_raycast`) and turned into a triangle mesh (`ovo_tsdf_mesh_plan` / `ovo_tsdf_mesh_emit`):
+csrc/tsdf.hip, csrc/mesh.hip, DESIGN.md sections 17 and 18.  `frustum_box`, `rigid_inverse_f32`
 and `volume_desc` / `camera_desc` are pure numpy / ctypes and need no GPU."""
 from __future__ import annotations
 
@@ -120,6 +121,28 @@ class TsdfVolume:
         cam = camera_desc(K, h, w, c2w, near, far)
         L.check(L.load().ovo_tsdf_raycast(L.ptr(self.vol), C.byref(self.desc), C.byref(cam), dz, L.ptr(out), L.stream()))
         return out
+
+    def extract_mesh(self, box: Optional[Box] = None, min_weight: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The surface inside the index box (None: the whole volume) as a welded triangle mesh on the device: (vertices f32[V, 3] in the volume's
+        frame, faces i32[T, 3]); marching tetrahedra over the cells whose eight corners have W >= min_weight (include/ovo_hip.h states the
+        contract).  Normals point into free space.  One host wait, for (V, T); V = 0 returns empty tensors and queues no second call."""
+        box = ((0, 0, 0), self.dims) if box is None else box
+        lo, hi = (C.c_int32 * 3)(*(int(x) for x in box[0])), (C.c_int32 * 3)(*(int(x) for x in box[1]))
+        lib, dev = L.load(), self.vol.device
+        nbytes = int(lib.ovo_tsdf_mesh_workspace_bytes(C.byref(self.desc), lo, hi))
+        if nbytes == 0:
+            raise L.OvoHipError(f"TsdfVolume.extract_mesh: the box {box} must lie inside the volume {self.dims} and span at least 2 voxels on every axis")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        L.check(lib.ovo_tsdf_mesh_plan(L.ptr(self.vol), C.byref(self.desc), lo, hi, float(min_weight), L.ptr(ws), nbytes, L.ptr(counts), L.stream()))
+        V, T = (int(x) for x in counts.tolist())
+        if max(V, T) > 2**31 - 1:
+            raise L.OvoHipError(f"TsdfVolume.extract_mesh: {V} vertices and {T} triangles do not fit 32-bit indices -- extract box by box")
+        vertices, faces = torch.empty((V, 3), dtype=torch.float32, device=dev), torch.empty((T, 3), dtype=torch.int32, device=dev)
+        if V > 0:
+            L.check(lib.ovo_tsdf_mesh_emit(L.ptr(self.vol), C.byref(self.desc), lo, hi, float(min_weight), L.ptr(ws), nbytes, L.ptr(vertices), L.ptr(faces),
+                                           V, T, L.stream()))
+        return vertices, faces
 
 
 def march_steps(near: float, far: float, dz: float) -> int:
