@@ -4,10 +4,12 @@ differs, through the same attributes and methods:
 
     frame                    the prepared `Frame` the next alignment runs against
     spare                    the pyramid buffer the next frame is written into (None: a new one); a LOST frame's own, set by the tracker
-    start(depth, aligner)    the first frame, at the identity pose
+    start(depth, aligner, t) the first frame (time stamp t), at the identity pose
     aim(aligner)             the device start pose before an alignment is queued
     compose(c2w, kf_c2w, T)  an alignment's result T -> (the frame's pose, the pose relative to the keyframe that `keyframe_decision` takes)
-    tracked(cur, depth, c2w, is_kf, aligner)   after an OK frame at pose c2w; returns the outgoing keyframe's `Frame` when there is one
+    tracked(cur, depth, c2w, is_kf, aligner, t=None, kf=0, relative=None)   after an OK frame at pose c2w (time stamp t, hanging on keyframe kf at
+                             `relative`); returns the outgoing keyframe's `Frame` when there is one
+    corrected(X, c2w)        after a loop closure moved the keyframes to X (f64) and this frame to c2w
 
 `prepare(depth, out)` is the tracker's `prepare_frame` with its own intrinsics and thresholds.  The two forms of `compose` ARE the contract
 (tests/icp_restatement.py, tests/tsdf_restatement.py): each is kept one operation at a time, and they are not to be unified."""
@@ -30,7 +32,7 @@ class KeyframeReference:
         self.prepare = prepare
         self.frame = self.spare = None
 
-    def start(self, depth, aligner) -> None:
+    def start(self, depth, aligner, t=None) -> None:
         self.frame = self.prepare(depth, None)
         aligner.set_pose(EYE)
 
@@ -40,7 +42,7 @@ class KeyframeReference:
     def compose(self, c2w, kf_c2w, T):
         return (kf_c2w @ T).astype(np.float32), T          # an f32 product; the keyframe is decided on T itself
 
-    def tracked(self, cur, depth, c2w, is_kf, aligner):
+    def tracked(self, cur, depth, c2w, is_kf, aligner, t=None, kf=0, relative=None):
         if not is_kf:
             self.spare = cur.pyramid
             return None
@@ -49,13 +51,21 @@ class KeyframeReference:
         self.spare = old.pyramid                           # (stream order: the next prepare is queued behind this frame's alignment)
         return old
 
+    def corrected(self, X, c2w) -> None:
+        pass                                               # the keyframe's own image is the model: nothing to rebuild
+
 
 class TsdfReference:
     """Every frame, from the identity, against the volume ray-cast at the last good pose: an OK frame is fused at its pose and the model image
     (`model_depth`) is cast again there; a LOST frame fuses nothing and the same image serves the next frame.  tsdf_origin None: the volume is
-    centred on the first camera, in the first camera's frame; tsdf_trunc None: 4 voxels; tsdf_far None: max_depth.  1 GB at 512^3."""
+    centred on the first camera, in the first camera's frame; tsdf_trunc None: 4 voxels; tsdf_far None: max_depth.  1 GB at 512^3.
 
-    def __init__(self, prepare, K, max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far) -> None:
+    history > 0: the last `history` fused depth images are kept (`tsdf_utils.TsdfHistory`), each with the keyframe it hangs
+    on and its pose relative to it, and `corrected` fuses the volume again from them after a loop closure.  The keyframes' OWN depth pyramids are
+    then kept as `KeyframeReference` keeps them -- `tracked` returns the outgoing one at a keyframe -- because loop verification aligns keyframe
+    images, not model images."""
+
+    def __init__(self, prepare, K, max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far, history=0) -> None:
         self.prepare, self.K = prepare, K
         self.dims, self.voxel = tuple(int(d) for d in tsdf_dims), float(tsdf_voxel)
         self.origin = tuple(-0.5 * self.voxel * (n - 1) for n in self.dims) if tsdf_origin is None else tuple(float(o) for o in tsdf_origin)
@@ -63,10 +73,15 @@ class TsdfReference:
         self.max_weight, self.near = float(tsdf_max_weight), float(tsdf_near)
         self.far = float(max_depth) if tsdf_far is None else float(tsdf_far)
         self.volume = self.model_depth = self.frame = self.spare = self._eye = None
+        self.history_capacity, self.history, self._kf = int(history), None, None
 
-    def start(self, depth, aligner) -> None:
+    def start(self, depth, aligner, t=None) -> None:
         self.volume = tsdf_utils.TsdfVolume(self.dims, self.voxel, self.origin, self.trunc, self.max_weight, device=depth.device)
         self._eye = torch.eye(4, dtype=torch.float32, device=depth.device)[:3].reshape(12).contiguous()
+        if self.history_capacity > 0:                      # the first keyframe's own pyramid, and history entry 0
+            self._kf = self.prepare(depth, None)
+            self.history = tsdf_utils.TsdfHistory(self.history_capacity, int(depth.shape[0]), int(depth.shape[1]), device=depth.device)
+            self.history.add(depth, t, 0, np.eye(4))
         self._fuse(depth, EYE)
 
     def aim(self, aligner) -> None:
@@ -76,14 +91,30 @@ class TsdfReference:
         c2w = (c2w.astype(np.float64) @ T.astype(np.float64)).astype(np.float32)      # an f64 product, rounded once
         return c2w, U.rigid_inverse(kf_c2w) @ c2w.astype(np.float64)
 
-    def tracked(self, cur, depth, c2w, is_kf, aligner):
-        self.spare = cur.pyramid                           # (stream order: the next prepare is queued behind this frame's alignment)
+    def tracked(self, cur, depth, c2w, is_kf, aligner, t=None, kf=0, relative=None):
+        old = None
+        if self.history is None or not is_kf:
+            self.spare = cur.pyramid                       # (stream order: the next prepare is queued behind this frame's alignment)
+        else:                                              # the keyframe's own pyramid is kept; the outgoing one is free unless a LoopCloser keeps it
+            old, self._kf = self._kf, cur
+            self.spare = old.pyramid
+        if self.history is not None:
+            self.history.add(depth, t, kf, np.eye(4) if is_kf else relative)
         self._fuse(depth, c2w)
-        return None
+        return old
+
+    def corrected(self, X, c2w) -> None:
+        """The keyframes moved to X: the volume is fused again from the history at X[kf] @ rel, and the model image is cast at the corrected pose.
+        All of it is queued; nothing waits."""
+        self.volume.refuse(self.history, self.K, self.history.poses(X), self.near, self.far)
+        self._cast(c2w)
 
     def _fuse(self, depth, c2w) -> None:
         """Fuses a tracked frame at its pose and ray-casts the model there for the next frame: queued, not waited for."""
-        h, w = int(depth.shape[0]), int(depth.shape[1])
+        self._hw = (int(depth.shape[0]), int(depth.shape[1]))
         self.volume.integrate(depth, self.K, c2w, self.near, self.far)
-        self.model_depth = self.volume.raycast(self.K, h, w, c2w, self.near, self.far, out=self.model_depth)
+        self._cast(c2w)
+
+    def _cast(self, c2w) -> None:
+        self.model_depth = self.volume.raycast(self.K, self._hw[0], self._hw[1], c2w, self.near, self.far, out=self.model_depth)
         self.frame = self.prepare(self.model_depth, None if self.frame is None else self.frame.pyramid)

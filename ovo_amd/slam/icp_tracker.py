@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from ..utils import icp_utils as U
+from ..utils.tsdf_utils import MAX_HISTORY
 from .icp_reference import KeyframeReference, TsdfReference
 from .loop_closer import LoopCloser
 
@@ -40,7 +41,7 @@ class IcpTracker:
                  loop_radius: float = 0.5, loop_angle_deg: float = 30.0, loop_max_candidates: int = 8, loop_iters=None, loop_dist_th: float = 0.2,
                  loop_min_overlap: float = 0.3, loop_max_rms: float = 0.02, loop_max_correction=(0.3, 10.0), loop_min_shift=(0.01, 0.2),
                  loop_max_keyframes: int = 256, model: str = "keyframe", tsdf_dims=(512, 512, 512), tsdf_voxel: float = 0.02, tsdf_origin=None,
-                 tsdf_trunc=None, tsdf_max_weight: float = 64, tsdf_near: float = 0.05, tsdf_far=None) -> None:
+                 tsdf_trunc=None, tsdf_max_weight: float = 64, tsdf_near: float = 0.05, tsdf_far=None, tsdf_history: int = 0) -> None:
         """No GPU work happens here: buffers are made with the first frame.  The loop_* parameters are read and checked by `LoopCloser`, the
         tsdf_* parameters by `TsdfReference`, whichever mode is chosen.
 
@@ -60,7 +61,15 @@ class IcpTracker:
         same model image serves the next frame.  Keyframes are decided on inv(kf_c2w) @ c2w and the alignment's pairs against the model.  A ray-cast
         sample needs all eight corners observed, so a model built from one frame with many depth holes is sparse (with 5 % holes about a fifth of
         the pixels pair on the second frame, three fifths from the third): choose kf_min_overlap with that in mind.  1 GB at 512^3.
-        model="tsdf" with close_loops=True raises ValueError: a corrected trajectory would need the volume fused again, which is not built."""
+        model="tsdf" with close_loops=True and tsdf_history=0 raises ValueError: a corrected trajectory would need the volume fused again, and
+        without the frames it cannot be.
+
+        tsdf_history > 0 (model="tsdf" only, at most 4096): the last tsdf_history fused depth images stay
+        on the device (`history`, a `TsdfHistory`: 1.12 MB a frame at 456 x 616), each with the keyframe it hangs on and its pose relative to it, and
+        close_loops=True is allowed: the keyframes' own depth pyramids are verified against each other as in keyframe mode, the odometry edge is the
+        keyframe-to-keyframe transform, and after an applied closure the volume is fused again from the history at the corrected poses
+        (`TsdfVolume.refuse`: one memset, then one `ovo_tsdf_integrate` call per kept frame) and ray-cast at the corrected pose, all queued behind that frame's one extra
+        wait.  A frame older than the history is no longer in the model after a re-fusion.  A LOST frame adds nothing to the history."""
         self.K = np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, dtype=np.float32)[:3, :3].copy()
         self.levels, self.iters = int(levels), tuple(int(i) for i in iters)
         if not 1 <= self.levels <= U.MAX_LEVELS or len(self.iters) != self.levels:
@@ -75,10 +84,16 @@ class IcpTracker:
         self.model = str(model)
         if self.model not in ("keyframe", "tsdf"):
             raise ValueError(f"IcpTracker: model must be 'keyframe' or 'tsdf' (got {model!r})")
-        if self.model == "tsdf" and self.close_loops:
+        self.tsdf_history = int(tsdf_history)
+        if not 0 <= self.tsdf_history <= MAX_HISTORY:
+            raise ValueError(f"IcpTracker: tsdf_history must be 0 .. {MAX_HISTORY} frames (got {tsdf_history})")
+        if self.tsdf_history > 0 and self.model != "tsdf":
+            raise ValueError("IcpTracker: tsdf_history keeps the frames of a fused volume and needs model='tsdf'")
+        if self.model == "tsdf" and self.close_loops and self.tsdf_history == 0:
             raise ValueError("IcpTracker: model='tsdf' with close_loops=True is not built: a corrected trajectory would need the volume fused again")
         # (read in either mode, as the loop parameters are: tsdf_trunc and tsdf_far are the tracker's attributes whatever the model)
-        tsdf = TsdfReference(self._prepare, self.K, self.max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far)
+        tsdf = TsdfReference(self._prepare, self.K, self.max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far,
+                             history=self.tsdf_history)
         self.tsdf_trunc, self.tsdf_far = tsdf.trunc, tsdf.far
         self._ref = tsdf if self.model == "tsdf" else KeyframeReference(self._prepare)
         self.device = device
@@ -94,8 +109,10 @@ class IcpTracker:
 
     volume = property(lambda self: getattr(self._ref, "volume", None))             # model="tsdf": the TsdfVolume, made with the first frame
     model_depth = property(lambda self: getattr(self._ref, "model_depth", None))   # model="tsdf": the last ray-cast image, what the next frame is aligned to
+    history = property(lambda self: getattr(self._ref, "history", None))           # tsdf_history > 0: the TsdfHistory, made with the first frame
     loop_edges = property(lambda self: self._loops.loop_edges)                     # close_loops: see LoopCloser
     last_loop = property(lambda self: self._loops.last_loop)
+    loop_poses = property(lambda self: self._loops.poses)                          # close_loops: the graph's keyframe poses in f64, what `history.poses` takes
 
     def _row_of(self, t, c2w: np.ndarray) -> np.ndarray:
         return np.concatenate([np.asarray([t], dtype=np.float32), np.asarray(c2w, dtype=np.float32)[:3].reshape(12)])
@@ -116,7 +133,7 @@ class IcpTracker:
         depth, ref = self._depth(depth), self._ref
         if self._aligner is None:                          # the first frame: the identity pose, a keyframe
             self._aligner = U.Aligner(depth.device)
-            ref.start(depth, self._aligner)
+            ref.start(depth, self._aligner, t)
             self._state, self._is_kf, self.last = self.OK, True, None
             self._row = self._row_of(t, self._c2w)
             self._keyframes.append(self._row)
@@ -138,14 +155,16 @@ class IcpTracker:
         if U.keyframe_decision(relative, res["pairs"], pixels, self.kf_translation, self.kf_rotation_deg, self.kf_min_overlap):
             self._kf_c2w, self._is_kf = self._c2w, True
             self._keyframes.append(self._row)
-        old = ref.tracked(cur, depth, self._c2w, self._is_kf, self._aligner)
+        n = len(self._keyframes) - 1                       # the keyframe this frame hangs on (itself, when it is one)
+        old = ref.tracked(cur, depth, self._c2w, self._is_kf, self._aligner, t, n, relative)
         if self._is_kf and self.close_loops:               # `old`'s pyramid is kept: the next frame takes the one that became free, or a new one
-            n = len(self._keyframes) - 1
-            X, ref.spare = self._loops.keyframe(n, old, cur, res, pixels, min_pairs)
+            # model="tsdf": `old` and `cur` are the keyframes' own images, and the edge is keyframe to keyframe, not the alignment to the model
+            X, ref.spare = self._loops.keyframe(n, old, cur, res, pixels, min_pairs, edge_T=relative if self.model == "tsdf" else None)
             if X is not None:                              # a closure moved the keyframes: their rows, rounded to f32, and this frame's pose
                 self._keyframes = [self._row_of(row[0], x) for row, x in zip(self._keyframes, X)]
                 self._kf_c2w = self._c2w = X[n].astype(np.float32)
                 self._row = self._keyframes[n]
+                ref.corrected(X, self._c2w)                # model="tsdf": the volume fused again from its history, the model image cast again
 
     def _need_frame(self) -> None:
         if self._row is None:

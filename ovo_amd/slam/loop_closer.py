@@ -40,12 +40,16 @@ class LoopCloser:
         self.loop_edges: List[Any] = []                    # (reference keyframe index, current keyframe index) of every accepted edge
         self.last_loop: Any = None                         # the last verification: {"n", "candidates", "results", "accepted", "applied", "graph"}
 
-    def keyframe(self, n: int, old: U.Frame, cur: U.Frame, res, pixels: int, min_pairs: int):
+    def keyframe(self, n: int, old: U.Frame, cur: U.Frame, res, pixels: int, min_pairs: int, edge_T=None):
         """The new keyframe n, `cur`, aligned to the outgoing keyframe `old` with result `res`: extends the graph, keeps `old`'s pyramid and
         verifies the candidates in one batch.  Returns (the corrected poses of keyframes 0 .. n in f64 when the optimised graph moved one, else
-        None; the pyramid buffer that became free, else None)."""
-        self._X.append(self._X[n - 1] @ res["T"].astype(np.float64))
-        self._edges.append((n - 1, n, res["T"].astype(np.float64), U.information(res["sums"])))
+        None; the pyramid buffer that became free, else None).
+        edge_T (model="tsdf"): the transform of the odometry edge n-1 -> n and of X[n] when it is not res["T"] -- there `res` aligned the frame to
+        the MODEL, and the edge is keyframe n's pose in keyframe n-1's frame.  The edge's information stays `U.information(res["sums"])`, that of
+        the keyframe frame's alignment to the model: a judgement, not a measurement of the edge's own uncertainty."""
+        T = (res["T"] if edge_T is None else np.asarray(edge_T)).astype(np.float64)
+        self._X.append(self._X[n - 1] @ T)
+        self._edges.append((n - 1, n, T, U.information(res["sums"])))
         self._db[n - 1] = old
         free = None
         if len(self._db) > self.max_keyframes:            # the oldest leaves the candidate set (it stays a node); its buffer takes the next frame
@@ -76,6 +80,11 @@ class LoopCloser:
         self.big_change += 1
         self.last_loop["applied"] = True
         return X, free
+
+    @property
+    def poses(self) -> List[np.ndarray]:
+        """The graph's keyframe poses, f64, by keyframe index (the keyframe rows are these rounded to f32)."""
+        return list(self._X)
 
     def release(self) -> None:
         self._batch, self._db = None, {}
