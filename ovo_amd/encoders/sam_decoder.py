@@ -16,7 +16,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -120,86 +120,156 @@ def point_grid(n_per_side: int) -> torch.Tensor:
     return torch.stack([xx, yy], dim=-1).reshape(-1, 2)
 
 
+class _Tokens(NamedTuple):
+    """The token side of one forward, [P * T, C] each: the f32 residual stream, its bf16 copy, the bf16 copy with the prompts' positional code (the
+    tokens as given) added, and where the self-attention leaves its output.  Every step overwrites them in place."""
+    q: torch.Tensor
+    q16: torch.Tensor
+    qpe16: torch.Tensor
+    attn_out: torch.Tensor
+
+
+class _KeyUpdate(NamedTuple):
+    """Operands of one image -> token key update, keys' = LayerNorm(residual[row % res_rows] + out-projection); its bf16 outputs are the stream's
+    `k16` / `kpe16`."""
+    res: Optional[torch.Tensor]         # the residual operand in f32 ...
+    res16: Optional[torch.Tensor]       # ... or in bf16
+    res_rows: int                       # S: the shared keys, broadcast to every prompt; P * S: per-prompt rows
+    y32: Optional[torch.Tensor]         # f32 output; None when nothing reads it later
+    broadcast: bool                     # `res` is the shared [S, C] keys, not the [P * S, C] stream the output continues
+
+
+class _ImageKeys:
+    """The image-side key stream through the two-way layers.  It starts as one [S, C] matrix shared by every prompt (`keys` f32, `k16` bf16, `kpe16`
+    bf16 with the positional code added) and becomes [P * S, C] rows per prompt at the first image -> token update.  From there on it is either bf16
+    only (`bf16_only`: an update reads the previous `k16` as its residual and writes a fresh one) or carries the f32 `keys` beside `k16`, updated in
+    place.  `k16` / `kpe16` are what the next product reads; `kpe16` is None once the prompts have diverged: (keys + pe) is never formed per prompt,
+    see `_upload_fused_image_projections`."""
+
+    def __init__(self, keys0: torch.Tensor, k16: torch.Tensor, kpe16: torch.Tensor, prompts: int, bf16_only: bool):
+        self.shared = True
+        self.keys: Optional[torch.Tensor] = keys0
+        self.k16, self.kpe16 = k16, kpe16
+        self.bf16_only = bf16_only
+        self.P, (self.S, self.c) = prompts, keys0.shape
+
+    def begin_update(self, last: bool) -> _KeyUpdate:
+        """What the next key update takes as residual and writes in f32; re-binds `k16` / `kpe16` to what it writes in bf16.
+        last: no layer follows, so the f32 residual stream is not read after this update."""
+        S, c, rows, dev = self.S, self.c, self.P * self.S, self.k16.device
+        if self.shared:                                           # the prompts diverge here: materialise per-prompt keys
+            res, res16, res_rows = self.keys, None, S
+            self.keys = None if last or self.bf16_only else torch.empty((rows, c), dtype=torch.float32, device=dev)
+            self.k16 = torch.empty((rows, c), dtype=torch.bfloat16, device=dev)
+            self.kpe16 = None
+        elif self.bf16_only:                                      # the previous bf16 keys are the residual, the new ones go to a buffer of their own
+            res, res16, res_rows = None, self.k16, rows
+            self.k16 = torch.empty((rows, c), dtype=torch.bfloat16, device=dev)
+        else:                                                     # the f32 stream, updated in place
+            res, res16, res_rows = self.keys, None, rows
+        update = _KeyUpdate(res, res16, res_rows, None if last else self.keys, self.shared)
+        self.shared = False
+        return update
+
+
 class HipSamDecoder:
     def __init__(self, spec: SamDecoderSpec, state: Optional[Dict[str, torch.Tensor]] = None, device="cuda", seed: int = 0):
         self.spec, self.device = spec, torch.device(device)
-        sd = state if state is not None else random_state(spec, seed)
-        self.sd = sd
-        c = spec.hidden
+        self.sd = state if state is not None else random_state(spec, seed)
         self.w: Dict[str, torch.Tensor] = {}
         self.q_prescaled = L.q_prescale_enabled()
+        self.res16 = RES16                                        # OVO_SAM_RES16, taken once at construction like q_prescaled
+        self.force_unfused = False                                # tests: take the unfused key update (and with it the f32 key stream) at any width
+        c, H = spec.hidden, spec.heads
+        self.c, self.ci, self.H, self.S = c, c // 2, H, spec.embed_size * spec.embed_size     # the cross attentions work at the inner width C / 2
+        self.hd_s, self.hd_c = c // H, c // 2 // H                # head dims: token self-attention, cross attentions
+        self._upload_weights()
+        self._upload_constants()
+        self._upload_fused_image_projections()
+        self.tokens0: Optional[torch.Tensor] = None
+        self.tok16: Optional[torch.Tensor] = None
+        self.P = 0
 
-        def up(name, t, dtype):
-            self.w[name] = t.to(self.device, dtype).contiguous()
+    # ------------------------------------------------------------------ weights (set-up)
+    def _up(self, name: str, t: torch.Tensor, dtype) -> None:
+        self.w[name] = t.to(self.device, dtype).contiguous()
 
-        def lin(name):
-            up(name + ".w", sd[name + ".weight"], torch.bfloat16)
-            up(name + ".b", sd[name + ".bias"].float(), torch.float32)
+    def _lin(self, name: str) -> None:
+        self._up(name + ".w", self.sd[name + ".weight"], torch.bfloat16)
+        self._up(name + ".b", self.sd[name + ".bias"].float(), torch.float32)
 
+    def _norm(self, name: str, key: Optional[str] = None) -> None:
+        key = name if key is None else key
+        self._up(key + ".g", self.sd[name + ".weight"].float(), torch.float32)
+        self._up(key + ".b", self.sd[name + ".bias"].float(), torch.float32)
+
+    def _upload_weights(self) -> None:
+        """The state dict's matrices (bf16) with their biases and norms (f32) under the state dict's names; q | k of the token self-attention as one."""
+        sd, spec, c = self.sd, self.spec, self.c
         t = MD + "transformer."
-        blocks = [t + f"layers.{i}." for i in range(spec.depth)]
-        for b in blocks:
+        projections = ("q_proj", "k_proj", "v_proj", "out_proj")
+        for i in range(spec.depth):
+            b = t + f"layers.{i}."
             sa = b + "self_attn."
             qkw, qkb = torch.cat([sd[sa + "q_proj.weight"], sd[sa + "k_proj.weight"]]), torch.cat([sd[sa + "q_proj.bias"], sd[sa + "k_proj.bias"]])
             if self.q_prescaled:                                  # token self-attention (ovo_attention): log2 e / sqrt(hd) into the q rows, in f32
-                qkw, qkb = L.fold_q_scale(qkw, qkb, c, c // spec.heads)
-            up(sa + "qk.w", qkw, torch.bfloat16)
-            up(sa + "qk.b", qkb.float(), torch.float32)
-            lin(sa + "v_proj"); lin(sa + "out_proj")
+                qkw, qkb = L.fold_q_scale(qkw, qkb, c, self.hd_s)
+            self._up(sa + "qk.w", qkw, torch.bfloat16)
+            self._up(sa + "qk.b", qkb.float(), torch.float32)
+            self._lin(sa + "v_proj"); self._lin(sa + "out_proj")
             for a in ("cross_attn_token_to_image.", "cross_attn_image_to_token."):
-                for p in ("q_proj", "k_proj", "v_proj", "out_proj"):
-                    lin(b + a + p)
-            lin(b + "mlp.layers.0"); lin(b + "mlp.layers.1")
+                for p in projections:
+                    self._lin(b + a + p)
+            self._lin(b + "mlp.layers.0"); self._lin(b + "mlp.layers.1")
             for k in range(1, 5):
-                up(b + f"norm{k}.g", sd[b + f"norm{k}.weight"].float(), torch.float32)
-                up(b + f"norm{k}.b", sd[b + f"norm{k}.bias"].float(), torch.float32)
-        for p in ("q_proj", "k_proj", "v_proj", "out_proj"):
-            lin(t + "final_attn_token_to_image." + p)
-        up(t + "norm_final_attn.g", sd[t + "norm_final_attn.weight"].float(), torch.float32)
-        up(t + "norm_final_attn.b", sd[t + "norm_final_attn.bias"].float(), torch.float32)
+                self._norm(b + f"norm{k}")
+        for p in projections:
+            self._lin(t + "final_attn_token_to_image." + p)
+        self._norm(t + "norm_final_attn")
         for i, key in ((0, "up1"), (3, "up2")):                   # ConvTranspose2d [Cin, Cout, 2, 2] -> GEMM weight [(dy, dx, co), Cin]
             wt = sd[MD + f"output_upscaling.{i}.weight"]
-            up(key + ".w", wt.permute(2, 3, 1, 0).reshape(4 * wt.shape[1], wt.shape[0]), torch.bfloat16)
-            up(key + ".b", sd[MD + f"output_upscaling.{i}.bias"].float(), torch.float32)
-        up("up_ln.g", sd[MD + "output_upscaling.1.weight"].float(), torch.float32)
-        up("up_ln.b", sd[MD + "output_upscaling.1.bias"].float(), torch.float32)
+            self._up(key + ".w", wt.permute(2, 3, 1, 0).reshape(4 * wt.shape[1], wt.shape[0]), torch.bfloat16)
+            self._up(key + ".b", sd[MD + f"output_upscaling.{i}.bias"].float(), torch.float32)
+        self._norm(MD + "output_upscaling.1", "up_ln")
         for i in range(spec.n_mask_tokens):
             for j in range(3):
-                lin(MD + f"output_hypernetworks_mlps.{i}.layers.{j}")
+                self._lin(MD + f"output_hypernetworks_mlps.{i}.layers.{j}")
         for j in range(3):
-            lin(MD + f"iou_prediction_head.layers.{j}")
-        # constants of the generator
-        gauss = sd[PE + "pe_layer.positional_encoding_gaussian_matrix"].double()
-        s = spec.embed_size
+            self._lin(MD + f"iou_prediction_head.layers.{j}")
+
+    def _upload_constants(self) -> None:
+        """Constants of the generator: the positional code of the embedding grid and the dense "no mask" embedding."""
+        sd, c, s = self.sd, self.c, self.spec.embed_size
+        self._gauss = sd[PE + "pe_layer.positional_encoding_gaussian_matrix"].double()
         tt = (torch.arange(s, dtype=torch.float64) + 0.5) / s
         yy, xx = torch.meshgrid(tt, tt, indexing="ij")
-        up("key_pe", fourier_pe(torch.stack([xx, yy], dim=-1), gauss).reshape(s * s, c).float(), torch.float32)
+        self._up("key_pe", fourier_pe(torch.stack([xx, yy], dim=-1), self._gauss).reshape(s * s, c).float(), torch.float32)
         dense = sd[PE + "no_mask_embed.weight"].reshape(1, c).float()
         if "no_mem_embed" in sd:                                  # SAM2ImagePredictor adds it to the lowest-resolution feature
             dense = dense + sd["no_mem_embed"].reshape(1, c).float()
-        up("dense", dense, torch.float32)
-        # Image-side projections once the prompts have diverged (layers >= 1 and the final attention): K | V (| Q of the image -> token
-        # attention) read the same keys, so they are ONE product over them; the positional code enters as its own projection, a per-pixel
-        # constant added in the epilogue (ovo_gemm_periodic): k_proj(keys + pe) = keys . Wk^T + (pe . Wk^T)[pixel].
+        self._up("dense", dense, torch.float32)
+
+    def _upload_fused_image_projections(self) -> None:
+        """Image-side projections once the prompts have diverged (layers >= 1 and the final attention): K | V (| Q of the image -> token
+        attention) read the same keys, so they are ONE product over them; the positional code enters as its own projection, a per-pixel
+        constant added in the epilogue (ovo_gemm_periodic): k_proj(keys + pe) = keys . Wk^T + (pe . Wk^T)[pixel]."""
+        sd = self.sd
         pe64 = self.w["key_pe"].double().cpu()
 
         def fuse(name, parts):                                     # parts: (projection, adds the positional code?)
             ws = [sd[pn + ".weight"] for pn, _ in parts]
-            up(name + ".w", torch.cat(ws), torch.bfloat16)
-            up(name + ".b", torch.cat([sd[pn + ".bias"] for pn, _ in parts]).float(), torch.float32)
+            self._up(name + ".w", torch.cat(ws), torch.bfloat16)
+            self._up(name + ".b", torch.cat([sd[pn + ".bias"] for pn, _ in parts]).float(), torch.float32)
             cols = [pe64 @ w.to(torch.bfloat16).double().T if with_pe else torch.zeros(pe64.shape[0], w.shape[0], dtype=torch.float64)
                     for w, (_, with_pe) in zip(ws, parts)]
-            up(name + ".add", torch.cat(cols, dim=1).float(), torch.float32)
+            self._up(name + ".add", torch.cat(cols, dim=1).float(), torch.float32)
 
-        for i in range(1, spec.depth):
-            b = blocks[i]
+        t = MD + "transformer."
+        for i in range(1, self.spec.depth):
+            b = t + f"layers.{i}."
             fuse(b + "kvq", [(b + "cross_attn_token_to_image.k_proj", True), (b + "cross_attn_token_to_image.v_proj", False),
                              (b + "cross_attn_image_to_token.q_proj", True)])
         fuse(t + "final_kv", [(t + "final_attn_token_to_image.k_proj", True), (t + "final_attn_token_to_image.v_proj", False)])
-        self._gauss = gauss
-        self.tokens0: Optional[torch.Tensor] = None
-        self.tok16: Optional[torch.Tensor] = None
-        self.P = 0
 
     # ------------------------------------------------------------------ prompts (set-up)
     def set_points(self, points_xy: torch.Tensor, labels: Optional[torch.Tensor] = None) -> None:
@@ -238,24 +308,6 @@ class HipSamDecoder:
             L.check(L.load().ovo_gemm(C.byref(g), L.stream()))
         return out
 
-    def _image_proj(self, a16: torch.Tensor, wname: str, groups) -> torch.Tensor:
-        """bf16 [rows, N] = a16 . W^T + bias + add[row % S] for the fused image-side projection `wname` (see `fuse`), computed as one
-        LDS-resident-weight stream per column group (`groups`: widths summing to N; ovo_sam_linear) or, for widths that has no
-        instantiation for, as one tiled GEMM with the periodic add."""
-        w, bias, add = self.w[wname + ".w"], self.w[wname + ".b"], self.w[wname + ".add"]
-        n, k = w.shape
-        rows, S = a16.shape[0], add.shape[0]
-        out = torch.empty((rows, n), dtype=torch.bfloat16, device=a16.device)
-        lib, lo = L.load(), 0
-        for width in groups:
-            rc = lib.ovo_sam_linear(L.ptr(a16), C.c_void_p(w.data_ptr() + 2 * lo * k), C.c_void_p(bias.data_ptr() + 4 * lo),
-                                    C.c_void_p(add.data_ptr() + 4 * lo), S, n, C.c_void_p(out.data_ptr() + 2 * lo), n, rows, width, k, L.stream())
-            if rc == L.E_UNSUPPORTED:
-                return self._gemm(a16, wname, torch.bfloat16, add=add, add_rows=S, out=out)
-            L.check(rc)
-            lo += width
-        return out
-
     @staticmethod
     def _attn(q, k, v, o, B, H, Tq, Tk, hd, qs, ks, vs, os_, prescaled=False):
         """q/k/v/o: (tensor, element offset); *s: (batch, head, token) strides in elements.  prescaled: q already carries
@@ -275,6 +327,181 @@ class HipSamDecoder:
         L.check(L.load().ovo_row_epilogue(L.ptr(x), R, Cc, L.ptr(base), base_rows, L.ptr(g), L.ptr(b), eps, L.ptr(pe), pe_rows,
                                           L.ptr(y), L.ptr(y16), L.ptr(ype16), L.stream()))
 
+    # ------------------------------------------------------------------ fused entry points (samfuse.hip), each with the chain it replaces
+    @staticmethod
+    def _unsupported(rc: int) -> bool:
+        """True when a fused entry point answered OVO_E_UNSUPPORTED -- it has no instantiation for the shape, the caller runs the unfused chain;
+        any other failure raises."""
+        if rc == L.E_UNSUPPORTED:
+            return True
+        L.check(rc)
+        return False
+
+    def _image_proj(self, a16: torch.Tensor, wname: str, groups) -> torch.Tensor:
+        """bf16 [rows, N] = a16 . W^T + bias + add[row % S] for the fused image-side projection `wname` (see `_upload_fused_image_projections`),
+        computed as one LDS-resident-weight stream per column group (`groups`: widths summing to N; ovo_sam_linear) or, for widths that entry
+        point has no instantiation for, as one tiled GEMM with the periodic add."""
+        w, bias, add = self.w[wname + ".w"], self.w[wname + ".b"], self.w[wname + ".add"]
+        n, k = w.shape
+        rows, S = a16.shape[0], add.shape[0]
+        out = torch.empty((rows, n), dtype=torch.bfloat16, device=a16.device)
+        lib, lo = L.load(), 0
+        for width in groups:
+            rc = lib.ovo_sam_linear(L.ptr(a16), C.c_void_p(w.data_ptr() + 2 * lo * k), C.c_void_p(bias.data_ptr() + 4 * lo),
+                                    C.c_void_p(add.data_ptr() + 4 * lo), S, n, C.c_void_p(out.data_ptr() + 2 * lo), n, rows, width, k, L.stream())
+            if self._unsupported(rc):
+                return self._gemm(a16, wname, torch.bfloat16, add=add, add_rows=S, out=out)
+            lo += width
+        return out
+
+    def _t2i_attention(self, tq: torch.Tensor, k, v, kv_sb: int, kv_st: int, o: torch.Tensor) -> None:
+        """o [P * T, ci] = attention of every prompt's T token queries `tq` over its S image keys.  k / v: (tensor, element offset), rows `kv_st`
+        elements apart, prompts `kv_sb` apart (0: one set of keys shared by all).  The dedicated kernel exists for head dim 16."""
+        P, S, T, H, ci, hd = self.P, self.S, self.T, self.H, self.ci, self.hd_c
+        rc = L.E_UNSUPPORTED
+        if hd == 16:
+            kptr, vptr = (C.c_void_p(t.data_ptr() + off * 2) for t, off in (k, v))
+            rc = L.load().ovo_sam_t2i_attention(L.ptr(tq), kptr, vptr, kv_sb, kv_st, L.ptr(o), P, S, T, H, hd ** -0.5, L.stream())
+        if self._unsupported(rc):
+            self._attn((tq, 0), k, v, (o, 0), P, H, T, S, hd, (T * ci, hd, ci), (kv_sb, hd, kv_st), (kv_sb, hd, kv_st), (T * ci, hd, ci))
+
+    def _update_keys(self, b: str, oi: torch.Tensor, keys: _ImageKeys, last: bool) -> None:
+        """The image -> token attention's out-projection + residual + norm4 (+ the bf16 copies the next products read): one fused launch; widths
+        it does not cover run the product and the row pass separately, over the f32 stream (the bf16-only stream exists at covered widths only)."""
+        P, S, c, w, key_pe = self.P, self.S, self.c, self.w, self.w["key_pe"]
+        a = b + "cross_attn_image_to_token."
+        u = keys.begin_update(last)
+        rc = L.E_UNSUPPORTED if self.force_unfused else \
+            L.load().ovo_sam_proj_ln(L.ptr(oi), L.ptr(w[a + "out_proj.w"]), L.ptr(w[a + "out_proj.b"]), L.ptr(u.res), L.ptr(u.res16), u.res_rows,
+                                     L.ptr(w[b + "norm4.g"]), L.ptr(w[b + "norm4.b"]), 1e-5, L.ptr(key_pe), S, L.ptr(u.y32), L.ptr(keys.k16),
+                                     L.ptr(keys.kpe16), P * S, c, self.ci, L.stream())
+        if not self._unsupported(rc):
+            return
+        if u.broadcast:
+            x = self._gemm(oi, a + "out_proj", torch.float32)
+            self._rows(x, P * S, c, base=u.res, base_rows=u.res_rows, norm=b + "norm4", pe=key_pe, pe_rows=S, y=u.y32, y16=keys.k16, ype16=keys.kpe16)
+        else:
+            self._gemm(oi, a + "out_proj", torch.float32, add=u.res, out=u.res)
+            self._rows(u.res, P * S, c, norm=b + "norm4", pe=key_pe, pe_rows=S, y=u.y32, y16=keys.k16, ype16=keys.kpe16)
+
+    def _up1_ln(self, k16: torch.Tensor, f1: torch.Tensor) -> torch.Tensor:
+        """bf16 [P * 4S, C/4]: the first transposed convolution as a skinny product fused with what follows it (+ feat_s1, LayerNorm2d, GELU)."""
+        P, s, c, w = self.P, self.spec.embed_size, self.c, self.w
+        up1 = torch.empty((P * 4 * self.S, c // 4), dtype=torch.bfloat16, device=self.device)
+        lib = L.load()
+        rc = lib.ovo_sam_up1_ln(L.ptr(k16), L.ptr(w["up1.w"]), L.ptr(w["up1.b"]), L.ptr(f1), L.ptr(w["up_ln.g"]), L.ptr(w["up_ln.b"]), 1e-6,
+                                P, s, c // 4, c, L.ptr(up1), L.stream())
+        if self._unsupported(rc):
+            g1 = self._gemm(k16, "up1", torch.bfloat16, bias=False)                       # [P*S, 4 * c/4]
+            L.check(lib.ovo_sam_upscale_ln(L.ptr(g1), L.ptr(w["up1.b"]), L.ptr(f1), L.ptr(w["up_ln.g"]), L.ptr(w["up_ln.b"]), 1e-6,
+                                           P, s, c // 4, L.ptr(up1), L.stream()))
+        return up1
+
+    def _up2_masks(self, up1: torch.Tensor, f0: torch.Tensor, hyper: torch.Tensor, first: int) -> torch.Tensor:
+        """f32 [P, n - first, 4s, 4s]: the second transposed convolution fused with what follows it (+ feat_s0, GELU, the product with the hyper-network
+        rows `first` .. n - 1 of `hyper` [P, n, C/8])."""
+        P, s, c, w, n = self.P, self.spec.embed_size, self.c, self.w, hyper.shape[1]
+        masks = torch.empty((P, n - first, 4 * s, 4 * s), dtype=torch.float32, device=self.device)
+        lib = L.load()
+        rc = lib.ovo_sam_up2_masks(L.ptr(up1), L.ptr(w["up2.w"]), L.ptr(w["up2.b"]), L.ptr(f0), L.ptr(hyper), n, first, P, 2 * s, c // 8, c // 4,
+                                   L.ptr(masks), L.stream())
+        if self._unsupported(rc):
+            g2 = self._gemm(up1, "up2", torch.bfloat16, bias=False)                       # [P*4S, 4 * c/8]
+            L.check(lib.ovo_sam_upscale_masks(L.ptr(g2), L.ptr(w["up2.b"]), L.ptr(f0), L.ptr(hyper), n, first, P, 2 * s, c // 8, L.ptr(masks),
+                                              L.stream()))
+        return masks
+
+    # ------------------------------------------------------------------ steps of the forward
+    def _layer0_keys(self, emb: torch.Tensor) -> _ImageKeys:
+        """keys = image embedding + dense "no mask" embedding, in f32, bf16 and bf16 with the positional code: shared by every prompt."""
+        S, c, dev = self.S, self.c, self.device
+        keys0 = torch.empty((S, c), dtype=torch.float32, device=dev)
+        k16 = torch.empty((S, c), dtype=torch.bfloat16, device=dev)
+        kpe16 = torch.empty((S, c), dtype=torch.bfloat16, device=dev)
+        self._rows(emb, S, c, base=self.w["dense"], base_rows=1, pe=self.w["key_pe"], pe_rows=S, y=keys0, y16=k16, ype16=kpe16)
+        # the per-prompt keys live as bf16 only where the fused out-projection + norm kernel exists (hidden 256 / 128, samfuse.hip); at any
+        # other width the unfused chain needs the f32 stream as its residual operand (`force_unfused`: tests)
+        bf16_only = self.res16 and c in (256, 128) and not self.force_unfused
+        return _ImageKeys(keys0, k16, kpe16, self.P, bf16_only)
+
+    def _token_buffers(self) -> _Tokens:
+        R, c, dev = self.P * self.T, self.c, self.device
+        q = torch.empty((R, c), dtype=torch.float32, device=dev)
+        q16 = torch.empty((R, c), dtype=torch.bfloat16, device=dev)
+        qpe16 = torch.empty((R, c), dtype=torch.bfloat16, device=dev)
+        attn_out = torch.empty((R, c), dtype=torch.bfloat16, device=dev)
+        return _Tokens(q, q16, qpe16, attn_out)
+
+    def _per_prompt_proj(self, keys: _ImageKeys, wname: str, groups) -> Optional[torch.Tensor]:
+        """The fused image-side projection `wname` of the per-prompt keys, bf16 [P * S, sum(groups)]; None while the keys are shared (layer 0): each
+        attention then projects the one [S, C] matrix itself."""
+        return None if keys.shared else self._image_proj(keys.k16, wname, groups)
+
+    def _self_attention(self, b: str, tok: _Tokens, first: bool) -> None:
+        """Self attention on the tokens + norm1 (first layer: the tokens as given are the input, no positional code, no residual)."""
+        P, T, c, H, hd = self.P, self.T, self.c, self.H, self.hd_s
+        qk = self._gemm(self.tok16 if first else tok.qpe16, b + "self_attn.qk", torch.bfloat16)          # [R, 2c]
+        v = self._gemm(self.tok16 if first else tok.q16, b + "self_attn.v_proj", torch.bfloat16)         # [R, c]
+        self._attn((qk, 0), (qk, c), (v, 0), (tok.attn_out, 0), P, H, T, T, hd, (T * 2 * c, hd, 2 * c), (T * 2 * c, hd, 2 * c),
+                   (T * c, hd, c), (T * c, hd, c), prescaled=self.q_prescaled)
+        self._gemm(tok.attn_out, b + "self_attn.out_proj", torch.float32, add=None if first else tok.q, out=tok.q)
+        self._rows(tok.q, P * T, c, norm=b + "norm1", pe=self.tokens0, pe_rows=P * T, y=tok.q, y16=tok.q16, ype16=tok.qpe16)
+
+    def _token_to_image(self, pre: str, norm: str, tok: _Tokens, keys: _ImageKeys, kv: Optional[torch.Tensor]) -> None:
+        """The tokens attend to the image + `norm`.  kv: the fused per-prompt projection bf16 [P*S, n * ci] (K | V | ...), or None while the keys are
+        shared (layer 0)."""
+        S, c, ci, R = self.S, self.c, self.ci, self.P * self.T
+        tq = self._gemm(tok.qpe16, pre + "q_proj", torch.bfloat16)                        # [R, ci]
+        if kv is None:
+            K = self._gemm(keys.kpe16, pre + "k_proj", torch.bfloat16)                    # [S, ci]
+            V = self._gemm(keys.k16, pre + "v_proj", torch.bfloat16)
+            k, v, kv_sb, kv_st = (K, 0), (V, 0), 0, ci
+        else:
+            k, v, kv_sb, kv_st = (kv, 0), (kv, ci), S * kv.shape[1], kv.shape[1]
+        o = torch.empty((R, ci), dtype=torch.bfloat16, device=self.device)
+        self._t2i_attention(tq, k, v, kv_sb, kv_st, o)
+        self._gemm(o, pre + "out_proj", torch.float32, add=tok.q, out=tok.q)
+        self._rows(tok.q, R, c, norm=norm, y=tok.q, y16=tok.q16)
+
+    def _mlp(self, b: str, tok: _Tokens) -> None:
+        R, c = self.P * self.T, self.c
+        h = self._gemm(tok.q16, b + "mlp.layers.0", torch.bfloat16, act=3)
+        self._gemm(h, b + "mlp.layers.1", torch.float32, add=tok.q, out=tok.q)
+        self._rows(tok.q, R, c, norm=b + "norm3", pe=self.tokens0, pe_rows=R, y=tok.q, y16=tok.q16, ype16=tok.qpe16)
+
+    def _image_to_token(self, a: str, tok: _Tokens, keys: _ImageKeys, kvq: Optional[torch.Tensor]) -> torch.Tensor:
+        """bf16 [P * S, ci]: the image attends to the tokens (before its out-projection: `_update_keys`).  kvq: K | V | Q of the per-prompt keys in one
+        matrix, or None while the keys are shared."""
+        P, S, T, H, ci, hd = self.P, self.S, self.T, self.H, self.ci, self.hd_c
+        kt = self._gemm(tok.qpe16, a + "k_proj", torch.bfloat16)                          # [R, ci]
+        vt = self._gemm(tok.q16, a + "v_proj", torch.bfloat16)
+        if kvq is None:
+            qi, q_off, q_sb, q_st = self._gemm(keys.kpe16, a + "q_proj", torch.bfloat16), 0, 0, ci       # [S, ci]
+        else:
+            qi, q_off, q_sb, q_st = kvq, 2 * ci, S * 3 * ci, 3 * ci
+        oi = torch.empty((P * S, ci), dtype=torch.bfloat16, device=self.device)
+        if hd == 16 and T <= 16 and 256 % H == 0:                 # S queries x 8 keys: the dedicated HBM-bound kernel
+            L.check(L.load().ovo_sam_i2t_attention(C.c_void_p(qi.data_ptr() + 2 * q_off), q_sb, q_st, L.ptr(kt), L.ptr(vt), L.ptr(oi), P, S, T, H,
+                                                   hd ** -0.5, L.stream()))
+        else:
+            self._attn((qi, q_off), (kt, 0), (vt, 0), (oi, 0), P, H, S, T, hd, (q_sb, hd, q_st), (T * ci, hd, ci), (T * ci, hd, ci), (S * ci, hd, ci))
+        return oi
+
+    def _heads(self, q16: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(predicted IoU f32 [P, nm], hyper-network rows f32 [P, nm, C/8]) straight from strided token rows: token 1 and tokens 2 .. 2 + nm."""
+        P, T, c, nm = self.P, self.T, self.c, self.spec.n_mask_tokens
+        bf, f32 = torch.bfloat16, torch.float32
+        x = self._gemm(q16, MD + "iou_prediction_head.layers.0", bf, act=3, rows=P, lda=T * c, a_off=1 * c)
+        x = self._gemm(x, MD + "iou_prediction_head.layers.1", bf, act=3)
+        iou = self._gemm(x, MD + "iou_prediction_head.layers.2", f32, act=4)
+        hyper = torch.empty((P, nm, c // 8), dtype=f32, device=self.device)
+        for m in range(nm):
+            pre = MD + f"output_hypernetworks_mlps.{m}."
+            x = self._gemm(q16, pre + "layers.0", bf, act=3, rows=P, lda=T * c, a_off=(2 + m) * c)
+            x = self._gemm(x, pre + "layers.1", bf, act=3)
+            self._gemm(x, pre + "layers.2", f32, out=hyper, ldc=nm * (c // 8), c_off=m * (c // 8))
+        return iou, hyper
+
     # ------------------------------------------------------------------ forward
     def forward(self, image_embed: torch.Tensor, feat_s1: torch.Tensor, feat_s0: torch.Tensor, multimask: bool = True
                 ) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -282,155 +509,30 @@ class HipSamDecoder:
         -> (mask logits f32 [P, 3 | 4, 4s, 4s], predicted IoU f32 [P, 3 | 4]) for the prompts of set_points()."""
         if self.tokens0 is None:
             raise L.OvoHipError("set_points() / set_point_grid() first")
-        spec = self.spec
-        c, ci, H, s = spec.hidden, spec.hidden // 2, spec.heads, spec.embed_size
-        S, P, T = s * s, self.P, self.T
-        dev = self.device
-        # the per-prompt keys live as bf16 only where the fused out-projection + norm kernel exists (hidden 256 / 128, samfuse.hip); at any
-        # other width the unfused chain needs the f32 stream as its residual operand (`force_unfused`: tests)
-        res16_on = RES16 and c in (256, 128) and not getattr(self, "force_unfused", False)
+        spec, S, c, ci = self.spec, self.S, self.c, self.ci
         emb = L.dev(image_embed.reshape(S, c), torch.float32, "image_embed")
         f1 = L.dev(feat_s1.reshape(4 * S, c // 4), torch.float32, "feat_s1")
         f0 = L.dev(feat_s0.reshape(16 * S, c // 8), torch.float32, "feat_s0")
-        bf, f32 = torch.bfloat16, torch.float32
-        lib = L.load()
-        key_pe, tok0 = self.w["key_pe"], self.tokens0
-        R = P * T
-
-        # keys of layer 0: shared by every prompt
-        keys0 = torch.empty((S, c), dtype=f32, device=dev)
-        k16 = torch.empty((S, c), dtype=bf, device=dev)
-        kpe16 = torch.empty((S, c), dtype=bf, device=dev)
-        self._rows(emb, S, c, base=self.w["dense"], base_rows=1, pe=key_pe, pe_rows=S, y=keys0, y16=k16, ype16=kpe16)
-        keys = None                                               # f32 [P*S, c] once the prompts diverge
-        shared = True
-
-        q = torch.empty((R, c), dtype=f32, device=dev)
-        q16 = torch.empty((R, c), dtype=bf, device=dev)
-        qpe16 = torch.empty((R, c), dtype=bf, device=dev)
-        o_tok = torch.empty((R, c), dtype=bf, device=dev)
-        hd_s, hd_c = c // H, ci // H
         t = MD + "transformer."
 
-        def t2i_attention(tq, K, V, kv_sb, kv_st, o):
-            rc = lib.ovo_sam_t2i_attention(L.ptr(tq), K, V, kv_sb, kv_st, L.ptr(o), P, S, T, H, hd_c ** -0.5, L.stream()) if hd_c == 16 \
-                else L.E_UNSUPPORTED
-            return rc
-
-        def token_to_image(pre, qin16, kv=None):
-            """kv: the fused per-prompt projection bf16 [P*S, n * ci] (K | V | ...), or None while the keys are shared (layer 0)."""
-            nonlocal q
-            tq = self._gemm(qin16, pre + "q_proj", bf)                                    # [R, ci]
-            if kv is None:
-                K = self._gemm(kpe16, pre + "k_proj", bf)                                 # [S, ci]
-                V = self._gemm(k16, pre + "v_proj", bf)
-                kt_, vt_, kb, ks = (K, 0), (V, 0), 0, ci
-            else:
-                kt_, vt_, kb, ks = (kv, 0), (kv, ci), S * kv.shape[1], kv.shape[1]
-            o = torch.empty((R, ci), dtype=bf, device=dev)
-            kptr, vptr = (C.c_void_p(t_.data_ptr() + off * 2) for t_, off in (kt_, vt_))
-            rc = t2i_attention(tq, kptr, vptr, kb, ks, o)
-            if rc == L.E_UNSUPPORTED:
-                self._attn((tq, 0), kt_, vt_, (o, 0), P, H, T, S, hd_c, (T * ci, hd_c, ci), (kb, hd_c, ks), (kb, hd_c, ks), (T * ci, hd_c, ci))
-            else:
-                L.check(rc)
-            self._gemm(o, pre + "out_proj", f32, add=q, out=q)
-
+        keys = self._layer0_keys(emb)
+        tok = self._token_buffers()
         for i in range(spec.depth):
             b = t + f"layers.{i}."
-            # per-prompt keys: K | V of the token -> image attention and Q of the image -> token attention in one product over them
-            kvq = None if shared else self._image_proj(k16, b + "kvq", (2 * ci, ci))                            # [P*S, 3 ci]
-            # ---- self attention on the tokens (first layer: no positional code, no residual)
-            qk = self._gemm(self.tok16 if i == 0 else qpe16, b + "self_attn.qk", bf)      # [R, 2c]
-            v = self._gemm(self.tok16 if i == 0 else q16, b + "self_attn.v_proj", bf)     # [R, c]
-            self._attn((qk, 0), (qk, c), (v, 0), (o_tok, 0), P, H, T, T, hd_s, (T * 2 * c, hd_s, 2 * c), (T * 2 * c, hd_s, 2 * c),
-                       (T * c, hd_s, c), (T * c, hd_s, c), prescaled=self.q_prescaled)
-            self._gemm(o_tok, b + "self_attn.out_proj", f32, add=None if i == 0 else q, out=q)
-            self._rows(q, R, c, norm=b + "norm1", pe=tok0, pe_rows=R, y=q, y16=q16, ype16=qpe16)
-            # ---- tokens attend to the image
-            token_to_image(b + "cross_attn_token_to_image.", qpe16, kvq)
-            self._rows(q, R, c, norm=b + "norm2", y=q, y16=q16)
-            # ---- MLP
-            h = self._gemm(q16, b + "mlp.layers.0", bf, act=3)
-            self._gemm(h, b + "mlp.layers.1", f32, add=q, out=q)
-            self._rows(q, R, c, norm=b + "norm3", pe=tok0, pe_rows=R, y=q, y16=q16, ype16=qpe16)
-            # ---- image attends to the tokens
-            a = b + "cross_attn_image_to_token."
-            kt = self._gemm(qpe16, a + "k_proj", bf)                                      # [R, ci]
-            vt = self._gemm(q16, a + "v_proj", bf)
-            if shared:
-                qi, q_off, q_sb, q_st = self._gemm(kpe16, a + "q_proj", bf), 0, 0, ci     # [S, ci]
-            else:
-                qi, q_off, q_sb, q_st = kvq, 2 * ci, S * 3 * ci, 3 * ci
-            oi = torch.empty((P * S, ci), dtype=bf, device=dev)
-            if hd_c == 16 and T <= 16 and 256 % H == 0:           # S queries x 8 keys: the dedicated HBM-bound kernel
-                L.check(lib.ovo_sam_i2t_attention(C.c_void_p(qi.data_ptr() + 2 * q_off), q_sb, q_st, L.ptr(kt), L.ptr(vt), L.ptr(oi), P, S, T, H,
-                                                  hd_c ** -0.5, L.stream()))
-            else:
-                self._attn((qi, q_off), (kt, 0), (vt, 0), (oi, 0), P, H, S, T, hd_c, (q_sb, hd_c, q_st), (T * ci, hd_c, ci),
-                           (T * ci, hd_c, ci), (S * ci, hd_c, ci))
-            # out-projection + residual + norm4 (+ the bf16 copies the next products read): one fused launch (samfuse.hip); widths it
-            # does not cover run the product and the row pass separately
-            last = i == spec.depth - 1
-            if shared:                                            # the prompts diverge here: materialise per-prompt keys
-                keys = None if last or res16_on else torch.empty((P * S, c), dtype=f32, device=dev)
-                k16 = torch.empty((P * S, c), dtype=bf, device=dev)
-                kpe16 = None                                      # (keys + pe) is never formed per prompt: see `fuse` in __init__
-                res, res16, res_rows = keys0, None, S
-            elif res16_on:
-                res, res16, res_rows, k16 = None, k16, P * S, torch.empty((P * S, c), dtype=bf, device=dev)
-            else:
-                res, res16, res_rows = keys, None, P * S
-            y32 = None if last else keys                          # the f32 residual stream is not read after the last layer
-            rc = L.E_UNSUPPORTED if getattr(self, "force_unfused", False) else \
-                lib.ovo_sam_proj_ln(L.ptr(oi), L.ptr(self.w[a + "out_proj.w"]), L.ptr(self.w[a + "out_proj.b"]), L.ptr(res), L.ptr(res16), res_rows,
-                                    L.ptr(self.w[b + "norm4.g"]), L.ptr(self.w[b + "norm4.b"]), 1e-5, L.ptr(key_pe), S, L.ptr(y32), L.ptr(k16),
-                                    L.ptr(kpe16), P * S, c, ci, L.stream())
-            if rc == L.E_UNSUPPORTED:                             # product and row pass separately (f32 stream: res16_on is off at these widths)
-                if shared:
-                    x = self._gemm(oi, a + "out_proj", f32)
-                    self._rows(x, P * S, c, base=keys0, base_rows=S, norm=b + "norm4", pe=key_pe, pe_rows=S, y=y32, y16=k16, ype16=kpe16)
-                else:
-                    self._gemm(oi, a + "out_proj", f32, add=keys, out=keys)
-                    self._rows(keys, P * S, c, norm=b + "norm4", pe=key_pe, pe_rows=S, y=None if last else keys, y16=k16, ype16=kpe16)
-            else:
-                L.check(rc)
-            shared = False
-        kv = None if shared else self._image_proj(k16, t + "final_kv", (2 * ci,))                               # [P*S, 2 ci]
-        token_to_image(t + "final_attn_token_to_image.", qpe16, kv)
-        self._rows(q, R, c, norm=t + "norm_final_attn", y=q, y16=q16)
+            # K | V of the token -> image attention and Q of the image -> token attention in one product over the per-prompt keys
+            kvq = self._per_prompt_proj(keys, b + "kvq", (2 * ci, ci))                    # [P*S, 3 ci]
+            self._self_attention(b, tok, first=i == 0)
+            self._token_to_image(b + "cross_attn_token_to_image.", b + "norm2", tok, keys, kvq)
+            self._mlp(b, tok)
+            oi = self._image_to_token(b + "cross_attn_image_to_token.", tok, keys, kvq)
+            self._update_keys(b, oi, keys, last=i == spec.depth - 1)
+        kv = self._per_prompt_proj(keys, t + "final_kv", (2 * ci,))                       # [P*S, 2 ci]
+        self._token_to_image(t + "final_attn_token_to_image.", t + "norm_final_attn", tok, keys, kv)
 
-        # ---- heads: IoU prediction and hyper-network rows straight from strided token rows
-        nm = spec.n_mask_tokens
-        x = self._gemm(q16, MD + "iou_prediction_head.layers.0", bf, act=3, rows=P, lda=T * c, a_off=1 * c)
-        x = self._gemm(x, MD + "iou_prediction_head.layers.1", bf, act=3)
-        iou = self._gemm(x, MD + "iou_prediction_head.layers.2", f32, act=4)              # [P, nm]
-        hyper = torch.empty((P, nm, c // 8), dtype=f32, device=dev)
-        for m in range(nm):
-            pre = MD + f"output_hypernetworks_mlps.{m}."
-            x = self._gemm(q16, pre + "layers.0", bf, act=3, rows=P, lda=T * c, a_off=(2 + m) * c)
-            x = self._gemm(x, pre + "layers.1", bf, act=3)
-            self._gemm(x, pre + "layers.2", f32, out=hyper, ldc=nm * (c // 8), c_off=m * (c // 8))
-        # ---- upscaling: two transposed convolutions as skinny products fused with what follows them (LayerNorm2d + GELU; GELU + the
-        # hyper-network product), samfuse.hip
-        up1 = torch.empty((P * 4 * S, c // 4), dtype=bf, device=dev)
-        rc = lib.ovo_sam_up1_ln(L.ptr(k16), L.ptr(self.w["up1.w"]), L.ptr(self.w["up1.b"]), L.ptr(f1), L.ptr(self.w["up_ln.g"]),
-                                L.ptr(self.w["up_ln.b"]), 1e-6, P, s, c // 4, c, L.ptr(up1), L.stream())
-        if rc == L.E_UNSUPPORTED:
-            g1 = self._gemm(k16, "up1", bf, bias=False)                                   # [P*S, 4 * c/4]
-            rc = lib.ovo_sam_upscale_ln(L.ptr(g1), L.ptr(self.w["up1.b"]), L.ptr(f1), L.ptr(self.w["up_ln.g"]), L.ptr(self.w["up_ln.b"]), 1e-6,
-                                        P, s, c // 4, L.ptr(up1), L.stream())
-        L.check(rc)
-        first = 1 if multimask else 0
-        n_out = nm - first if multimask else 1
-        masks = torch.empty((P, n_out, 4 * s, 4 * s), dtype=f32, device=dev)
-        hy = hyper if multimask else hyper[:, :1].contiguous()
-        n_m, fst = (nm, 1) if multimask else (1, 0)
-        rc = lib.ovo_sam_up2_masks(L.ptr(up1), L.ptr(self.w["up2.w"]), L.ptr(self.w["up2.b"]), L.ptr(f0), L.ptr(hy), n_m, fst, P, 2 * s, c // 8,
-                                   c // 4, L.ptr(masks), L.stream())
-        if rc == L.E_UNSUPPORTED:
-            g2 = self._gemm(up1, "up2", bf, bias=False)                                   # [P*4S, 4 * c/8]
-            rc = lib.ovo_sam_upscale_masks(L.ptr(g2), L.ptr(self.w["up2.b"]), L.ptr(f0), L.ptr(hy), n_m, fst, P, 2 * s, c // 8, L.ptr(masks),
-                                           L.stream())
-        L.check(rc)
-        return (masks, iou[:, 1:]) if multimask else (masks, iou[:, :1])
+        iou, hyper = self._heads(tok.q16)
+        # multimask: mask tokens 1 .. nm - 1 are the outputs; otherwise token 0 alone, and only its hyper-network row is handed on
+        first, n = (1, spec.n_mask_tokens) if multimask else (0, 1)
+        up1 = self._up1_ln(keys.k16, f1)
+        masks = self._up2_masks(up1, f0, hyper[:, :n].contiguous(), first)
+        return masks, iou[:, first:n]
+
