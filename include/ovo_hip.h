@@ -963,6 +963,39 @@ int ovo_tsdf_mesh_plan(const void *vol, const ovo_tsdf_volume_t *desc, const int
 int ovo_tsdf_mesh_emit(const void *vol, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight, const void *ws,
                        size_t ws_bytes, float *vertices, int32_t *faces, int64_t V, int64_t T, ovo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Colour in the volume (still ABI v23: entry points added, none changed; restated in tests/tsdf_color_restatement.py).
+ *
+ * The colour volume: a second device array beside `vol`, uint16 [nz][ny][nx][4] = (R, G, B, spare), x fastest, 8 bytes a voxel, the volume's
+ * indexing and its 16-byte alignment rule; all-zero bytes mean "unobserved".  A channel is 8.8 fixed point: level * 256, 0 .. 65280.
+ * ovo_tsdf_color_bytes: its size, or 0 for a descriptor the entry points would refuse.  Colour has no weight of its own: it shares W.
+ *
+ * ovo_tsdf_integrate_color: ovo_tsdf_integrate with rgb uint8 [h][w][3] (dense) beside the depth image.  (F, W) come out bit-equal to
+ * ovo_tsdf_integrate on the same inputs.  A frame updates a voxel's colour exactly when it updates its (F, W), with the pixel (v, u) the depth was
+ * read at; per channel ch, with c = rgb[v][u][ch], W the weight BEFORE the update and W1 = W + 1:
+ *   q <- (uint16) rintf(((float) q * W + 256.0f * (float) c) / W1)          every step one f32 IEEE operation
+ * and the spare word is stored as it was read.  For an integer max_weight <= 127 this is exact integer arithmetic: the quotient of two integers
+ * below 2^24, rounded half to even.  Nothing outside [lo, hi) is touched in either array.
+ *
+ * ovo_tsdf_raycast_color: ovo_tsdf_raycast (depth_out bit-equal) and rgb_out uint8 [h][w][3], (0, 0, 0) without a hit.  At a hit found at sample
+ * k the samples k - 1 and k are both valid.  For each of the two, each channel is the trilinear blend of the eight corners' (float) q with that
+ * sample's t and lerp in the order above (x, then y, then z); then c = lerp(c_{k-1}, c_k, s) with s = f_prev / (f_prev - f_k), the quotient the
+ * depth uses; then out = (uint8) rintf(fminf(fmaxf(c / 256.0f, 0.0f), 255.0f)).  Colour is loaded only at a hit.
+ *
+ * ovo_tsdf_mesh_colors: after ovo_tsdf_mesh_plan, with the same vol, desc, lo, hi, min_weight and workspace; rgb_out uint8 [V][3].  Vertex n of
+ * the emit order lies on the edge from its owner p to q = p + offset at t = F_p / (F_p - F_q); per channel its colour is
+ * lerp((float) q_p, (float) q_q, t), then / 256, clamp and rintf as above.  The plan's head is read back as by ovo_tsdf_mesh_emit; V == 0 (of a
+ * plan without vertices) queues nothing.
+ * OVO_E_ARG, nothing launched: what the colourless counterpart refuses, a null or not 16-byte aligned col, a null rgb / rgb_out;
+ * mesh_colors: V negative, above 2^31 - 1 or not the plan's. */
+size_t ovo_tsdf_color_bytes(const ovo_tsdf_volume_t *desc);
+int ovo_tsdf_integrate_color(void *vol, void *col, const ovo_tsdf_volume_t *desc, const float *depth, const uint8_t *rgb, const ovo_tsdf_camera_t *cam,
+                             const int32_t *lo, const int32_t *hi, ovo_stream_t stream);
+int ovo_tsdf_raycast_color(const void *vol, const void *col, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, float *depth_out,
+                           uint8_t *rgb_out, ovo_stream_t stream);
+int ovo_tsdf_mesh_colors(const void *vol, const void *col, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight,
+                         const void *ws, size_t ws_bytes, uint8_t *rgb_out, int64_t V, ovo_stream_t stream);
+
 
 /* =============================================================================================
  * The keyframe chain without host round trips (MI355X extension of a6 / a9; what the reference does with a `.sum()` / vstack

@@ -3,10 +3,18 @@
 //   ovo_tsdf_integrate   k_tsdf_integrate<V>   one launch over the index box [lo, hi): one thread owns a voxel (V = 1, 8 bytes) or two x-neighbours
 //                                              (V = 2, 16 bytes, volumes with an even nx: every pair is 16-byte aligned), lanes along x
 //   ovo_tsdf_raycast     k_tsdf_raycast        one launch, one thread per pixel, 16 x 16 pixel tiles: a fixed-step march, trilinear samples
+//   ovo_tsdf_integrate_color   k_tsdf_integrate_color<V>   the same launch with a colour volume beside the first: a voxel's colour
+//                                              is updated exactly when its (F, W) is, from the pixel the depth was read at
+//   ovo_tsdf_raycast_color     k_tsdf_raycast_color        the same march; at a hit, 16 eight-byte colour loads and three blends per channel
 // The volume is float2 [nz][ny][nx] = (F, W), x fastest; all-zero bytes are "unobserved".  No atomics, no cross-thread traffic: both results are pure
 // functions of their inputs, bit-equal from run to run and whatever OVO_TSDF_GRID_CAP says (it only changes which workgroup visits a voxel).
 // Every volume index is in range by construction: integrate's box is checked against the volume on the host, the ray caster tests a sample's base
 // cell against [0, n - 2] on all three axes BEFORE it forms an address, and issues no load for a sample that fails.
+// The colour volume is uint2 [nz][ny][nx] (four u16: R, G, B, spare) with the volume's indexing.  Every `col` address is formed from the index the `vol`
+// address is formed from: integrate adds one `idx` to both bases; the ray caster reads colour only at a hit, at the base cells of the samples k - 1 and
+// k, both of which passed the march's range test -- the march keeps no index alive from sample to sample, so both are formed again by the march's own
+// expressions (the same IEEE operations on the same values) and clamped to [0, n - 2], which changes nothing.  Every `rgb` address is formed from the (v, u) that
+// tsdf_sample has tested against the image; rgb_out is written at the pixel depth_out is.
 // This file is compiled with -ffp-contract=off (projection.h): f32 operations are single IEEE operations in the order written, except the dot3 / dot4 chains.
 #include <math.h>
 
@@ -23,15 +31,17 @@ constexpr int TSDF_TILE = 16;                              // ray-cast pixel til
 struct TsdfCam { float c2w[12], w2c[12], fx, fy, cx, cy; int h, w; float near, far; };
 struct TsdfBox { int x0, y0, z0, x1, y1, z1; };
 
-// What one depth frame says about the voxel at (i, j, k): false = nothing (the voxel keeps its bits), true = the sample f in [-1, 1].
-__device__ __forceinline__ bool tsdf_sample(const TsdfVol &v, const TsdfCam &c, const float *__restrict__ depth, int i, int j, int k, float &f) {
+// What one depth frame says about the voxel at (i, j, k): false = nothing (the voxel keeps its bits), true = the sample f in [-1, 1] and the
+// index v * w + u of the pixel it was read at.
+__device__ __forceinline__ bool tsdf_sample(const TsdfVol &v, const TsdfCam &c, const float *__restrict__ depth, int i, int j, int k, float &f, int64_t &pix) {
     const float x = __fadd_rn(v.ox, __fmul_rn(v.voxel, (float)i)), y = __fadd_rn(v.oy, __fmul_rn(v.voxel, (float)j));
     const float z = __fadd_rn(v.oz, __fmul_rn(v.voxel, (float)k));
     const float px = dot4(c.w2c, x, y, z, 1.0f), py = dot4(c.w2c + 4, x, y, z, 1.0f), pz = dot4(c.w2c + 8, x, y, z, 1.0f);
     if (!(pz > 0.0f)) return false;
     const float uf = rintf(c.fx * px / pz + c.cx), vf = rintf(c.fy * py / pz + c.cy);
     if (!(uf >= 0.0f && uf <= (float)(c.w - 1) && vf >= 0.0f && vf <= (float)(c.h - 1))) return false;      // (NaN fails)
-    const float d = depth[(int64_t)(int)vf * c.w + (int)uf];
+    pix = (int64_t)(int)vf * c.w + (int)uf;
+    const float d = depth[pix];
     if (!(fabsf(d) < INFINITY && d >= c.near && d <= c.far)) return false;                                  // (NaN fails)
     const float sdf = d - pz;
     if (sdf < -v.trunc) return false;
@@ -60,7 +70,8 @@ __global__ void __launch_bounds__(256) k_tsdf_integrate(float2 *__restrict__ vol
         if (V == 2) {
             const bool in0 = i >= b.x0, in1 = i + 1 < b.x1;                                      // (at least one of them)
             float f0 = 0.0f, f1 = 0.0f;
-            const bool up0 = in0 && tsdf_sample(v, c, depth, i, j, k, f0), up1 = in1 && tsdf_sample(v, c, depth, i + 1, j, k, f1);
+            int64_t px;
+            const bool up0 = in0 && tsdf_sample(v, c, depth, i, j, k, f0, px), up1 = in1 && tsdf_sample(v, c, depth, i + 1, j, k, f1, px);
             if (!(up0 || up1)) continue;
             if (in0 && in1) {
                 float4 a = *(float4 *)p;
@@ -75,7 +86,8 @@ __global__ void __launch_bounds__(256) k_tsdf_integrate(float2 *__restrict__ vol
             }
         } else {
             float f = 0.0f;
-            if (!tsdf_sample(v, c, depth, i, j, k, f)) continue;
+            int64_t px;
+            if (!tsdf_sample(v, c, depth, i, j, k, f, px)) continue;
             float2 a = *p;
             tsdf_update(a.x, a.y, f, v.max_weight);
             *p = a;
@@ -83,12 +95,99 @@ __global__ void __launch_bounds__(256) k_tsdf_integrate(float2 *__restrict__ vol
     }
 }
 
-__device__ __forceinline__ float lerp1(float a, float b, float t) { return a + t * (b - a); }      // three operations, three roundings
+// One channel: q <- rint((q W + 256 c) / W1), W the weight BEFORE this frame's update.  For an integer max_weight <= 127 both numerator terms and
+// their sum are integers below 2^24, so the only rounding is the division's, and rintf takes the quotient half to even.
+__device__ __forceinline__ uint32_t color_mix(uint32_t q, float W, float W1, uint8_t c) { return (uint32_t)rintf(((float)q * W + 256.0f * (float)c) / W1); }
+
+__device__ __forceinline__ void tsdf_update_color(uint32_t &rg, uint32_t &bs, float W, const uint8_t *__restrict__ rgb, int64_t pix) {
+    const float W1 = W + 1.0f;
+    const uint8_t *s = rgb + pix * 3;
+    rg = color_mix(rg & 0xffffu, W, W1, s[0]) | color_mix(rg >> 16, W, W1, s[1]) << 16;
+    bs = color_mix(bs & 0xffffu, W, W1, s[2]) | (bs & 0xffff0000u);                            // the spare word is stored as it was read
+}
+
+// k_tsdf_integrate<V> with the colour volume beside it: the same items, the same decisions, the same (F, W) bits; `idx` serves both arrays.
+template <int V>
+__global__ void __launch_bounds__(256) k_tsdf_integrate_color(float2 *__restrict__ vol, uint2 *__restrict__ col, const TsdfVol v, const float *__restrict__ depth,
+                                                              const uint8_t *__restrict__ rgb, const TsdfCam c, const TsdfBox b) {
+    const uint32_t q0 = (uint32_t)(b.x0 / V), nq = (uint32_t)((b.x1 - 1) / V) - q0 + 1, by = (uint32_t)(b.y1 - b.y0);
+    const uint64_t items = (uint64_t)nq * by * (uint32_t)(b.z1 - b.z0);                          // <= 2^31
+    for (uint64_t it = (uint64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (uint64_t)gridDim.x * 256) {
+        const uint32_t row = (uint32_t)it / nq, q = (uint32_t)it - row * nq;                     // (it < 2^32)
+        const uint32_t kk = row / by, jj = row - kk * by;
+        const int i = (int)(q0 + q) * V, j = b.y0 + (int)jj, k = b.z0 + (int)kk;
+        const int64_t idx = ((int64_t)k * v.ny + j) * v.nx + i;
+        float2 *p = vol + idx;
+        uint2 *pc = col + idx;
+        if (V == 2) {
+            const bool in0 = i >= b.x0, in1 = i + 1 < b.x1;                                      // (at least one of them)
+            float f0 = 0.0f, f1 = 0.0f;
+            int64_t px0 = 0, px1 = 0;
+            const bool up0 = in0 && tsdf_sample(v, c, depth, i, j, k, f0, px0), up1 = in1 && tsdf_sample(v, c, depth, i + 1, j, k, f1, px1);
+            if (!(up0 || up1)) continue;
+            if (in0 && in1) {
+                float4 a = *(float4 *)p;
+                uint4 w = *(uint4 *)pc;
+                if (up0) { tsdf_update_color(w.x, w.y, a.y, rgb, px0); tsdf_update(a.x, a.y, f0, v.max_weight); }
+                if (up1) { tsdf_update_color(w.z, w.w, a.w, rgb, px1); tsdf_update(a.z, a.w, f1, v.max_weight); }
+                *(float4 *)p = a;
+                *(uint4 *)pc = w;
+            } else {
+                const int o = in0 ? 0 : 1;
+                float2 a = p[o];
+                uint2 w = pc[o];
+                tsdf_update_color(w.x, w.y, a.y, rgb, in0 ? px0 : px1);
+                tsdf_update(a.x, a.y, in0 ? f0 : f1, v.max_weight);
+                p[o] = a;
+                pc[o] = w;
+            }
+        } else {
+            float f = 0.0f;
+            int64_t px = 0;
+            if (!tsdf_sample(v, c, depth, i, j, k, f, px)) continue;
+            float2 a = *p;
+            uint2 w = *pc;
+            tsdf_update_color(w.x, w.y, a.y, rgb, px);
+            tsdf_update(a.x, a.y, f, v.max_weight);
+            *p = a;
+            *pc = w;
+        }
+    }
+}
 
 // The samples of pixel (v, u) lie at z_k = near + k dz, k = 0 .. kmax.  [k0, k1] is a range outside of which every sample is provably outside the volume
 // (slabs of the box grown by a voxel and a relative margin, two steps added at each end); inside it the validity test decides, as it would for every k.
-__global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const float2 *__restrict__ vol, const TsdfVol v, const TsdfCam c, float dz, int kmax,
-                                                                        int tiles_x, float *__restrict__ out) {
+// The three channels of sample k of a ray, each the trilinear blend of the eight corners' (float) q with the sample's own t, along x, then y, then z.
+// Only called for a sample the march found valid: the base cell is then in [0, n - 2] already, and the clamp is a no-op that keeps every address in range.
+__device__ __forceinline__ void tsdf_cell_color(const uint2 *__restrict__ col, const TsdfVol &v, const TsdfCam &c, float dz, int k, const float t0[3],
+                                                const float dw[3], float out[3]) {
+    const float org[3] = {v.ox, v.oy, v.oz};
+    const int n[3] = {v.nx, v.ny, v.nz};
+    const float zk = c.near + (float)k * dz;
+    float tt[3];
+    int b[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float pos = t0[a] + zk * dw[a];
+        const float g = (pos - org[a]) / v.voxel;
+        const float bf = floorf(g);
+        tt[a] = g - bf;
+        b[a] = (int)fminf(fmaxf(bf, 0.0f), (float)(n[a] - 2));
+    }
+    const uint2 *p = col + ((int64_t)b[2] * v.ny + b[1]) * v.nx + b[0];
+    const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
+    const uint2 c000 = p[0], c100 = p[1], c010 = p[sy], c110 = p[sy + 1], c001 = p[sz], c101 = p[sz + 1], c011 = p[sz + sy], c111 = p[sz + sy + 1];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+        out[ch] = lerp1(lerp1(lerp1(color_channel(c000, ch), color_channel(c100, ch), tt[0]), lerp1(color_channel(c010, ch), color_channel(c110, ch), tt[0]), tt[1]),
+                        lerp1(lerp1(color_channel(c001, ch), color_channel(c101, ch), tt[0]), lerp1(color_channel(c011, ch), color_channel(c111, ch), tt[0]), tt[1]),
+                        tt[2]);
+}
+
+// COLOR: at a hit the colour volume is read at the base cells of the two bracketing samples; the march itself is the same code for both kernels.
+template <bool COLOR>
+__device__ __forceinline__ void tsdf_march(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v, const TsdfCam c, float dz, int kmax,
+                                           int tiles_x, float *__restrict__ out, uint8_t *__restrict__ rgb_out) {
     const int tile = blockIdx.x, ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const int pu = tx * TSDF_TILE + (threadIdx.x & (TSDF_TILE - 1)), pv = ty * TSDF_TILE + (threadIdx.x / TSDF_TILE);
     if (pu >= c.w || pv >= c.h) return;
@@ -119,6 +218,7 @@ __global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const flo
     }
     // ---- the march
     float depth = 0.0f, f_prev = 0.0f;
+    float rgbf[3] = {0.0f, 0.0f, 0.0f};
     bool valid_prev = false;
     for (int k = k0; k <= k1; ++k) {
         const float zk = c.near + (float)k * dz;
@@ -144,13 +244,40 @@ __global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const flo
         const float f = lerp1(lerp1(lerp1(c000.x, c100.x, tt[0]), lerp1(c010.x, c110.x, tt[0]), tt[1]),
                               lerp1(lerp1(c001.x, c101.x, tt[0]), lerp1(c011.x, c111.x, tt[0]), tt[1]), tt[2]);
         if (valid_prev) {
-            if (f_prev > 0.0f && f <= 0.0f) { depth = (c.near + (float)(k - 1) * dz) + dz * (f_prev / (f_prev - f)); break; }
+            if (f_prev > 0.0f && f <= 0.0f) {
+                const float s = f_prev / (f_prev - f);
+                depth = (c.near + (float)(k - 1) * dz) + dz * s;
+                if (COLOR) {                                 // sample k - 1 was valid too (valid_prev), so all sixteen corners are observed
+                    float ca[3], cb[3];
+                    tsdf_cell_color(col, v, c, dz, k - 1, t0, dw, ca);
+                    tsdf_cell_color(col, v, c, dz, k, t0, dw, cb);
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch) rgbf[ch] = lerp1(ca[ch], cb[ch], s);
+                }
+                break;
+            }
             if (f_prev <= 0.0f && f > 0.0f) break;           // a back face: no hit
         }
         f_prev = f;
         valid_prev = true;
     }
     out[(int64_t)pv * c.w + pu] = depth;
+    if (COLOR) {                                             // (0, 0, 0) without a hit
+        uint8_t *o = rgb_out + ((int64_t)pv * c.w + pu) * 3;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) o[ch] = color_level(rgbf[ch]);
+    }
+}
+
+__global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const float2 *__restrict__ vol, const TsdfVol v, const TsdfCam c, float dz, int kmax,
+                                                                        int tiles_x, float *__restrict__ out) {
+    tsdf_march<false>(vol, nullptr, v, c, dz, kmax, tiles_x, out, nullptr);
+}
+
+__global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast_color(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v,
+                                                                              const TsdfCam c, float dz, int kmax, int tiles_x, float *__restrict__ out,
+                                                                              uint8_t *__restrict__ rgb_out) {
+    tsdf_march<true>(vol, col, v, c, dz, kmax, tiles_x, out, rgb_out);
 }
 
 const char *tsdf_camera_check(const ovo_tsdf_camera_t *c) {
@@ -193,6 +320,54 @@ extern "C" int ovo_tsdf_integrate(void *vol, const ovo_tsdf_volume_t *desc, cons
     const int grid = ovo_grid(items, 256, cap > 0 ? cap : 256 * 16);
     if (pairs) k_tsdf_integrate<2><<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, tsdf_vol(*desc), depth, tsdf_cam(*cam), b);
     else k_tsdf_integrate<1><<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, tsdf_vol(*desc), depth, tsdf_cam(*cam), b);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
+
+extern "C" size_t ovo_tsdf_color_bytes(const ovo_tsdf_volume_t *desc) {
+    return tsdf_volume_check(desc) ? 0 : (size_t)desc->nx * (size_t)desc->ny * (size_t)desc->nz * sizeof(uint2);
+}
+
+extern "C" int ovo_tsdf_integrate_color(void *vol, void *col, const ovo_tsdf_volume_t *desc, const float *depth, const uint8_t *rgb,
+                                        const ovo_tsdf_camera_t *cam, const int32_t *lo, const int32_t *hi, ovo_stream_t stream) {
+    // everything is checked HERE, before anything is queued
+    OVO_REQUIRE(vol && col && desc && depth && rgb && cam && lo && hi, "null pointer");
+    const char *wrong = tsdf_volume_check(desc);
+    OVO_REQUIRE(!wrong, wrong);
+    wrong = tsdf_camera_check(cam);
+    OVO_REQUIRE(!wrong, wrong);
+    OVO_REQUIRE(((uintptr_t)vol & 15) == 0 && ((uintptr_t)col & 15) == 0 && ((uintptr_t)depth & 3) == 0, "volume or colour volume not 16-byte aligned (depth: 4)");
+    const int n[3] = {desc->nx, desc->ny, desc->nz};
+    for (int a = 0; a < 3; ++a) OVO_REQUIRE(lo[a] >= 0 && lo[a] < hi[a] && hi[a] <= n[a], "the box must lie inside the volume with lo < hi on every axis");
+    const TsdfBox b{lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
+    const bool pairs = (desc->nx & 1) == 0;                 // as ovo_tsdf_integrate: the same items, the same grid
+    const int64_t nq = pairs ? (int64_t)((b.x1 - 1) / 2 - b.x0 / 2 + 1) : (int64_t)(b.x1 - b.x0);
+    const int64_t items = nq * (b.y1 - b.y0) * (b.z1 - b.z0);
+    const int cap = ovo_knob_int("OVO_TSDF_GRID_CAP", 256 * 16);
+    const int grid = ovo_grid(items, 256, cap > 0 ? cap : 256 * 16);
+    if (pairs) k_tsdf_integrate_color<2><<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, (uint2 *)col, tsdf_vol(*desc), depth, rgb, tsdf_cam(*cam), b);
+    else k_tsdf_integrate_color<1><<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, (uint2 *)col, tsdf_vol(*desc), depth, rgb, tsdf_cam(*cam), b);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
+
+extern "C" int ovo_tsdf_raycast_color(const void *vol, const void *col, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, float *depth_out,
+                                      uint8_t *rgb_out, ovo_stream_t stream) {
+    // everything is checked HERE, before anything is queued
+    OVO_REQUIRE(vol && col && desc && cam && depth_out && rgb_out, "null pointer");
+    const char *wrong = tsdf_volume_check(desc);
+    OVO_REQUIRE(!wrong, wrong);
+    wrong = tsdf_camera_check(cam);
+    OVO_REQUIRE(!wrong, wrong);
+    OVO_REQUIRE(finite_f(cam->far), "far must be finite for a march");
+    OVO_REQUIRE(((uintptr_t)vol & 15) == 0 && ((uintptr_t)col & 15) == 0 && ((uintptr_t)depth_out & 3) == 0,
+                "volume or colour volume not 16-byte aligned (depth_out: 4)");
+    OVO_REQUIRE(dz > 0.0f && finite_f(dz), "dz must be > 0");
+    const double steps = ceil(((double)cam->far - (double)cam->near) / (double)dz);
+    OVO_REQUIRE(steps <= (double)TSDF_MAX_STEPS, "more than 4096 steps between near and far");
+    const int tiles_x = (cam->w + TSDF_TILE - 1) / TSDF_TILE, tiles_y = (cam->h + TSDF_TILE - 1) / TSDF_TILE;      // (tiles_x * tiles_y < 2^27)
+    k_tsdf_raycast_color<<<tiles_x * tiles_y, TSDF_TILE * TSDF_TILE, 0, (hipStream_t)stream>>>((const float2 *)vol, (const uint2 *)col, tsdf_vol(*desc),
+                                                                                              tsdf_cam(*cam), dz, (int)steps, tiles_x, depth_out, rgb_out);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }

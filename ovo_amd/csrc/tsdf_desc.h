@@ -22,4 +22,9 @@ static inline const char *tsdf_volume_check(const ovo_tsdf_volume_t *d) {
     return nullptr;
 }
 
+// The colour volume: uint16 [nz][ny][nx][4] = (R, G, B, spare) in 8.8 fixed point, read as uint2 = (R | G << 16, B | spare << 16).
+__device__ __forceinline__ float lerp1(float a, float b, float t) { return a + t * (b - a); }      // three operations, three roundings
+__device__ __forceinline__ float color_channel(uint2 q, int ch) { return (float)(ch == 0 ? q.x & 0xffffu : ch == 1 ? q.x >> 16 : q.y & 0xffffu); }
+__device__ __forceinline__ uint8_t color_level(float c) { return (uint8_t)rintf(fminf(fmaxf(c / 256.0f, 0.0f), 255.0f)); }      // (fmaxf drops a NaN: 0)
+
 static inline TsdfVol tsdf_vol(const ovo_tsdf_volume_t &d) { return TsdfVol{d.nx, d.ny, d.nz, d.voxel, d.origin[0], d.origin[1], d.origin[2], d.trunc, d.max_weight}; }

@@ -4,7 +4,7 @@ differs, through the same attributes and methods:
 
     frame                    the prepared `Frame` the next alignment runs against
     spare                    the pyramid buffer the next frame is written into (None: a new one); a LOST frame's own, set by the tracker
-    start(depth, aligner, t) the first frame (time stamp t), at the identity pose
+    start(depth, aligner, t) the first frame (time stamp t), at the identity pose; `TsdfReference(color=True)` takes rgb= here and in `tracked`
     aim(aligner)             the device start pose before an alignment is queued
     compose(c2w, kf_c2w, T)  an alignment's result T -> (the frame's pose, the pose relative to the keyframe that `keyframe_decision` takes)
     tracked(cur, depth, c2w, is_kf, aligner, t=None, kf=0, relative=None)   after an OK frame at pose c2w (time stamp t, hanging on keyframe kf at
@@ -63,9 +63,13 @@ class TsdfReference:
     history > 0: the last `history` fused depth images are kept (`tsdf_utils.TsdfHistory`), each with the keyframe it hangs
     on and its pose relative to it, and `corrected` fuses the volume again from them after a loop closure.  The keyframes' OWN depth pyramids are
     then kept as `KeyframeReference` keeps them -- `tracked` returns the outgoing one at a keyframe -- because loop verification aligns keyframe
-    images, not model images."""
+    images, not model images.
 
-    def __init__(self, prepare, K, max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far, history=0) -> None:
+    color: the volume and the history are made with color=True and every fused frame brings its colour image; the model
+    image the next frame is aligned to stays the depth-only ray cast, so poses do not depend on it.  `render(c2w)` casts depth and colour."""
+
+    def __init__(self, prepare, K, max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far, history=0,
+                 color=False) -> None:
         self.prepare, self.K = prepare, K
         self.dims, self.voxel = tuple(int(d) for d in tsdf_dims), float(tsdf_voxel)
         self.origin = tuple(-0.5 * self.voxel * (n - 1) for n in self.dims) if tsdf_origin is None else tuple(float(o) for o in tsdf_origin)
@@ -74,15 +78,17 @@ class TsdfReference:
         self.far = float(max_depth) if tsdf_far is None else float(tsdf_far)
         self.volume = self.model_depth = self.frame = self.spare = self._eye = None
         self.history_capacity, self.history, self._kf = int(history), None, None
+        self.color = bool(color)
+        self._more = {"color": True} if self.color else {}     # a plain model is made by the very calls it was made by before there was colour
 
-    def start(self, depth, aligner, t=None) -> None:
-        self.volume = tsdf_utils.TsdfVolume(self.dims, self.voxel, self.origin, self.trunc, self.max_weight, device=depth.device)
+    def start(self, depth, aligner, t=None, rgb=None) -> None:
+        self.volume = tsdf_utils.TsdfVolume(self.dims, self.voxel, self.origin, self.trunc, self.max_weight, device=depth.device, **self._more)
         self._eye = torch.eye(4, dtype=torch.float32, device=depth.device)[:3].reshape(12).contiguous()
         if self.history_capacity > 0:                      # the first keyframe's own pyramid, and history entry 0
             self._kf = self.prepare(depth, None)
-            self.history = tsdf_utils.TsdfHistory(self.history_capacity, int(depth.shape[0]), int(depth.shape[1]), device=depth.device)
-            self.history.add(depth, t, 0, np.eye(4))
-        self._fuse(depth, EYE)
+            self.history = tsdf_utils.TsdfHistory(self.history_capacity, int(depth.shape[0]), int(depth.shape[1]), device=depth.device, **self._more)
+            self.history.add(depth, t, 0, np.eye(4), **self._with(rgb))
+        self._fuse(depth, EYE, rgb)
 
     def aim(self, aligner) -> None:
         aligner.T.copy_(self._eye)                         # device to device: no host wait
@@ -91,7 +97,10 @@ class TsdfReference:
         c2w = (c2w.astype(np.float64) @ T.astype(np.float64)).astype(np.float32)      # an f64 product, rounded once
         return c2w, U.rigid_inverse(kf_c2w) @ c2w.astype(np.float64)
 
-    def tracked(self, cur, depth, c2w, is_kf, aligner, t=None, kf=0, relative=None):
+    def _with(self, rgb) -> dict:
+        return {"rgb": rgb} if self.color else {}
+
+    def tracked(self, cur, depth, c2w, is_kf, aligner, t=None, kf=0, relative=None, rgb=None):
         old = None
         if self.history is None or not is_kf:
             self.spare = cur.pyramid                       # (stream order: the next prepare is queued behind this frame's alignment)
@@ -99,8 +108,8 @@ class TsdfReference:
             old, self._kf = self._kf, cur
             self.spare = old.pyramid
         if self.history is not None:
-            self.history.add(depth, t, kf, np.eye(4) if is_kf else relative)
-        self._fuse(depth, c2w)
+            self.history.add(depth, t, kf, np.eye(4) if is_kf else relative, **self._with(rgb))
+        self._fuse(depth, c2w, rgb)
         return old
 
     def corrected(self, X, c2w) -> None:
@@ -109,11 +118,15 @@ class TsdfReference:
         self.volume.refuse(self.history, self.K, self.history.poses(X), self.near, self.far)
         self._cast(c2w)
 
-    def _fuse(self, depth, c2w) -> None:
+    def _fuse(self, depth, c2w, rgb=None) -> None:
         """Fuses a tracked frame at its pose and ray-casts the model there for the next frame: queued, not waited for."""
         self._hw = (int(depth.shape[0]), int(depth.shape[1]))
-        self.volume.integrate(depth, self.K, c2w, self.near, self.far)
+        self.volume.integrate(depth, self.K, c2w, self.near, self.far, **self._with(rgb))
         self._cast(c2w)
+
+    def render(self, c2w):
+        """(depth f32[h, w], rgb u8[h, w, 3]) of the colour model from c2w, into new tensors: the model image of the frame loop is not touched."""
+        return self.volume.raycast(self.K, self._hw[0], self._hw[1], c2w, self.near, self.far, color=True)
 
     def _cast(self, c2w) -> None:
         self.model_depth = self.volume.raycast(self.K, self._hw[0], self._hw[1], c2w, self.near, self.far, out=self.model_depth)

@@ -41,7 +41,8 @@ class IcpTracker:
                  loop_radius: float = 0.5, loop_angle_deg: float = 30.0, loop_max_candidates: int = 8, loop_iters=None, loop_dist_th: float = 0.2,
                  loop_min_overlap: float = 0.3, loop_max_rms: float = 0.02, loop_max_correction=(0.3, 10.0), loop_min_shift=(0.01, 0.2),
                  loop_max_keyframes: int = 256, model: str = "keyframe", tsdf_dims=(512, 512, 512), tsdf_voxel: float = 0.02, tsdf_origin=None,
-                 tsdf_trunc=None, tsdf_max_weight: float = 64, tsdf_near: float = 0.05, tsdf_far=None, tsdf_history: int = 0) -> None:
+                 tsdf_trunc=None, tsdf_max_weight: float = 64, tsdf_near: float = 0.05, tsdf_far=None, tsdf_history: int = 0,
+                 tsdf_color: bool = False) -> None:
         """No GPU work happens here: buffers are made with the first frame.  The loop_* parameters are read and checked by `LoopCloser`, the
         tsdf_* parameters by `TsdfReference`, whichever mode is chosen.
 
@@ -69,7 +70,11 @@ class IcpTracker:
         close_loops=True is allowed: the keyframes' own depth pyramids are verified against each other as in keyframe mode, the odometry edge is the
         keyframe-to-keyframe transform, and after an applied closure the volume is fused again from the history at the corrected poses
         (`TsdfVolume.refuse`: one memset, then one `ovo_tsdf_integrate` call per kept frame) and ray-cast at the corrected pose, all queued behind that frame's one extra
-        wait.  A frame older than the history is no longer in the model after a re-fusion.  A LOST frame adds nothing to the history."""
+        wait.  A frame older than the history is no longer in the model after a re-fusion.  A LOST frame adds nothing to the history.
+
+        tsdf_color (model="tsdf" only): the volume also fuses the colour image of every tracked frame (1 GB more at 512^3,
+        0.84 MB a frame more in the history), `render_model` shows the model in colour and `extract_mesh(colors=True)` puts it on the mesh.
+        Colour takes no part in the alignment: the model image stays the depth-only ray cast, and poses are bit-identical with it on or off."""
         self.K = np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, dtype=np.float32)[:3, :3].copy()
         self.levels, self.iters = int(levels), tuple(int(i) for i in iters)
         if not 1 <= self.levels <= U.MAX_LEVELS or len(self.iters) != self.levels:
@@ -92,8 +97,11 @@ class IcpTracker:
         if self.model == "tsdf" and self.close_loops and self.tsdf_history == 0:
             raise ValueError("IcpTracker: model='tsdf' with close_loops=True is not built: a corrected trajectory would need the volume fused again")
         # (read in either mode, as the loop parameters are: tsdf_trunc and tsdf_far are the tracker's attributes whatever the model)
+        self.tsdf_color = bool(tsdf_color)
+        if self.tsdf_color and self.model != "tsdf":
+            raise ValueError("IcpTracker: tsdf_color fuses colour into the volume and needs model='tsdf'")
         tsdf = TsdfReference(self._prepare, self.K, self.max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far,
-                             history=self.tsdf_history)
+                             history=self.tsdf_history, color=self.tsdf_color)
         self.tsdf_trunc, self.tsdf_far = tsdf.trunc, tsdf.far
         self._ref = tsdf if self.model == "tsdf" else KeyframeReference(self._prepare)
         self.device = device
@@ -122,18 +130,30 @@ class IcpTracker:
             depth = torch.from_numpy(np.ascontiguousarray(np.asarray(depth, dtype=np.float32)))
         return depth.to(device=self.device, dtype=torch.float32).contiguous()
 
+    def _rgb(self, rgb, depth: torch.Tensor) -> dict:
+        """tsdf_color: {"rgb": the frame's colour image u8[h, w, 3] on the device}; else {} -- the image takes no part and is not looked at."""
+        if not self.tsdf_color:
+            return {}
+        if isinstance(rgb, np.ndarray) and rgb.dtype == np.uint8:
+            rgb = torch.from_numpy(np.ascontiguousarray(rgb))
+        if not isinstance(rgb, torch.Tensor) or rgb.dtype != torch.uint8 or tuple(rgb.shape) != (int(depth.shape[0]), int(depth.shape[1]), 3):
+            got = f"{rgb.dtype} {tuple(rgb.shape)}" if isinstance(rgb, (torch.Tensor, np.ndarray)) else type(rgb).__name__
+            raise ValueError(f"IcpTracker: tsdf_color needs rgb as a u8 array or tensor [{int(depth.shape[0])}, {int(depth.shape[1])}, 3] (got {got})")
+        return {"rgb": rgb.to(device=self.device).contiguous()}
+
     def _prepare(self, depth: torch.Tensor, out: Optional[torch.Tensor]) -> U.Frame:
         return U.prepare_frame(depth, self.K, self.levels, self.max_depth, self.depth_jump, out=out)
 
     def process_image_rgbd(self, rgb, depth, t) -> None:
-        """Tracks one frame (the colour image takes no part); returns when its pose is on the host: one host wait per frame, and one more on a
-        keyframe whose loop candidates are verified."""
+        """Tracks one frame (the colour image takes no part in it; tsdf_color fuses it into the model of a tracked frame); returns when its pose
+        is on the host: one host wait per frame, and one more on a keyframe whose loop candidates are verified."""
         if self.closed:
             raise RuntimeError("IcpTracker: shut down")
         depth, ref = self._depth(depth), self._ref
+        color = self._rgb(rgb, depth)
         if self._aligner is None:                          # the first frame: the identity pose, a keyframe
             self._aligner = U.Aligner(depth.device)
-            ref.start(depth, self._aligner, t)
+            ref.start(depth, self._aligner, t, **color)
             self._state, self._is_kf, self.last = self.OK, True, None
             self._row = self._row_of(t, self._c2w)
             self._keyframes.append(self._row)
@@ -156,7 +176,7 @@ class IcpTracker:
             self._kf_c2w, self._is_kf = self._c2w, True
             self._keyframes.append(self._row)
         n = len(self._keyframes) - 1                       # the keyframe this frame hangs on (itself, when it is one)
-        old = ref.tracked(cur, depth, self._c2w, self._is_kf, self._aligner, t, n, relative)
+        old = ref.tracked(cur, depth, self._c2w, self._is_kf, self._aligner, t, n, relative, **color)
         if self._is_kf and self.close_loops:               # `old`'s pyramid is kept: the next frame takes the one that became free, or a new one
             # model="tsdf": `old` and `cur` are the keyframes' own images, and the edge is keyframe to keyframe, not the alignment to the model
             X, ref.spare = self._loops.keyframe(n, old, cur, res, pixels, min_pairs, edge_T=relative if self.model == "tsdf" else None)
@@ -190,12 +210,22 @@ class IcpTracker:
 
     def extract_mesh(self, **kw):
         """model="tsdf": `TsdfVolume.extract_mesh(**kw)` of the fused model, (vertices f32[V, 3], faces i32[T, 3]) on the device, in the tracker's
-        frame (that of the first camera: a world_ref is applied by whoever holds it, e.g. `OVO.semantic_mesh(transform=)`)."""
+        frame (that of the first camera: a world_ref is applied by whoever holds it, e.g. `OVO.semantic_mesh(transform=)`).  With tsdf_color,
+        `colors=True` adds rgb u8[V, 3], which `OVO.semantic_mesh(rgb=)` carries into the PLY."""
         if self.model != "tsdf":
             raise ValueError("IcpTracker.extract_mesh: model='keyframe' keeps no fused model (build the tracker with model='tsdf')")
         if self.volume is None:
             raise ValueError("IcpTracker.extract_mesh: no frame processed yet (the volume is made with the first frame)")
         return self.volume.extract_mesh(**kw)
+
+    def render_model(self, c2w=None):
+        """tsdf_color: the fused model seen from `c2w` (None: the last good pose), in the tracker's frame: (depth f32[h, w], rgb u8[h, w, 3]) on
+        the device, new tensors; the depth has the bits `model_depth` has at that pose.  Queued on the current stream, not waited for."""
+        if not self.tsdf_color:
+            raise ValueError("IcpTracker.render_model: the model holds no colour (build the tracker with model='tsdf', tsdf_color=True)")
+        if self.volume is None:
+            raise ValueError("IcpTracker.render_model: no frame processed yet (the volume is made with the first frame)")
+        return self._ref.render(self._c2w if c2w is None else np.asarray(c2w.detach().cpu() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float32))
 
     def shutdown(self) -> None:
         self._aligner = self._ref = None                   # with the reference go the keyframe's pyramid, or the volume and its image

@@ -1,6 +1,7 @@
 """A fused geometric model on the GPU: `TsdfVolume`, a dense truncated-signed-distance volume integrated from depth frames (`ovo_tsdf_integrate`)
 ray-cast back into a depth image from any pose (`ovo_tsdf_raycast`) and turned into a triangle mesh (`ovo_tsdf_mesh_plan` / `ovo_tsdf_mesh_emit`):
-csrc/tsdf.hip, csrc/mesh.hip, DESIGN.md sections 17 and 18.  `TsdfHistory` keeps the depth images a volume was fused from, and
+csrc/tsdf.hip, csrc/mesh.hip, DESIGN.md sections 17 and 18.  With `color=True` a second array holds the fused colour of every voxel, and the
+same three steps carry it along (`ovo_tsdf_integrate_color`, `ovo_tsdf_raycast_color`, `ovo_tsdf_mesh_colors`: section 20).  `TsdfHistory` keeps the depth images a volume was fused from, and
 `TsdfVolume.refuse` fuses it again from them at other poses -- what a loop closure needs (section 19).  `frustum_box`, `rigid_inverse_f32` and `volume_desc` / `camera_desc` are pure numpy / ctypes and need no GPU."""
 from __future__ import annotations
 
@@ -72,9 +73,11 @@ def frustum_box(dims: Sequence[int], voxel: float, origin: Sequence[float], trun
 
 class TsdfVolume:
     """A dense TSDF volume on the device: `vol` is f32[nz, ny, nx, 2] = (F, W), zero = unobserved.  dims = (nx, ny, nz); voxel (i, j, k) sits at
-    origin + voxel * (i, j, k) in the frame the poses are given in.  512^3 is 1 GB."""
+    origin + voxel * (i, j, k) in the frame the poses are given in.  512^3 is 1 GB.  `color=True`: `col` is int16[nz, ny, nx, 4] holding the bits of
+    u16 (R, G, B, spare), a channel = level * 256, zero = unobserved; it shares W with `vol`, and every `integrate` then needs `rgb`.  1 GB more."""
 
-    def __init__(self, dims: Sequence[int], voxel: float, origin: Sequence[float], trunc: float, max_weight: float = 64, device="cuda") -> None:
+    def __init__(self, dims: Sequence[int], voxel: float, origin: Sequence[float], trunc: float, max_weight: float = 64, device="cuda",
+                 color: bool = False) -> None:
         self.dims = tuple(int(d) for d in dims)
         self.voxel, self.trunc, self.max_weight = float(voxel), float(trunc), float(max_weight)
         self.origin = tuple(float(o) for o in origin)
@@ -88,56 +91,108 @@ class TsdfVolume:
         nx, ny, nz = self.dims
         self.vol = torch.zeros((nz, ny, nx, 2), dtype=torch.float32, device=device)
         L.dev(self.vol, torch.float32, "volume")
+        self.col = None
+        if color:
+            if int(L.load().ovo_tsdf_color_bytes(C.byref(self.desc))) != nbytes:
+                raise L.OvoHipError("TsdfVolume: the library's colour volume is not 8 bytes a voxel")
+            self.col = torch.zeros((nz, ny, nx, 4), dtype=torch.int16, device=device)
 
     def reset(self) -> None:
         self.vol.zero_()
+        if self.col is not None:
+            self.col.zero_()
+
+    def _rgb(self, rgb, shape, what: str):
+        """The colour image of a call, checked against the volume's kind -- u8 on the device for a colour volume, None for a plain one -- and, when
+        `shape` is given, against (h, w, 3)."""
+        if (rgb is None) != (self.col is None):
+            raise L.OvoHipError(f"TsdfVolume.{what}: " + ("a colour volume needs rgb u8[h, w, 3] with every depth image" if rgb is None else
+                                                         "rgb given to a volume made without color=True"))
+        if rgb is not None and shape is not None:
+            L.dev(rgb, torch.uint8, "rgb")
+            if tuple(rgb.shape) != tuple(shape):
+                raise L.OvoHipError(f"TsdfVolume.{what}: rgb must be {list(shape)} (got {tuple(rgb.shape)})")
+        return rgb
 
     def frustum_box(self, K, h: int, w: int, c2w, near: float, far: float) -> Optional[Box]:
         return frustum_box(self.dims, self.voxel, self.origin, self.trunc, K, h, w, c2w, near, far)
 
-    def integrate(self, depth: torch.Tensor, K, c2w, near: float = 0.05, far: float = 10.0, box: Optional[Box] = None) -> Optional[Box]:
+    def integrate(self, depth: torch.Tensor, K, c2w, near: float = 0.05, far: float = 10.0, box: Optional[Box] = None,
+                  rgb: Optional[torch.Tensor] = None) -> Optional[Box]:
         """Fuses depth f32[h, w] (device) seen from `c2w` into the volume on the current stream; returns the box it visited (None: the frame's
-        frustum misses the volume and nothing was queued).  `box=None` visits `frustum_box(...)`, with the same bits as the whole volume."""
+        frustum misses the volume and nothing was queued).  `box=None` visits `frustum_box(...)`, with the same bits as the whole volume.
+        A colour volume takes `rgb` u8[h, w, 3] (device) with it and updates a voxel's colour where it updates (F, W); without it, or with it on a
+        plain volume, `OvoHipError`."""
+        self._rgb(rgb, None, "integrate")                   # the wrong kind of call is refused before anything else is looked at
         L.dev(depth, torch.float32, "depth")
         if depth.dim() != 2:
             raise L.OvoHipError(f"TsdfVolume.integrate: depth must be [h, w] (got {tuple(depth.shape)})")
         h, w = int(depth.shape[0]), int(depth.shape[1])
+        rgb = self._rgb(rgb, (h, w, 3), "integrate")
         if box is None:
             box = self.frustum_box(K, h, w, c2w, near, far)
             if box is None:
                 return None
         cam = camera_desc(K, h, w, c2w, near, far)
         lo, hi = (C.c_int32 * 3)(*(int(x) for x in box[0])), (C.c_int32 * 3)(*(int(x) for x in box[1]))
-        L.check(L.load().ovo_tsdf_integrate(L.ptr(self.vol), C.byref(self.desc), L.ptr(depth), C.byref(cam), lo, hi, L.stream()))
+        if rgb is None:
+            L.check(L.load().ovo_tsdf_integrate(L.ptr(self.vol), C.byref(self.desc), L.ptr(depth), C.byref(cam), lo, hi, L.stream()))
+        else:
+            L.check(L.load().ovo_tsdf_integrate_color(L.ptr(self.vol), L.ptr(self.col), C.byref(self.desc), L.ptr(depth), L.ptr(rgb), C.byref(cam), lo, hi,
+                                                      L.stream()))
         return box
 
     def refuse(self, history: "TsdfHistory", K, poses, near: float, far: float) -> None:
         """Fuses the volume again from the frames of `history` at `poses` (one per live entry, oldest first: `history.poses(X)`): `reset()`, then
         one `integrate` (`ovo_tsdf_integrate`, the single-frame kernel) per entry in the history's order.  Queues work and never waits.
-        40 us a frame on the device at 456 x 616 into 512^3."""
+        40 us a frame on the device at 456 x 616 into 512^3.  A colour volume fuses its colour again too, from the
+        history's `colors` (a history made with color=True)."""
         entries = history.entries()
         if len(entries) != len(poses):
             raise L.OvoHipError(f"TsdfVolume.refuse: {len(poses)} poses for {len(entries)} frames of the history")
+        color = getattr(self, "col", None) is not None
+        if color and getattr(history, "colors", None) is None:
+            raise L.OvoHipError("TsdfVolume.refuse: a colour volume needs a TsdfHistory made with color=True")
         self.reset()
         for e, c2w in zip(entries, poses):
-            self.integrate(history.depths[e["slot"]], K, c2w, near, far)
+            if color:
+                self.integrate(history.depths[e["slot"]], K, c2w, near, far, rgb=history.colors[e["slot"]])
+            else:
+                self.integrate(history.depths[e["slot"]], K, c2w, near, far)
 
-    def raycast(self, K, h: int, w: int, c2w, near: float, far: float, dz: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The model's depth image f32[h, w] from `c2w` on the current stream (0 = no surface); dz defaults to trunc / 2."""
+    def raycast(self, K, h: int, w: int, c2w, near: float, far: float, dz: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                color: bool = False, out_rgb: Optional[torch.Tensor] = None):
+        """The model's depth image f32[h, w] from `c2w` on the current stream (0 = no surface); dz defaults to trunc / 2.  `color=True` (a colour
+        volume only): (depth, rgb u8[h, w, 3]), the colour blended at the hit, (0, 0, 0) where there is none; the depth has the same bits."""
         dz = self.trunc / 2 if dz is None else float(dz)
+        if color and self.col is None:
+            raise L.OvoHipError("TsdfVolume.raycast: color=True needs a volume made with color=True")
+        if out_rgb is not None and not color:
+            raise L.OvoHipError("TsdfVolume.raycast: out_rgb is only written with color=True")
         if out is None:
             out = torch.empty((int(h), int(w)), dtype=torch.float32, device=self.vol.device)
         L.dev(out, torch.float32, "out")
         if tuple(out.shape) != (int(h), int(w)):
             raise L.OvoHipError(f"TsdfVolume.raycast: out must be [{h}, {w}] (got {tuple(out.shape)})")
         cam = camera_desc(K, h, w, c2w, near, far)
-        L.check(L.load().ovo_tsdf_raycast(L.ptr(self.vol), C.byref(self.desc), C.byref(cam), dz, L.ptr(out), L.stream()))
-        return out
+        if not color:
+            L.check(L.load().ovo_tsdf_raycast(L.ptr(self.vol), C.byref(self.desc), C.byref(cam), dz, L.ptr(out), L.stream()))
+            return out
+        if out_rgb is None:
+            out_rgb = torch.empty((int(h), int(w), 3), dtype=torch.uint8, device=self.vol.device)
+        L.dev(out_rgb, torch.uint8, "out_rgb")
+        if tuple(out_rgb.shape) != (int(h), int(w), 3):
+            raise L.OvoHipError(f"TsdfVolume.raycast: out_rgb must be [{h}, {w}, 3] (got {tuple(out_rgb.shape)})")
+        L.check(L.load().ovo_tsdf_raycast_color(L.ptr(self.vol), L.ptr(self.col), C.byref(self.desc), C.byref(cam), dz, L.ptr(out), L.ptr(out_rgb), L.stream()))
+        return out, out_rgb
 
-    def extract_mesh(self, box: Optional[Box] = None, min_weight: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    def extract_mesh(self, box: Optional[Box] = None, min_weight: float = 1.0, colors: bool = False):
         """The surface inside the index box (None: the whole volume) as a welded triangle mesh on the device: (vertices f32[V, 3] in the volume's
         frame, faces i32[T, 3]); marching tetrahedra over the cells whose eight corners have W >= min_weight (include/ovo_hip.h states the
-        contract).  Normals point into free space.  One host wait, for (V, T); V = 0 returns empty tensors and queues no second call."""
+        contract).  Normals point into free space.  One host wait, for (V, T); V = 0 returns empty tensors and queues no second call.
+        `colors=True` (a colour volume only): (vertices, faces, rgb u8[V, 3]), each vertex's colour blended between the two ends of its edge."""
+        if colors and self.col is None:
+            raise L.OvoHipError("TsdfVolume.extract_mesh: colors=True needs a volume made with color=True")
         box = ((0, 0, 0), self.dims) if box is None else box
         lo, hi = (C.c_int32 * 3)(*(int(x) for x in box[0])), (C.c_int32 * 3)(*(int(x) for x in box[1]))
         lib, dev = L.load(), self.vol.device
@@ -154,32 +209,47 @@ class TsdfVolume:
         if V > 0:
             L.check(lib.ovo_tsdf_mesh_emit(L.ptr(self.vol), C.byref(self.desc), lo, hi, float(min_weight), L.ptr(ws), nbytes, L.ptr(vertices), L.ptr(faces),
                                            V, T, L.stream()))
-        return vertices, faces
+        if not colors:
+            return vertices, faces
+        rgb = torch.empty((V, 3), dtype=torch.uint8, device=dev)
+        if V > 0:
+            L.check(lib.ovo_tsdf_mesh_colors(L.ptr(self.vol), L.ptr(self.col), C.byref(self.desc), lo, hi, float(min_weight), L.ptr(ws), nbytes, L.ptr(rgb), V,
+                                             L.stream()))
+        return vertices, faces, rgb
 
 
 class TsdfHistory:
     """The depth images a volume was fused from, so that it can be fused again from corrected poses (`TsdfVolume.refuse`): a ring `depths`
     f32[capacity, h, w] on the device -- f32, the exact bits that were fused live -- and, on the host, each entry's time stamp, the index `kf`
     of the keyframe it hangs on and `rel` = inv(kf_c2w) @ c2w in f64 (the exact identity for a keyframe itself).  When the ring is full the
-    oldest entry is overwritten: after the next re-fusion the model no longer holds that frame.  1.12 MB a frame at 456 x 616, 1.15 GB at 1024."""
+    oldest entry is overwritten: after the next re-fusion the model no longer holds that frame.  1.12 MB a frame at 456 x 616, 1.15 GB at 1024.
+    `color=True`: a ring `colors` u8[capacity, h, w, 3] beside it, slot for slot (0.84 MB a frame more), and `add` needs `rgb`."""
 
-    def __init__(self, capacity: int, h: int, w: int, device="cuda") -> None:
+    def __init__(self, capacity: int, h: int, w: int, device="cuda", color: bool = False) -> None:
         self.capacity, self.h, self.w = int(capacity), int(h), int(w)
         if not 1 <= self.capacity <= MAX_HISTORY:
             raise ValueError(f"TsdfHistory: capacity must be 1 .. {MAX_HISTORY}")
         self.depths = torch.zeros((self.capacity, self.h, self.w), dtype=torch.float32, device=device)
+        self.colors = torch.zeros((self.capacity, self.h, self.w, 3), dtype=torch.uint8, device=device) if color else None
         self._entries: list = []                           # live entries, oldest first
         self._next = 0                                     # the slot the next frame is written to
 
     def __len__(self) -> int:
         return len(self._entries)
 
-    def add(self, depth: torch.Tensor, t, kf: int, rel) -> int:
-        """Copies depth f32[h, w] into the ring on the current stream (device to device, no host wait); returns its slot."""
+    def add(self, depth: torch.Tensor, t, kf: int, rel, rgb: Optional[torch.Tensor] = None) -> int:
+        """Copies depth f32[h, w] (and, in a colour history, rgb u8[h, w, 3]) into the ring on the current stream (device to device, no host
+        wait); returns its slot."""
         if tuple(depth.shape) != (self.h, self.w) or depth.dtype != torch.float32:
             raise ValueError(f"TsdfHistory.add: depth must be f32 [{self.h}, {self.w}] (got {depth.dtype} {tuple(depth.shape)})")
+        if (rgb is None) != (self.colors is None):
+            raise ValueError("TsdfHistory.add: rgb goes with a history made with color=True, and only with one")
+        if rgb is not None and (tuple(rgb.shape) != (self.h, self.w, 3) or rgb.dtype != torch.uint8):
+            raise ValueError(f"TsdfHistory.add: rgb must be u8 [{self.h}, {self.w}, 3] (got {rgb.dtype} {tuple(rgb.shape)})")
         slot = self._next
         self.depths[slot].copy_(depth)
+        if rgb is not None:
+            self.colors[slot].copy_(rgb)
         if len(self._entries) == self.capacity:
             self._entries.pop(0)                           # it held `slot`
         self._entries.append({"slot": slot, "t": t, "kf": int(kf), "rel": np.array(rel, dtype=np.float64)})
