@@ -996,6 +996,35 @@ int ovo_tsdf_raycast_color(const void *vol, const void *col, const ovo_tsdf_volu
 int ovo_tsdf_mesh_colors(const void *vol, const void *col, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight,
                          const void *ws, size_t ws_bytes, uint8_t *rgb_out, int64_t V, ovo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Surface normals from the volume (still ABI v23: entry points added, none changed; restated in
+ * tests/tsdf_normal_restatement.py).  F grows into free space, so its gradient is the outward normal -- the direction the mesh's winding promises.
+ * Every floating-point step is one f32 IEEE operation; lerp(p, q, t) = p + t * (q - p) as above.
+ *
+ * GRADIENT grad(p; obs) of an observed voxel p, obs a predicate on a voxel.  It is a property of the VOLUME: neighbours are looked up in the whole
+ * volume [0, n), never clipped to a mesh box.  Per axis a, with m = p - e_a, r = p + e_a, lo_ok = p[a] >= 1 && obs(m), hi_ok = p[a] <= n[a] - 2 && obs(r):
+ *   both: g[a] = (F(r) - F(m)) * 0.5f     only hi_ok: F(r) - F(p)     only lo_ok: F(p) - F(m)     neither: 0.0f
+ * No address is formed for a neighbour that fails its index test.  The unit is "F per voxel": the voxel is a cube, nothing is divided by `voxel`.
+ * UNIT unit(g): len = sqrtf(g0*g0 + g1*g1 + g2*g2), products first, then the two sums left to right; (g0/len, g1/len, g2/len) if len > 0 and
+ * finite, otherwise three +0.0f.
+ *
+ * ovo_tsdf_mesh_normals: after ovo_tsdf_mesh_plan, with the same vol, desc, lo, hi, min_weight and workspace; normals_out f32 [V][3], in the
+ * volume's frame.  Vertex n of the emit order lies on the edge from its owner p to q = p + offset at t = F_p / (F_p - F_q), emit's own bits; its
+ * normal is unit(lerp(grad(p), grad(q), t)) per component with obs = OBSERVED (W >= min_weight and |F| <= 1, a NaN fails).  The plan's head is read
+ * back as by ovo_tsdf_mesh_colors, a foreign plan is refused; V == 0 queues nothing; every store is bounded by V.
+ *
+ * ovo_tsdf_raycast_normals: ovo_tsdf_raycast (depth_out bit-equal), with col also ovo_tsdf_raycast_color (rgb_out bit-equal), and normals_out
+ * f32 [h][w][3], three +0.0f without a hit.  At a hit found at sample k the samples k - 1 and k are both valid.  For each of the two, each gradient
+ * component is the trilinear blend (x, then y, then z, that sample's t) of grad(corner; obs) over its eight corners with obs(x) = W(x) > 0, the
+ * march's own validity; then g = lerp(g_{k-1}, g_k, s) with the s the depth uses, and the pixel is unit(g).  Gradients are loaded only at a hit.
+ *
+ * OVO_E_ARG, nothing launched: what the colourless counterpart refuses; a null or not 4-byte aligned normals_out; col and rgb_out that are not
+ * both null or both given; a col not 16-byte aligned; mesh_normals: V negative, above 2^31 - 1 or not the plan's.  Neither call writes to a volume. */
+int ovo_tsdf_mesh_normals(const void *vol, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight, const void *ws,
+                          size_t ws_bytes, float *normals_out, int64_t V, ovo_stream_t stream);
+int ovo_tsdf_raycast_normals(const void *vol, const void *col /* may be NULL */, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz,
+                             float *depth_out, uint8_t *rgb_out /* NULL iff col is NULL */, float *normals_out, ovo_stream_t stream);
+
 
 /* =============================================================================================
  * The keyframe chain without host round trips (MI355X extension of a6 / a9; what the reference does with a `.sum()` / vstack

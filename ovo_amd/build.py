@@ -34,7 +34,7 @@ EXTRA = {"geometry.hip": ["-ffp-contract=off"], "render.hip": ["-ffp-contract=of
          "merger.hip": ["-fno-slp-vectorize"],       # k_merge_clips takes a row's sum of squares and shares its CU: the same treatment as the LayerNorm files
          "icp.hip": ["-ffp-contract=off"],           # projection.h's chains; its f32 vertices, normals and Jacobian rows are stated one IEEE operation at a time
          "tsdf.hip": ["-ffp-contract=off"],          # projection.h's chains; the voxel and colour updates and the trilinear blends are stated one IEEE operation at a time
-         "mesh.hip": ["-ffp-contract=off"]}          # a mesh vertex is t = Fp / (Fp - Fq), g = p + t d, origin + voxel g, its colour p + t (q - p): one rounding each, as tsdf.hip
+         "mesh.hip": ["-ffp-contract=off"]}          # a mesh vertex is t = Fp / (Fp - Fq), g = p + t d, origin + voxel g, its colour p + t (q - p): one rounding each, as tsdf.hip; so are the gradient and its normalisation (tsdf_gradient.h)
 
 
 def hipcc() -> str:

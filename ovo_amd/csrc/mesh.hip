@@ -13,19 +13,23 @@
 //                                          + in-row offset + the number of lower slots in use
 //   ovo_tsdf_mesh_colors k_mesh_colors      the vertex half of k_mesh_emit over the same units: a voxel blends its own colour and
 //                                          that of each used slot's other end with emit's t, one u8 triple a vertex
+//   ovo_tsdf_mesh_normals k_mesh_normals    the same walk: a voxel takes the gradient of F (tsdf_gradient.h) at itself and at each used
+//                                          slot's other end, blends the two with emit's t and normalises, one f32 triple a vertex
 // A word: bits 0-6 the used slots, bits 8-22 the in-row vertex offset (<= 7 * 4095).  B word: bits 0-15 the in-row triangle offset (<= 12 * 4095),
 // bits 16-19 the cell's triangle count, bits 20-27 its corner mask (corner x + 2 y + 4 z inside).
 // The only atomic is the OR into A, whose result does not depend on order: plan and emit are pure functions of their inputs, bit-equal from run to
 // run and whatever OVO_MESH_GRID_CAP says.  Every index is in range by construction: the box is checked against the volume on the host; a thread
 // loads row j + 1 / k + 1 / column i + 1 only where the box has it; a slot is flagged only by a cell that holds both of its ends; emit bounds every
 // store by the V and T it was given, which the host has compared with the plan's.  k_mesh_colors forms every colour address from the index its F
-// address is formed from, and bounds every store by V likewise.
+// address is formed from, and bounds every store by V likewise.  k_mesh_normals reads the neighbours of both ends in the whole VOLUME, not the box: each
+// neighbour's address is formed from the index that has passed the test against [0, n) (tsdf_gradient), and every store is bounded by V.
 // This file is compiled with -ffp-contract=off: the vertex is t = Fp / (Fp - Fq), g = p + t * d, pos = origin + voxel * g, one rounding each.
 #include <string.h>
 
 #include "common.h"
 #include "mesh_table.h"
 #include "tsdf_desc.h"
+#include "tsdf_gradient.h"
 
 namespace {
 
@@ -310,6 +314,45 @@ __global__ void __launch_bounds__(256) k_mesh_colors(const float2 *__restrict__ 
     }
 }
 
+// The normal of vertex n of the emit order: unit(lerp1(grad(p), grad(q), t)) per component with t = Fp / (Fp - Fq), emit's own bits; both ends are
+// OBSERVED because a slot is flagged only by a valid cell, and so are the neighbours that count.
+__global__ void __launch_bounds__(256) k_mesh_normals(const float2 *__restrict__ vol, const TsdfVol v, const MeshBox b, float min_weight,
+                                                      const uint32_t *__restrict__ A, const uint2 *__restrict__ rows, float *__restrict__ normals, int64_t V) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t chunks = (uint32_t)(b.bx + 63) >> 6;
+    const uint64_t units = (uint64_t)((uint32_t)b.by * (uint32_t)b.bz) * chunks;
+    const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
+    const TsdfObserved obs{min_weight};
+    for (uint64_t u = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < units; u += (uint64_t)gridDim.x * 4) {
+        const MeshUnit m = mesh_unit(u, chunks, b, lane);
+        const uint32_t a = m.live ? A[m.lin] : 0;
+        if (!(a & 127)) continue;
+        const int pi = b.x0 + m.i, pj = b.y0 + (int)m.jj, pk = b.z0 + (int)m.kk;
+        const float2 *p = vol + (int64_t)pk * sz + (int64_t)pj * sy + pi;
+        const float Fp = p->x;
+        float gp[3];
+        tsdf_gradient(vol, v, pi, pj, pk, Fp, obs, gp);
+        int64_t vi = (int64_t)rows[m.row].x + (a >> 8);
+#pragma unroll
+        for (int s = 0; s < 7; ++s) {
+            if (!(a >> s & 1)) continue;
+            const int d = MESH_SLOT[s];
+            const float Fq = p[(d & 1) + (d >> 1 & 1) * sy + (d >> 2) * sz].x;
+            const float t = Fp / (Fp - Fq);
+            if (vi < V) {
+                float gq[3], g[3], nrm[3];
+                tsdf_gradient(vol, v, pi + (d & 1), pj + (d >> 1 & 1), pk + (d >> 2), Fq, obs, gq);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) g[c] = lerp1(gp[c], gq[c], t);
+                tsdf_unit(g, nrm);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) normals[vi * 3 + c] = nrm[c];
+            }
+            ++vi;
+        }
+    }
+}
+
 // ---- host
 const char *mesh_layout(const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, MeshLayout &l) {
     if (!lo || !hi) return "null pointer";
@@ -438,6 +481,31 @@ extern "C" int ovo_tsdf_mesh_colors(const void *vol, const void *col, const ovo_
     const int64_t units = (int64_t)l.nrows * ((l.b.bx + 63) / 64);
     k_mesh_colors<<<mesh_grid(units), 256, 0, s>>>((const float2 *)vol, (const uint2 *)col, tsdf_vol(*desc), l.b, (const uint32_t *)(base + l.off_a),
                                                       (const uint2 *)(base + l.off_rows), rgb_out, V);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
+
+extern "C" int ovo_tsdf_mesh_normals(const void *vol, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight, const void *ws,
+                                     size_t ws_bytes, float *normals_out, int64_t V, ovo_stream_t stream) {
+    // everything is checked HERE, before anything is queued -- the plan's head included, as ovo_tsdf_mesh_emit reads it
+    MeshLayout l;
+    OVO_REQUIRE(normals_out, "null pointer");
+    const char *wrong = mesh_common_check(vol, desc, lo, hi, min_weight, ws, ws_bytes, l);
+    OVO_REQUIRE(!wrong, wrong);
+    OVO_REQUIRE(((uintptr_t)normals_out & 3) == 0, "normals_out not 4-byte aligned");
+    OVO_REQUIRE(V >= 0 && V <= MESH_MAX_COUNT, "V must be 0 .. 2^31 - 1");
+    const hipStream_t s = (hipStream_t)stream;
+    int64_t head[4] = {0, 0, 0, 0}, key[2];
+    mesh_key(desc, l.b, min_weight, key);
+    OVO_HIP(hipMemcpyAsync(head, ws, sizeof(head), hipMemcpyDeviceToHost, s));
+    OVO_HIP(hipStreamSynchronize(s));
+    OVO_REQUIRE(head[2] == key[0] && head[3] == key[1], "the workspace holds no plan for this volume shape, box and min_weight");
+    OVO_REQUIRE(head[0] == V, "V differs from the plan in the workspace");
+    if (V == 0) return OVO_OK;                               // a plan without vertices: nothing to queue
+    const char *base = (const char *)ws;
+    const int64_t units = (int64_t)l.nrows * ((l.b.bx + 63) / 64);
+    k_mesh_normals<<<mesh_grid(units), 256, 0, s>>>((const float2 *)vol, tsdf_vol(*desc), l.b, min_weight, (const uint32_t *)(base + l.off_a),
+                                                       (const uint2 *)(base + l.off_rows), normals_out, V);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }

@@ -6,6 +6,8 @@
 //   ovo_tsdf_integrate_color   k_tsdf_integrate_color<V>   the same launch with a colour volume beside the first: a voxel's colour
 //                                              is updated exactly when its (F, W) is, from the pixel the depth was read at
 //   ovo_tsdf_raycast_color     k_tsdf_raycast_color        the same march; at a hit, 16 eight-byte colour loads and three blends per channel
+//   ovo_tsdf_raycast_normals   k_tsdf_raycast_normals / k_tsdf_raycast_color_normals   the same march; at a hit, the gradient of F
+//                                              (tsdf_gradient.h) at the eight corners of the two bracketing samples, blended as F is, normalised
 // The volume is float2 [nz][ny][nx] = (F, W), x fastest; all-zero bytes are "unobserved".  No atomics, no cross-thread traffic: both results are pure
 // functions of their inputs, bit-equal from run to run and whatever OVO_TSDF_GRID_CAP says (it only changes which workgroup visits a voxel).
 // Every volume index is in range by construction: integrate's box is checked against the volume on the host, the ray caster tests a sample's base
@@ -15,12 +17,15 @@
 // k, both of which passed the march's range test -- the march keeps no index alive from sample to sample, so both are formed again by the march's own
 // expressions (the same IEEE operations on the same values) and clamped to [0, n - 2], which changes nothing.  Every `rgb` address is formed from the (v, u) that
 // tsdf_sample has tested against the image; rgb_out is written at the pixel depth_out is.
+// A normal is read only at a hit too, around the same two base cells, formed again and clamped the same way; a corner's neighbour is addressed only after
+// its index has passed the test against [0, n) (tsdf_gradient), and normals_out is written at the pixel depth_out is.
 // This file is compiled with -ffp-contract=off (projection.h): f32 operations are single IEEE operations in the order written, except the dot3 / dot4 chains.
 #include <math.h>
 
 #include "common.h"
 #include "projection.h"
 #include "tsdf_desc.h"
+#include "tsdf_gradient.h"
 
 namespace {
 
@@ -184,10 +189,41 @@ __device__ __forceinline__ void tsdf_cell_color(const uint2 *__restrict__ col, c
                         tt[2]);
 }
 
-// COLOR: at a hit the colour volume is read at the base cells of the two bracketing samples; the march itself is the same code for both kernels.
-template <bool COLOR>
+// The gradient at sample k of a ray: each component the trilinear blend (x, then y, then z, the sample's own t) of grad(corner; W > 0) over the eight
+// corners.  Only called for a sample the march found valid, as tsdf_cell_color: the same expressions, the same no-op clamp.
+__device__ __forceinline__ void tsdf_cell_gradient(const float2 *__restrict__ vol, const TsdfVol &v, const TsdfCam &c, float dz, int k, const float t0[3],
+                                                   const float dw[3], float out[3]) {
+    const float org[3] = {v.ox, v.oy, v.oz};
+    const int n[3] = {v.nx, v.ny, v.nz};
+    const float zk = c.near + (float)k * dz;
+    float tt[3];
+    int b[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float pos = t0[a] + zk * dw[a];
+        const float g = (pos - org[a]) / v.voxel;
+        const float bf = floorf(g);
+        tt[a] = g - bf;
+        b[a] = (int)fminf(fmaxf(bf, 0.0f), (float)(n[a] - 2));
+    }
+    float gc[8][3];                                          // corner x + 2 y + 4 z; every index below is a compile-time constant
+#pragma unroll
+    for (int cn = 0; cn < 8; ++cn) {
+        const int i = b[0] + (cn & 1), j = b[1] + (cn >> 1 & 1), kk = b[2] + (cn >> 2);      // within [0, n - 1]
+        const float Fp = vol[((int64_t)kk * v.ny + j) * v.nx + i].x;
+        tsdf_gradient(vol, v, i, j, kk, Fp, TsdfSeen{}, gc[cn]);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+        out[a] = lerp1(lerp1(lerp1(gc[0][a], gc[1][a], tt[0]), lerp1(gc[2][a], gc[3][a], tt[0]), tt[1]),
+                       lerp1(lerp1(gc[4][a], gc[5][a], tt[0]), lerp1(gc[6][a], gc[7][a], tt[0]), tt[1]), tt[2]);
+}
+
+// COLOR: at a hit the colour volume is read at the base cells of the two bracketing samples; the march itself is the same code for all four kernels.
+// NORMALS: the gradient is read around the same two cells of a hit, after the march (the loop only notes k and s); three +0.0f without a hit.
+template <bool COLOR, bool NORMALS>
 __device__ __forceinline__ void tsdf_march(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v, const TsdfCam c, float dz, int kmax,
-                                           int tiles_x, float *__restrict__ out, uint8_t *__restrict__ rgb_out) {
+                                           int tiles_x, float *__restrict__ out, uint8_t *__restrict__ rgb_out, float *__restrict__ normals_out) {
     const int tile = blockIdx.x, ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const int pu = tx * TSDF_TILE + (threadIdx.x & (TSDF_TILE - 1)), pv = ty * TSDF_TILE + (threadIdx.x / TSDF_TILE);
     if (pu >= c.w || pv >= c.h) return;
@@ -219,6 +255,8 @@ __device__ __forceinline__ void tsdf_march(const float2 *__restrict__ vol, const
     // ---- the march
     float depth = 0.0f, f_prev = 0.0f;
     float rgbf[3] = {0.0f, 0.0f, 0.0f};
+    float nrm[3] = {0.0f, 0.0f, 0.0f}, hit_s = 0.0f;
+    int hit_k = -1;
     bool valid_prev = false;
     for (int k = k0; k <= k1; ++k) {
         const float zk = c.near + (float)k * dz;
@@ -247,13 +285,14 @@ __device__ __forceinline__ void tsdf_march(const float2 *__restrict__ vol, const
             if (f_prev > 0.0f && f <= 0.0f) {
                 const float s = f_prev / (f_prev - f);
                 depth = (c.near + (float)(k - 1) * dz) + dz * s;
-                if (COLOR) {                                 // sample k - 1 was valid too (valid_prev), so all sixteen corners are observed
+                if (COLOR && !NORMALS) {                     // sample k - 1 was valid too (valid_prev), so all sixteen corners are observed
                     float ca[3], cb[3];
                     tsdf_cell_color(col, v, c, dz, k - 1, t0, dw, ca);
                     tsdf_cell_color(col, v, c, dz, k, t0, dw, cb);
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) rgbf[ch] = lerp1(ca[ch], cb[ch], s);
                 }
+                if (NORMALS) { hit_k = k; hit_s = s; }      // read after the march, when the lanes of a wave that hit at different k have met again
                 break;
             }
             if (f_prev <= 0.0f && f > 0.0f) break;           // a back face: no hit
@@ -261,23 +300,57 @@ __device__ __forceinline__ void tsdf_march(const float2 *__restrict__ vol, const
         f_prev = f;
         valid_prev = true;
     }
+    if (NORMALS && hit_k >= 0) {                             // samples hit_k - 1 and hit_k are both valid: every corner whose gradient is taken is observed
+        float ca[3] = {0.0f, 0.0f, 0.0f}, cb[3] = {0.0f, 0.0f, 0.0f};
+        float ga[3] = {0.0f, 0.0f, 0.0f}, gb[3] = {0.0f, 0.0f, 0.0f}, g[3];
+#pragma unroll 1
+        for (int e = 0; e < 2; ++e) {                        // one sample at a time: this runs once a pixel, and the kernel keeps the march's occupancy
+#pragma unroll
+            for (int a = 0; a < 3; ++a) { ga[a] = gb[a]; ca[a] = cb[a]; }
+            if (COLOR) tsdf_cell_color(col, v, c, dz, hit_k - 1 + e, t0, dw, cb);      // the same operations on the same values as k_tsdf_raycast_color's
+            tsdf_cell_gradient(vol, v, c, dz, hit_k - 1 + e, t0, dw, gb);
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) g[a] = lerp1(ga[a], gb[a], hit_s);
+        tsdf_unit(g, nrm);
+        if (COLOR) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) rgbf[ch] = lerp1(ca[ch], cb[ch], hit_s);
+        }
+    }
     out[(int64_t)pv * c.w + pu] = depth;
     if (COLOR) {                                             // (0, 0, 0) without a hit
         uint8_t *o = rgb_out + ((int64_t)pv * c.w + pu) * 3;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) o[ch] = color_level(rgbf[ch]);
     }
+    if (NORMALS) {
+        float *o = normals_out + ((int64_t)pv * c.w + pu) * 3;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) o[a] = nrm[a];
+    }
 }
 
 __global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const float2 *__restrict__ vol, const TsdfVol v, const TsdfCam c, float dz, int kmax,
                                                                         int tiles_x, float *__restrict__ out) {
-    tsdf_march<false>(vol, nullptr, v, c, dz, kmax, tiles_x, out, nullptr);
+    tsdf_march<false, false>(vol, nullptr, v, c, dz, kmax, tiles_x, out, nullptr, nullptr);
 }
 
 __global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast_color(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v,
                                                                               const TsdfCam c, float dz, int kmax, int tiles_x, float *__restrict__ out,
                                                                               uint8_t *__restrict__ rgb_out) {
-    tsdf_march<true>(vol, col, v, c, dz, kmax, tiles_x, out, rgb_out);
+    tsdf_march<true, false>(vol, col, v, c, dz, kmax, tiles_x, out, rgb_out, nullptr);
+}
+
+__global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast_normals(const float2 *__restrict__ vol, const TsdfVol v, const TsdfCam c, float dz, int kmax,
+                                                                                int tiles_x, float *__restrict__ out, float *__restrict__ normals_out) {
+    tsdf_march<false, true>(vol, nullptr, v, c, dz, kmax, tiles_x, out, nullptr, normals_out);
+}
+
+__global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast_color_normals(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v,
+                                                                                      const TsdfCam c, float dz, int kmax, int tiles_x, float *__restrict__ out,
+                                                                                      uint8_t *__restrict__ rgb_out, float *__restrict__ normals_out) {
+    tsdf_march<true, true>(vol, col, v, c, dz, kmax, tiles_x, out, rgb_out, normals_out);
 }
 
 const char *tsdf_camera_check(const ovo_tsdf_camera_t *c) {
@@ -388,6 +461,32 @@ extern "C" int ovo_tsdf_raycast(const void *vol, const ovo_tsdf_volume_t *desc, 
     const int tiles_x = (cam->w + TSDF_TILE - 1) / TSDF_TILE, tiles_y = (cam->h + TSDF_TILE - 1) / TSDF_TILE;      // (tiles_x * tiles_y < 2^27)
     k_tsdf_raycast<<<tiles_x * tiles_y, TSDF_TILE * TSDF_TILE, 0, (hipStream_t)stream>>>((const float2 *)vol, tsdf_vol(*desc), tsdf_cam(*cam), dz, (int)steps,
                                                                                         tiles_x, depth_out);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
+
+extern "C" int ovo_tsdf_raycast_normals(const void *vol, const void *col, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, float *depth_out,
+                                        uint8_t *rgb_out, float *normals_out, ovo_stream_t stream) {
+    // everything is checked HERE, before anything is queued
+    OVO_REQUIRE(vol && desc && cam && depth_out && normals_out, "null pointer");
+    OVO_REQUIRE((col == nullptr) == (rgb_out == nullptr), "col and rgb_out go together: both null or both given");
+    const char *wrong = tsdf_volume_check(desc);
+    OVO_REQUIRE(!wrong, wrong);
+    wrong = tsdf_camera_check(cam);
+    OVO_REQUIRE(!wrong, wrong);
+    OVO_REQUIRE(finite_f(cam->far), "far must be finite for a march");
+    OVO_REQUIRE(((uintptr_t)vol & 15) == 0 && ((uintptr_t)col & 15) == 0 && ((uintptr_t)depth_out & 3) == 0 && ((uintptr_t)normals_out & 3) == 0,
+                "volume or colour volume not 16-byte aligned (depth_out, normals_out: 4)");
+    OVO_REQUIRE(dz > 0.0f && finite_f(dz), "dz must be > 0");
+    const double steps = ceil(((double)cam->far - (double)cam->near) / (double)dz);
+    OVO_REQUIRE(steps <= (double)TSDF_MAX_STEPS, "more than 4096 steps between near and far");
+    const int tiles_x = (cam->w + TSDF_TILE - 1) / TSDF_TILE, tiles_y = (cam->h + TSDF_TILE - 1) / TSDF_TILE;      // (tiles_x * tiles_y < 2^27)
+    if (col)
+        k_tsdf_raycast_color_normals<<<tiles_x * tiles_y, TSDF_TILE * TSDF_TILE, 0, (hipStream_t)stream>>>(
+            (const float2 *)vol, (const uint2 *)col, tsdf_vol(*desc), tsdf_cam(*cam), dz, (int)steps, tiles_x, depth_out, rgb_out, normals_out);
+    else
+        k_tsdf_raycast_normals<<<tiles_x * tiles_y, TSDF_TILE * TSDF_TILE, 0, (hipStream_t)stream>>>((const float2 *)vol, tsdf_vol(*desc), tsdf_cam(*cam), dz,
+                                                                                                    (int)steps, tiles_x, depth_out, normals_out);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }

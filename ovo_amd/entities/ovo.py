@@ -849,7 +849,7 @@ class OVO:
     # ------------------------------------------------------------------ a labelled surface (no reference counterpart: it shows its result in a window)
     @torch.no_grad()
     def semantic_mesh(self, map_data, vertices: torch.Tensor, faces: torch.Tensor, transform=None, classes: Optional[List[str]] = None,
-                      template="This is a photo of a {}", th: float = 0.0, max_dist: Optional[float] = None, rgb=None) -> Dict[str, Any]:
+                      template="This is a photo of a {}", th: float = 0.0, max_dist: Optional[float] = None, rgb=None, normals=None) -> Dict[str, Any]:
         """The map's labels on a mesh (e.g. `IcpTracker.extract_mesh()`), ready for `mesh_utils.write_ply(path, **out)`:
           "vertices" f32[V,3]  `vertices` moved by the 4 x 4 `transform` (mesh frame -> map frame, e.g. the tracker's world_ref), in f32
           "faces"    i32[T,3]  as given
@@ -857,16 +857,23 @@ class OVO:
                                the nearest of them is farther than `max_dist`, or when the map has fewer than 5 assigned points
           "cls"      i32[V]    `classes` given: `classify_instances(classes, template, th)` of that instance, -1 without one; else None
           "rgb"      u8[V,3]   `rgb` when given (the scene's appearance, e.g. `extract_mesh(colors=True)`: u8[V,3], one row a vertex, else
-                               ValueError); otherwise `mesh_utils.label_colors` of the class when `classes` is given, else of the instance"""
+                               ValueError); otherwise `mesh_utils.label_colors` of the class when `classes` is given, else of the instance
+          "normals"  f32[V,3]  only when `normals` is given (e.g. `extract_mesh(normals=True)`: an f32 tensor [V,3], else ValueError): its rows rotated
+                               by transform[:3, :3] in f32.  The transform is assumed rigid, so they are not normalised again."""
         from ..utils import mesh_utils as M
         pcd, point_ins = map_data[0], map_data[2].reshape(-1)
         v = vertices.to(torch.float32)
         if rgb is not None and not (isinstance(rgb, torch.Tensor) and rgb.dtype == torch.uint8 and tuple(rgb.shape) == (v.shape[0], 3)):
             got = f"{rgb.dtype} {tuple(rgb.shape)}" if isinstance(rgb, torch.Tensor) else type(rgb).__name__
             raise ValueError(f"OVO.semantic_mesh: rgb must be a u8 tensor [{v.shape[0]}, 3], one row a vertex (got {got})")
+        if normals is not None and not (isinstance(normals, torch.Tensor) and normals.dtype == torch.float32 and tuple(normals.shape) == (v.shape[0], 3)):
+            got = f"{normals.dtype} {tuple(normals.shape)}" if isinstance(normals, torch.Tensor) else type(normals).__name__
+            raise ValueError(f"OVO.semantic_mesh: normals must be an f32 tensor [{v.shape[0]}, 3], one row a vertex (got {got})")
         if transform is not None:
             m = torch.as_tensor(np.asarray(transform.detach().cpu() if isinstance(transform, torch.Tensor) else transform, dtype=np.float32)).to(v.device)
             v = v @ m[:3, :3].t() + m[:3, 3]
+            if normals is not None:
+                normals = (normals @ m[:3, :3].t()).contiguous()
         v = v.contiguous()
         assigned = point_ins >= 0
         if int(assigned.sum()) >= 5:
@@ -882,7 +889,10 @@ class OVO:
             cls = table[torch.where(known, instance.long(), torch.full_like(instance, table.numel() - 1).long())].to(torch.int32)
         if rgb is None:
             rgb = torch.from_numpy(M.label_colors(instance if cls is None else cls)).to(v.device)
-        return {"vertices": v, "faces": faces, "instance": instance, "cls": cls, "rgb": rgb}
+        out = {"vertices": v, "faces": faces, "instance": instance, "cls": cls, "rgb": rgb}
+        if normals is not None:
+            out["normals"] = normals
+        return out
 
     # ------------------------------------------------------------------ where the instances are (the viewer's boxes: vis_utils.py:72-87)
     @torch.no_grad()

@@ -124,9 +124,12 @@ class TsdfReference:
         self.volume.integrate(depth, self.K, c2w, self.near, self.far, **self._with(rgb))
         self._cast(c2w)
 
-    def render(self, c2w):
-        """(depth f32[h, w], rgb u8[h, w, 3]) of the colour model from c2w, into new tensors: the model image of the frame loop is not touched."""
-        return self.volume.raycast(self.K, self._hw[0], self._hw[1], c2w, self.near, self.far, color=True)
+    def render(self, c2w, normals: bool = False):
+        """(depth f32[h, w], rgb u8[h, w, 3]) of the colour model from c2w, into new tensors: the model image of the frame loop is not touched.
+        `normals=True` (any volume): the normal image f32[h, w, 3] comes last, and the rgb only from a colour volume."""
+        if not normals:
+            return self.volume.raycast(self.K, self._hw[0], self._hw[1], c2w, self.near, self.far, color=True)
+        return self.volume.raycast(self.K, self._hw[0], self._hw[1], c2w, self.near, self.far, **({"color": True} if self.color else {}), normals=True)
 
     def _cast(self, c2w) -> None:
         self.model_depth = self.volume.raycast(self.K, self._hw[0], self._hw[1], c2w, self.near, self.far, out=self.model_depth)

@@ -211,21 +211,27 @@ class IcpTracker:
     def extract_mesh(self, **kw):
         """model="tsdf": `TsdfVolume.extract_mesh(**kw)` of the fused model, (vertices f32[V, 3], faces i32[T, 3]) on the device, in the tracker's
         frame (that of the first camera: a world_ref is applied by whoever holds it, e.g. `OVO.semantic_mesh(transform=)`).  With tsdf_color,
-        `colors=True` adds rgb u8[V, 3], which `OVO.semantic_mesh(rgb=)` carries into the PLY."""
+        `colors=True` adds rgb u8[V, 3], which `OVO.semantic_mesh(rgb=)` carries into the PLY.  `normals=True` adds vertex normals f32[V, 3] last
+        (the volume's gradient), which `OVO.semantic_mesh(normals=)` carries likewise."""
         if self.model != "tsdf":
             raise ValueError("IcpTracker.extract_mesh: model='keyframe' keeps no fused model (build the tracker with model='tsdf')")
         if self.volume is None:
             raise ValueError("IcpTracker.extract_mesh: no frame processed yet (the volume is made with the first frame)")
         return self.volume.extract_mesh(**kw)
 
-    def render_model(self, c2w=None):
+    def render_model(self, c2w=None, normals: bool = False):
         """tsdf_color: the fused model seen from `c2w` (None: the last good pose), in the tracker's frame: (depth f32[h, w], rgb u8[h, w, 3]) on
-        the device, new tensors; the depth has the bits `model_depth` has at that pose.  Queued on the current stream, not waited for."""
-        if not self.tsdf_color:
+        the device, new tensors; the depth has the bits `model_depth` has at that pose.  Queued on the current stream, not waited for.
+        `normals=True` (any model="tsdf" tracker): (depth, normals f32[h, w, 3]), or (depth, rgb, normals) with tsdf_color --
+        unit normals in the tracker's frame from the volume's gradient, zeros where there is no surface; `tsdf_utils.shade_normals` makes a picture of them."""
+        if normals and self.model != "tsdf":
+            raise ValueError("IcpTracker.render_model: model='keyframe' keeps no fused model (build the tracker with model='tsdf')")
+        if not normals and not self.tsdf_color:
             raise ValueError("IcpTracker.render_model: the model holds no colour (build the tracker with model='tsdf', tsdf_color=True)")
         if self.volume is None:
             raise ValueError("IcpTracker.render_model: no frame processed yet (the volume is made with the first frame)")
-        return self._ref.render(self._c2w if c2w is None else np.asarray(c2w.detach().cpu() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float32))
+        pose = self._c2w if c2w is None else np.asarray(c2w.detach().cpu() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float32)
+        return self._ref.render(pose, normals=True) if normals else self._ref.render(pose)
 
     def shutdown(self) -> None:
         self._aligner = self._ref = None                   # with the reference go the keyframe's pyramid, or the volume and its image

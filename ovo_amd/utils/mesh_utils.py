@@ -49,8 +49,10 @@ def _host(a, dtype, shape_tail) -> np.ndarray:
     return a
 
 
-def _vertex_dtype(rgb: bool, instance: bool, cls: bool) -> np.dtype:
+def _vertex_dtype(rgb: bool, instance: bool, cls: bool, normals: bool = False) -> np.dtype:
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals:                                            # directly after the position: the order MeshLab and Open3D read
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if rgb:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
     if instance:
@@ -64,14 +66,16 @@ _FACE = np.dtype([("n", "u1"), ("vertex_indices", "<i4", (3,))])
 _PLY_TYPE = {"<f4": "float", "u1": "uchar", "|u1": "uchar", "<i4": "int"}
 
 
-def write_ply(path, vertices, faces, rgb=None, instance=None, cls=None) -> None:
-    """binary_little_endian 1.0: `element vertex` with x y z (float), optionally red green blue (uchar), `int instance`, `int class`; `element face`
-    with `list uchar int vertex_indices`.  Tensors or arrays; vertices f32[V, 3], faces i32[T, 3], rgb u8[V, 3], instance / cls integer [V]."""
+def write_ply(path, vertices, faces, rgb=None, instance=None, cls=None, normals=None) -> None:
+    """binary_little_endian 1.0: `element vertex` with x y z (float), optionally nx ny nz (float), red green blue (uchar), `int instance`,
+    `int class`; `element face` with `list uchar int vertex_indices`.  Tensors or arrays; vertices f32[V, 3], faces i32[T, 3], rgb u8[V, 3],
+    instance / cls integer [V], normals f32[V, 3] (their bits are written as they are; a wrong dtype or row count is a ValueError)."""
     v, f = _host(vertices, np.float32, (3,)), _host(faces, np.int32, (3,))
-    vd = _vertex_dtype(rgb is not None, instance is not None, cls is not None)
+    vd = _vertex_dtype(rgb is not None, instance is not None, cls is not None, normals is not None)
     rec = np.zeros(len(v), dtype=vd)
     rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
-    for name, col, dt, tail in (("rgb", rgb, np.uint8, (3,)), ("instance", instance, np.int32, ()), ("class", cls, np.int32, ())):
+    for name, col, dt, tail in (("normals", normals, np.float32, (3,)), ("rgb", rgb, np.uint8, (3,)), ("instance", instance, np.int32, ()),
+                                ("class", cls, np.int32, ())):
         if col is None:
             continue
         col = _host(col, dt, tail)
@@ -79,6 +83,8 @@ def write_ply(path, vertices, faces, rgb=None, instance=None, cls=None) -> None:
             raise ValueError(f"write_ply: {name} has {len(col)} rows for {len(v)} vertices")
         if name == "rgb":
             rec["red"], rec["green"], rec["blue"] = col[:, 0], col[:, 1], col[:, 2]
+        elif name == "normals":
+            rec["nx"], rec["ny"], rec["nz"] = col[:, 0], col[:, 1], col[:, 2]
         else:
             rec[name] = col
     fr = np.zeros(len(f), dtype=_FACE)
@@ -94,7 +100,7 @@ def write_ply(path, vertices, faces, rgb=None, instance=None, cls=None) -> None:
 
 def read_ply(path) -> Dict[str, Optional[np.ndarray]]:
     """What `write_ply` wrote, and only that form: {"vertices" f32[V, 3], "faces" i32[T, 3], "rgb" u8[V, 3] | None, "instance" i32[V] | None,
-    "cls" i32[V] | None}."""
+    "cls" i32[V] | None, "normals" f32[V, 3] | None}."""
     with open(path, "rb") as f:
         data = f.read()
     end = data.find(b"end_header\n")
@@ -111,7 +117,7 @@ def read_ply(path) -> Dict[str, Optional[np.ndarray]]:
         props.append(tuple(lines[k].split()[1:]))
         k += 1
     names = [p[1] for p in props]
-    vd = _vertex_dtype("red" in names, "instance" in names, "class" in names)
+    vd = _vertex_dtype("red" in names, "instance" in names, "class" in names, "nx" in names)
     if props != [(_PLY_TYPE[vd[name].str], name) for name in vd.names]:
         raise ValueError(f"read_ply: vertex properties {props} are not of write_ply's form")
     if lines[k + 1:] != ["property list uchar int vertex_indices"] or not lines[k].startswith("element face "):
@@ -127,4 +133,5 @@ def read_ply(path) -> Dict[str, Optional[np.ndarray]]:
             "faces": np.ascontiguousarray(fr["vertex_indices"]),
             "rgb": np.stack([rec["red"], rec["green"], rec["blue"]], 1) if "red" in names else None,
             "instance": np.ascontiguousarray(rec["instance"]) if "instance" in names else None,
-            "cls": np.ascontiguousarray(rec["class"]) if "class" in names else None}
+            "cls": np.ascontiguousarray(rec["class"]) if "class" in names else None,
+            "normals": np.stack([rec["nx"], rec["ny"], rec["nz"]], 1) if "nx" in names else None}

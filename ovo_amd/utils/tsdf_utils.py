@@ -1,7 +1,8 @@
 """A fused geometric model on the GPU: `TsdfVolume`, a dense truncated-signed-distance volume integrated from depth frames (`ovo_tsdf_integrate`)
 ray-cast back into a depth image from any pose (`ovo_tsdf_raycast`) and turned into a triangle mesh (`ovo_tsdf_mesh_plan` / `ovo_tsdf_mesh_emit`):
 csrc/tsdf.hip, csrc/mesh.hip, DESIGN.md sections 17 and 18.  With `color=True` a second array holds the fused colour of every voxel, and the
-same three steps carry it along (`ovo_tsdf_integrate_color`, `ovo_tsdf_raycast_color`, `ovo_tsdf_mesh_colors`: section 20).  `TsdfHistory` keeps the depth images a volume was fused from, and
+same three steps carry it along (`ovo_tsdf_integrate_color`, `ovo_tsdf_raycast_color`, `ovo_tsdf_mesh_colors`: section 20).  The gradient of F is the surface
+normal: `raycast(normals=True)` and `extract_mesh(normals=True)` return it (`ovo_tsdf_raycast_normals`, `ovo_tsdf_mesh_normals`: section 21) and `shade_normals` makes a lit picture of it.  `TsdfHistory` keeps the depth images a volume was fused from, and
 `TsdfVolume.refuse` fuses it again from them at other poses -- what a loop closure needs (section 19).  `frustum_box`, `rigid_inverse_f32` and `volume_desc` / `camera_desc` are pure numpy / ctypes and need no GPU."""
 from __future__ import annotations
 
@@ -161,20 +162,39 @@ class TsdfVolume:
                 self.integrate(history.depths[e["slot"]], K, c2w, near, far)
 
     def raycast(self, K, h: int, w: int, c2w, near: float, far: float, dz: Optional[float] = None, out: Optional[torch.Tensor] = None,
-                color: bool = False, out_rgb: Optional[torch.Tensor] = None):
+                color: bool = False, out_rgb: Optional[torch.Tensor] = None, normals: bool = False, out_normals: Optional[torch.Tensor] = None):
         """The model's depth image f32[h, w] from `c2w` on the current stream (0 = no surface); dz defaults to trunc / 2.  `color=True` (a colour
-        volume only): (depth, rgb u8[h, w, 3]), the colour blended at the hit, (0, 0, 0) where there is none; the depth has the same bits."""
+        volume only): (depth, rgb u8[h, w, 3]), the colour blended at the hit, (0, 0, 0) where there is none; the depth has the same bits.
+        `normals=True` appends the normal image f32[h, w, 3] (`ovo_tsdf_raycast_normals`): the unit gradient of F at the hit, in
+        the volume's frame, pointing into free space, zeros where there is no surface -- (depth, normals) or (depth, rgb, normals), same bits."""
         dz = self.trunc / 2 if dz is None else float(dz)
         if color and self.col is None:
             raise L.OvoHipError("TsdfVolume.raycast: color=True needs a volume made with color=True")
         if out_rgb is not None and not color:
             raise L.OvoHipError("TsdfVolume.raycast: out_rgb is only written with color=True")
+        if out_normals is not None and not normals:
+            raise L.OvoHipError("TsdfVolume.raycast: out_normals is only written with normals=True")
         if out is None:
             out = torch.empty((int(h), int(w)), dtype=torch.float32, device=self.vol.device)
         L.dev(out, torch.float32, "out")
         if tuple(out.shape) != (int(h), int(w)):
             raise L.OvoHipError(f"TsdfVolume.raycast: out must be [{h}, {w}] (got {tuple(out.shape)})")
         cam = camera_desc(K, h, w, c2w, near, far)
+        if normals:
+            if out_normals is None:
+                out_normals = torch.empty((int(h), int(w), 3), dtype=torch.float32, device=self.vol.device)
+            L.dev(out_normals, torch.float32, "out_normals")
+            if tuple(out_normals.shape) != (int(h), int(w), 3):
+                raise L.OvoHipError(f"TsdfVolume.raycast: out_normals must be [{h}, {w}, 3] (got {tuple(out_normals.shape)})")
+            if color:
+                if out_rgb is None:
+                    out_rgb = torch.empty((int(h), int(w), 3), dtype=torch.uint8, device=self.vol.device)
+                L.dev(out_rgb, torch.uint8, "out_rgb")
+                if tuple(out_rgb.shape) != (int(h), int(w), 3):
+                    raise L.OvoHipError(f"TsdfVolume.raycast: out_rgb must be [{h}, {w}, 3] (got {tuple(out_rgb.shape)})")
+            L.check(L.load().ovo_tsdf_raycast_normals(L.ptr(self.vol), L.ptr(self.col) if color else None, C.byref(self.desc), C.byref(cam), dz, L.ptr(out),
+                                                      L.ptr(out_rgb) if color else None, L.ptr(out_normals), L.stream()))
+            return (out, out_rgb, out_normals) if color else (out, out_normals)
         if not color:
             L.check(L.load().ovo_tsdf_raycast(L.ptr(self.vol), C.byref(self.desc), C.byref(cam), dz, L.ptr(out), L.stream()))
             return out
@@ -186,11 +206,13 @@ class TsdfVolume:
         L.check(L.load().ovo_tsdf_raycast_color(L.ptr(self.vol), L.ptr(self.col), C.byref(self.desc), C.byref(cam), dz, L.ptr(out), L.ptr(out_rgb), L.stream()))
         return out, out_rgb
 
-    def extract_mesh(self, box: Optional[Box] = None, min_weight: float = 1.0, colors: bool = False):
+    def extract_mesh(self, box: Optional[Box] = None, min_weight: float = 1.0, colors: bool = False, normals: bool = False):
         """The surface inside the index box (None: the whole volume) as a welded triangle mesh on the device: (vertices f32[V, 3] in the volume's
         frame, faces i32[T, 3]); marching tetrahedra over the cells whose eight corners have W >= min_weight (include/ovo_hip.h states the
         contract).  Normals point into free space.  One host wait, for (V, T); V = 0 returns empty tensors and queues no second call.
-        `colors=True` (a colour volume only): (vertices, faces, rgb u8[V, 3]), each vertex's colour blended between the two ends of its edge."""
+        `colors=True` (a colour volume only): (vertices, faces, rgb u8[V, 3]), each vertex's colour blended between the two ends of its edge.
+        `normals=True` appends vertex normals f32[V, 3] (`ovo_tsdf_mesh_normals`): the unit gradient of F blended between the two
+        ends of the vertex's edge, in the volume's frame; the zero vector where the gradient vanishes.  V = 0: an empty [0, 3] tensor and no call."""
         if colors and self.col is None:
             raise L.OvoHipError("TsdfVolume.extract_mesh: colors=True needs a volume made with color=True")
         box = ((0, 0, 0), self.dims) if box is None else box
@@ -209,13 +231,19 @@ class TsdfVolume:
         if V > 0:
             L.check(lib.ovo_tsdf_mesh_emit(L.ptr(self.vol), C.byref(self.desc), lo, hi, float(min_weight), L.ptr(ws), nbytes, L.ptr(vertices), L.ptr(faces),
                                            V, T, L.stream()))
-        if not colors:
-            return vertices, faces
-        rgb = torch.empty((V, 3), dtype=torch.uint8, device=dev)
-        if V > 0:
-            L.check(lib.ovo_tsdf_mesh_colors(L.ptr(self.vol), L.ptr(self.col), C.byref(self.desc), lo, hi, float(min_weight), L.ptr(ws), nbytes, L.ptr(rgb), V,
-                                             L.stream()))
-        return vertices, faces, rgb
+        result = (vertices, faces)
+        if colors:
+            rgb = torch.empty((V, 3), dtype=torch.uint8, device=dev)
+            if V > 0:
+                L.check(lib.ovo_tsdf_mesh_colors(L.ptr(self.vol), L.ptr(self.col), C.byref(self.desc), lo, hi, float(min_weight), L.ptr(ws), nbytes, L.ptr(rgb), V,
+                                                 L.stream()))
+            result += (rgb,)
+        if normals:
+            nrm = torch.empty((V, 3), dtype=torch.float32, device=dev)
+            if V > 0:
+                L.check(lib.ovo_tsdf_mesh_normals(L.ptr(self.vol), C.byref(self.desc), lo, hi, float(min_weight), L.ptr(ws), nbytes, L.ptr(nrm), V, L.stream()))
+            result += (nrm,)
+        return result
 
 
 class TsdfHistory:
@@ -262,6 +290,32 @@ class TsdfHistory:
     def poses(self, X) -> list:
         """The live entries' poses under the keyframe poses X (f64, by keyframe index): X[kf] @ rel in f64, rounded to f32 once."""
         return [(np.asarray(X[e["kf"]], dtype=np.float64) @ e["rel"]).astype(np.float32) for e in self._entries]
+
+
+def shade_normals(normals: torch.Tensor, K, c2w, rgb: Optional[torch.Tensor] = None, ambient: float = 0.2) -> torch.Tensor:
+    """A head-light Lambert picture u8[h, w, 3] of a normal image f32[h, w, 3] (`TsdfVolume.raycast(normals=True)`, `IcpTracker.render_model(normals=True)`)
+    seen from `c2w` with intrinsics K: with d the unit ray of the pixel in the normals' frame, i = ambient + (1 - ambient) * clamp(-n . d, 0, 1); the
+    picture is rint(255 i) in all three channels, or rint(i * rgb) with `rgb` u8[h, w, 3]; a pixel whose normal is the zero vector is (0, 0, 0).
+    Plain torch on the normals' device, f32: a viewer's step, not a hot path."""
+    if normals.dim() != 3 or normals.shape[2] != 3 or normals.dtype != torch.float32:
+        raise ValueError(f"shade_normals: normals must be f32 [h, w, 3] (got {normals.dtype} {tuple(normals.shape)})")
+    if rgb is not None and (tuple(rgb.shape) != tuple(normals.shape) or rgb.dtype != torch.uint8):
+        raise ValueError(f"shade_normals: rgb must be u8 {list(normals.shape)} (got {rgb.dtype} {tuple(rgb.shape)})")
+    if not 0.0 <= float(ambient) <= 1.0:
+        raise ValueError("shade_normals: ambient must lie in [0, 1]")
+    h, w = int(normals.shape[0]), int(normals.shape[1])
+    dev = normals.device
+    K, pose = _np(K, np.float32), _np(c2w, np.float32)
+    u = (torch.arange(w, dtype=torch.float32, device=dev) - float(K[0, 2])) / float(K[0, 0])
+    v = (torch.arange(h, dtype=torch.float32, device=dev) - float(K[1, 2])) / float(K[1, 1])
+    dc = torch.stack([u[None, :].expand(h, w), v[:, None].expand(h, w), torch.ones((h, w), dtype=torch.float32, device=dev)], -1)
+    d = dc @ torch.from_numpy(np.ascontiguousarray(pose[:3, :3])).to(dev).T
+    d = d / d.norm(dim=-1, keepdim=True)
+    i = float(ambient) + (1.0 - float(ambient)) * (-(normals * d).sum(-1)).clamp(0.0, 1.0)
+    base = torch.full((h, w, 3), 255.0, dtype=torch.float32, device=dev) if rgb is None else rgb.to(torch.float32)
+    out = torch.round(i[..., None] * base).clamp(0.0, 255.0)
+    lit = (normals != 0).any(-1, keepdim=True)
+    return torch.where(lit, out, torch.zeros_like(out)).to(torch.uint8)
 
 
 def march_steps(near: float, far: float, dz: float) -> int:
