@@ -358,7 +358,9 @@ typedef struct {
     int64_t q_sb, q_sh, q_st, k_sb, k_sh, k_st, v_sb, v_sh, v_st, o_sb, o_sh, o_st;
     int32_t B, H, Tq, Tk, hd;
     float scale;
-    int32_t causal;                                   /* 1: key j is visible to query i only if j <= i (text towers); ABI v2 */
+    int32_t causal;                                   /* 1: key j is visible to query i only if j <= i (text towers); ABI v2.  i and j are the
+                                                       * absolute row indices of q and k, also where Tq != Tk: with Tq > Tk the queries
+                                                       * i >= Tk see every key, with Tq < Tk the keys j >= Tq are visible to no query */
 } ovo_attention_t;
 int ovo_attention(const ovo_attention_t *a, ovo_stream_t stream);
 

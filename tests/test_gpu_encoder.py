@@ -453,10 +453,12 @@ def test_attention_rescale_path(B, H, Tq, Tk, hd):
     assert (out.float() - ref).abs().mean() < 3e-3
 
 
-def _attention_call(qkv, B, H, Tq, Tk, hd, causal=0):
+def _attention_call(qkv, B, H, Tq, Tk, hd, causal=0, scale=None, out=None):
+    """ovo_attention on a packed qkv; scale None: hd ** -0.5; out None: a fresh [B, Tq, H hd] (else any bf16 tensor of that many elements)."""
     from ovo_amd import _lib as L
-    out = torch.zeros(B, Tq, H * hd, dtype=torch.bfloat16, device=DEV)
-    a = L.attention_packed(qkv, out, B, H, Tq, Tk, hd, scale=hd ** -0.5, causal=causal)
+    if out is None:
+        out = torch.zeros(B, Tq, H * hd, dtype=torch.bfloat16, device=DEV)
+    a = L.attention_packed(qkv, out, B, H, Tq, Tk, hd, scale=hd ** -0.5 if scale is None else scale, causal=causal)
     L.check(L.load().ovo_attention(C.byref(a), L.stream()))
     torch.cuda.synchronize()
     return out
