@@ -11,18 +11,19 @@
 //   ovo_tsdf_mesh_emit   k_mesh_emit       a wave per 64 voxels of an x-row: a voxel writes the vertices of its used slots, a cell its triangles --
 //                                          the table (mesh_table.h) names each vertex as (owner corner, slot), its index is the owner's row base
 //                                          + in-row offset + the number of lower slots in use
-//   ovo_tsdf_mesh_colors k_mesh_colors      the vertex half of k_mesh_emit over the same units: a voxel blends its own colour and
-//                                          that of each used slot's other end with emit's t, one u8 triple a vertex
+//   ovo_tsdf_mesh_colors k_mesh_colors      the vertex half of k_mesh_emit over the same units (mesh_vertices: one walk, one t for
+//                                          all three kernels): a voxel blends its own colour and that of each used slot's other end, one u8 triple a vertex
 //   ovo_tsdf_mesh_normals k_mesh_normals    the same walk: a voxel takes the gradient of F (tsdf_gradient.h) at itself and at each used
-//                                          slot's other end, blends the two with emit's t and normalises, one f32 triple a vertex
+//                                          slot's other end, blends the two and normalises, one f32 triple a vertex
 // A word: bits 0-6 the used slots, bits 8-22 the in-row vertex offset (<= 7 * 4095).  B word: bits 0-15 the in-row triangle offset (<= 12 * 4095),
 // bits 16-19 the cell's triangle count, bits 20-27 its corner mask (corner x + 2 y + 4 z inside).
 // The only atomic is the OR into A, whose result does not depend on order: plan and emit are pure functions of their inputs, bit-equal from run to
 // run and whatever OVO_MESH_GRID_CAP says.  Every index is in range by construction: the box is checked against the volume on the host; a thread
-// loads row j + 1 / k + 1 / column i + 1 only where the box has it; a slot is flagged only by a cell that holds both of its ends; emit bounds every
-// store by the V and T it was given, which the host has compared with the plan's.  k_mesh_colors forms every colour address from the index its F
-// address is formed from, and bounds every store by V likewise.  k_mesh_normals reads the neighbours of both ends in the whole VOLUME, not the box: each
-// neighbour's address is formed from the index that has passed the test against [0, n) (tsdf_gradient), and every store is bounded by V.
+// loads row j + 1 / k + 1 / column i + 1 only where the box has it; a slot is flagged only by a cell that holds both of its ends; mesh_vertices hands
+// out a vertex index only below the V it was given and emit bounds every face store by T, both of which the host has compared with the plan's
+// (mesh_planned).  k_mesh_colors forms every colour address from the index and offset the walk forms the F addresses from.  k_mesh_normals reads the
+// neighbours of both ends in the whole VOLUME, not the box: each neighbour's address is formed from the index that has passed the test against [0, n)
+// (tsdf_gradient).
 // This file is compiled with -ffp-contract=off: the vertex is t = Fp / (Fp - Fq), g = p + t * d, pos = origin + voxel * g, one rounding each.
 #include <string.h>
 
@@ -38,7 +39,12 @@ constexpr size_t MESH_HEAD_BYTES = 256;                    // int64 V, T, key0, 
 constexpr int MESH_SLOT[7] = {1, 2, 4, 3, 5, 6, 7};        // slot -> the offset to the edge's other end, as corner bits x + 2 y + 4 z
 
 struct MeshBox { int x0, y0, z0, bx, by, bz; };
-struct MeshLayout { MeshBox b; int64_t nvox; uint32_t nrows; size_t off_rows, off_a, off_b, bytes; };
+struct MeshLayout {                                        // of a workspace: the head, then `rows`, A and B; units: see mesh_unit
+    MeshBox b; int64_t nvox, units; uint32_t nrows; size_t off_rows, off_a, off_b, bytes;
+    uint2 *rows(const void *ws) const { return (uint2 *)((char *)ws + off_rows); }
+    uint32_t *A(const void *ws) const { return (uint32_t *)((char *)ws + off_a); }
+    uint32_t *B(const void *ws) const { return (uint32_t *)((char *)ws + off_b); }
+};
 
 __device__ __forceinline__ uint32_t scan64(uint32_t x, int lane) {      // inclusive, over the wave
 #pragma unroll
@@ -201,40 +207,81 @@ __device__ __forceinline__ uint32_t pick8(const Oct &x, uint32_t c) {
     return c & 4 ? hi : lo;
 }
 
+// The vertices the voxel of unit m owns (a: its A word with some slot in use, row_base: the number of vertices before its row), in the emit order: for
+// every used slot, the other end q = p + d of the edge and t = Fp / (Fp - Fq) -- computed HERE and nowhere else: a vertex's position, colour and
+// normal are blended with the same bits.  Both ends are OBSERVED because a slot is flagged only by a valid cell.  `per` is told the voxel once
+// (per.voxel: its indices, its offset `idx` in the volume, Fp) and then every vertex whose index is below V (per.vertex: the index, the constant d as
+// corner bits x + 2 y + 4 z, q's offset from p in the volume, Fq, t), so whatever it stores at the vertex index is bounded by V.
+template <class Per>
+__device__ __forceinline__ void mesh_vertices(const float2 *__restrict__ vol, const TsdfVol &v, const MeshBox &b, const MeshUnit &m, uint32_t a, uint32_t row_base,
+                                              int64_t V, Per per) {
+    const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
+    const int pi = b.x0 + m.i, pj = b.y0 + (int)m.jj, pk = b.z0 + (int)m.kk;
+    const int64_t idx = (int64_t)pk * sz + (int64_t)pj * sy + pi;
+    const float2 *p = vol + idx;
+    const float Fp = p->x;
+    per.voxel(pi, pj, pk, idx, Fp);
+    int64_t vi = (int64_t)row_base + (a >> 8);
+#pragma unroll
+    for (int s = 0; s < 7; ++s) {
+        if (!(a >> s & 1)) continue;
+        const int d = MESH_SLOT[s];
+        const int64_t off = (d & 1) + (d >> 1 & 1) * sy + (d >> 2) * sz;
+        const float Fq = p[off].x;
+        const float t = Fp / (Fp - Fq);
+        if (vi < V) per.vertex(vi, d, off, Fq, t);
+        ++vi;
+    }
+}
+
+struct MeshPosition {                                      // k_mesh_emit: g = p + t * d, pos = origin + voxel * g
+    const TsdfVol &v; float *__restrict__ verts; float pf[3];
+    __device__ __forceinline__ void voxel(int pi, int pj, int pk, int64_t, float) { pf[0] = (float)pi; pf[1] = (float)pj; pf[2] = (float)pk; }
+    __device__ __forceinline__ void vertex(int64_t vi, int d, int64_t, float, float t) const {
+        const float org[3] = {v.ox, v.oy, v.oz};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float g = pf[c] + t * (float)(d >> c & 1);
+            verts[vi * 3 + c] = org[c] + v.voxel * g;
+        }
+    }
+};
+
+struct MeshColor {                                         // k_mesh_colors: lerp1 of the two ends' (float) q per channel; `idx` and `off` serve both arrays
+    const uint2 *__restrict__ col; uint8_t *__restrict__ rgb; const uint2 *pc; uint2 cp;
+    __device__ __forceinline__ void voxel(int, int, int, int64_t idx, float) { pc = col + idx; cp = *pc; }
+    __device__ __forceinline__ void vertex(int64_t vi, int, int64_t off, float, float t) const {
+        const uint2 cq = pc[off];
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) rgb[vi * 3 + ch] = color_level(lerp1(color_channel(cp, ch), color_channel(cq, ch), t));
+    }
+};
+
+struct MeshNormal {                                        // k_mesh_normals: unit(lerp1(grad(p), grad(q), t)) per component; the neighbours that count are OBSERVED
+    const float2 *__restrict__ vol; const TsdfVol &v; TsdfObserved obs; float *__restrict__ normals; int pi, pj, pk; float gp[3];
+    __device__ __forceinline__ void voxel(int i, int j, int k, int64_t, float Fp) { pi = i; pj = j; pk = k; tsdf_gradient(vol, v, i, j, k, Fp, obs, gp); }
+    __device__ __forceinline__ void vertex(int64_t vi, int d, int64_t, float Fq, float t) const {
+        float gq[3], g[3], nrm[3];
+        tsdf_gradient(vol, v, pi + (d & 1), pj + (d >> 1 & 1), pk + (d >> 2), Fq, obs, gq);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) g[c] = lerp1(gp[c], gq[c], t);
+        tsdf_unit(g, nrm);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) normals[vi * 3 + c] = nrm[c];
+    }
+};
+
 __global__ void __launch_bounds__(256) k_mesh_emit(const float2 *__restrict__ vol, const TsdfVol v, const MeshBox b, const uint32_t *__restrict__ A,
                                                    const uint32_t *__restrict__ B, const uint2 *__restrict__ rows, float *__restrict__ verts,
                                                    int32_t *__restrict__ faces, int64_t V, int64_t T) {
     const int lane = threadIdx.x & 63;
     const uint32_t chunks = (uint32_t)(b.bx + 63) >> 6;
     const uint64_t units = (uint64_t)((uint32_t)b.by * (uint32_t)b.bz) * chunks;
-    const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
-    const float org[3] = {v.ox, v.oy, v.oz};
     for (uint64_t u = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < units; u += (uint64_t)gridDim.x * 4) {
         const MeshUnit m = mesh_unit(u, chunks, b, lane);
         const uint32_t a = m.live ? A[m.lin] : 0, w = m.live ? B[m.lin] : 0;
         const uint2 base = rows[m.row];
-        // ---- the vertices this voxel owns
-        if (a & 127) {
-            const float2 *p = vol + (int64_t)(b.z0 + (int)m.kk) * sz + (int64_t)(b.y0 + (int)m.jj) * sy + (b.x0 + m.i);
-            const float Fp = p->x;
-            const float pf[3] = {(float)(b.x0 + m.i), (float)(b.y0 + (int)m.jj), (float)(b.z0 + (int)m.kk)};
-            int64_t vi = (int64_t)base.x + (a >> 8);
-#pragma unroll
-            for (int s = 0; s < 7; ++s) {
-                if (!(a >> s & 1)) continue;
-                const int d = MESH_SLOT[s];
-                const float Fq = p[(d & 1) + (d >> 1 & 1) * sy + (d >> 2) * sz].x;
-                const float t = Fp / (Fp - Fq);
-                if (vi < V) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const float g = pf[c] + t * (float)(d >> c & 1);
-                        verts[vi * 3 + c] = org[c] + v.voxel * g;
-                    }
-                }
-                ++vi;
-            }
-        }
+        if (a & 127) mesh_vertices(vol, v, b, m, a, base.x, V, MeshPosition{v, verts});
         // ---- the triangles of this cell
         const uint32_t ntri = w >> 16 & 15;
         if (!__any(ntri != 0)) continue;                     // wave-uniform: most of a volume is far from the surface
@@ -279,78 +326,28 @@ __global__ void __launch_bounds__(256) k_mesh_emit(const float2 *__restrict__ vo
     }
 }
 
-// The colour of vertex n of the emit order: lerp1 of the two ends' (float) q per channel with t = Fp / (Fp - Fq), emit's own bits; both ends are observed
-// because a slot is flagged only by a valid cell.
-__global__ void __launch_bounds__(256) k_mesh_colors(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v, const MeshBox b,
-                                                     const uint32_t *__restrict__ A, const uint2 *__restrict__ rows, uint8_t *__restrict__ rgb, int64_t V) {
+// The vertex half of k_mesh_emit alone, over the same units: what `per` makes of vertex n of the emit order.
+template <class Per>
+__device__ __forceinline__ void mesh_vertex_pass(const float2 *__restrict__ vol, const TsdfVol &v, const MeshBox &b, const uint32_t *__restrict__ A,
+                                                 const uint2 *__restrict__ rows, int64_t V, const Per &per) {
     const int lane = threadIdx.x & 63;
     const uint32_t chunks = (uint32_t)(b.bx + 63) >> 6;
     const uint64_t units = (uint64_t)((uint32_t)b.by * (uint32_t)b.bz) * chunks;
-    const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
     for (uint64_t u = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < units; u += (uint64_t)gridDim.x * 4) {
         const MeshUnit m = mesh_unit(u, chunks, b, lane);
         const uint32_t a = m.live ? A[m.lin] : 0;
-        if (!(a & 127)) continue;
-        const int64_t idx = (int64_t)(b.z0 + (int)m.kk) * sz + (int64_t)(b.y0 + (int)m.jj) * sy + (b.x0 + m.i);
-        const float2 *p = vol + idx;
-        const uint2 *pc = col + idx;
-        const float Fp = p->x;
-        const uint2 cp = *pc;
-        int64_t vi = (int64_t)rows[m.row].x + (a >> 8);
-#pragma unroll
-        for (int s = 0; s < 7; ++s) {
-            if (!(a >> s & 1)) continue;
-            const int d = MESH_SLOT[s];
-            const int64_t off = (d & 1) + (d >> 1 & 1) * sy + (d >> 2) * sz;
-            const float Fq = p[off].x;
-            const uint2 cq = pc[off];
-            const float t = Fp / (Fp - Fq);
-            if (vi < V) {
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) rgb[vi * 3 + ch] = color_level(lerp1(color_channel(cp, ch), color_channel(cq, ch), t));
-            }
-            ++vi;
-        }
+        if (a & 127) mesh_vertices(vol, v, b, m, a, rows[m.row].x, V, per);
     }
 }
 
-// The normal of vertex n of the emit order: unit(lerp1(grad(p), grad(q), t)) per component with t = Fp / (Fp - Fq), emit's own bits; both ends are
-// OBSERVED because a slot is flagged only by a valid cell, and so are the neighbours that count.
+__global__ void __launch_bounds__(256) k_mesh_colors(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v, const MeshBox b,
+                                                     const uint32_t *__restrict__ A, const uint2 *__restrict__ rows, uint8_t *__restrict__ rgb, int64_t V) {
+    mesh_vertex_pass(vol, v, b, A, rows, V, MeshColor{col, rgb});
+}
+
 __global__ void __launch_bounds__(256) k_mesh_normals(const float2 *__restrict__ vol, const TsdfVol v, const MeshBox b, float min_weight,
                                                       const uint32_t *__restrict__ A, const uint2 *__restrict__ rows, float *__restrict__ normals, int64_t V) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t chunks = (uint32_t)(b.bx + 63) >> 6;
-    const uint64_t units = (uint64_t)((uint32_t)b.by * (uint32_t)b.bz) * chunks;
-    const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
-    const TsdfObserved obs{min_weight};
-    for (uint64_t u = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); u < units; u += (uint64_t)gridDim.x * 4) {
-        const MeshUnit m = mesh_unit(u, chunks, b, lane);
-        const uint32_t a = m.live ? A[m.lin] : 0;
-        if (!(a & 127)) continue;
-        const int pi = b.x0 + m.i, pj = b.y0 + (int)m.jj, pk = b.z0 + (int)m.kk;
-        const float2 *p = vol + (int64_t)pk * sz + (int64_t)pj * sy + pi;
-        const float Fp = p->x;
-        float gp[3];
-        tsdf_gradient(vol, v, pi, pj, pk, Fp, obs, gp);
-        int64_t vi = (int64_t)rows[m.row].x + (a >> 8);
-#pragma unroll
-        for (int s = 0; s < 7; ++s) {
-            if (!(a >> s & 1)) continue;
-            const int d = MESH_SLOT[s];
-            const float Fq = p[(d & 1) + (d >> 1 & 1) * sy + (d >> 2) * sz].x;
-            const float t = Fp / (Fp - Fq);
-            if (vi < V) {
-                float gq[3], g[3], nrm[3];
-                tsdf_gradient(vol, v, pi + (d & 1), pj + (d >> 1 & 1), pk + (d >> 2), Fq, obs, gq);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) g[c] = lerp1(gp[c], gq[c], t);
-                tsdf_unit(g, nrm);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) normals[vi * 3 + c] = nrm[c];
-            }
-            ++vi;
-        }
-    }
+    mesh_vertex_pass(vol, v, b, A, rows, V, MeshNormal{vol, v, TsdfObserved{min_weight}, normals});
 }
 
 // ---- host
@@ -364,6 +361,7 @@ const char *mesh_layout(const ovo_tsdf_volume_t *desc, const int32_t *lo, const 
     l.b = MeshBox{lo[0], lo[1], lo[2], hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
     l.nvox = (int64_t)l.b.bx * l.b.by * l.b.bz;
     l.nrows = (uint32_t)l.b.by * (uint32_t)l.b.bz;
+    l.units = (int64_t)l.nrows * ((l.b.bx + 63) / 64);
     const auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     l.off_rows = MESH_HEAD_BYTES;
     l.off_a = l.off_rows + up((size_t)l.nrows * sizeof(uint2));
@@ -398,6 +396,25 @@ const char *mesh_common_check(const void *vol, const ovo_tsdf_volume_t *desc, co
     return nullptr;
 }
 
+// What emit, colours and normals ask beyond mesh_common_check: that the workspace holds a plan, made for this volume shape, box and min_weight, with
+// this V (and T, where one is given).  The plan's head, 32 bytes, is read back from the workspace, which waits for the stream (the caller has waited
+// for `counts` already: it could not have sized the outputs otherwise).  Returns the read-back's HIP status; `wrong`: what the entry point reports.
+hipError_t mesh_planned(const void *vol, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight, const void *ws, size_t ws_bytes,
+                        int64_t V, const int64_t *T, hipStream_t s, MeshLayout &l, const char *&wrong) {
+    wrong = mesh_common_check(vol, desc, lo, hi, min_weight, ws, ws_bytes, l);
+    if (wrong) return hipSuccess;
+    wrong = T ? "V and T must be 0 .. 2^31 - 1" : "V must be 0 .. 2^31 - 1";
+    if (!(V >= 0 && V <= MESH_MAX_COUNT && (!T || (*T >= 0 && *T <= MESH_MAX_COUNT)))) return hipSuccess;
+    int64_t head[4] = {0, 0, 0, 0}, key[2];
+    mesh_key(desc, l.b, min_weight, key);
+    hipError_t e = hipMemcpyAsync(head, ws, sizeof(head), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (head[2] != key[0] || head[3] != key[1]) wrong = "the workspace holds no plan for this volume shape, box and min_weight";
+    else if (head[0] != V || (T && head[1] != *T)) wrong = T ? "V, T differ from the plan in the workspace" : "V differs from the plan in the workspace";
+    else wrong = nullptr;
+    return e;
+}
+
 int mesh_grid(int64_t units) {
     const int cap = ovo_knob_int("OVO_MESH_GRID_CAP", 256 * 16);      // (tests: 2, so that every workgroup loops)
     return ovo_grid(units * 64, 256, cap > 0 ? cap : 256 * 16);
@@ -418,94 +435,60 @@ extern "C" int ovo_tsdf_mesh_plan(const void *vol, const ovo_tsdf_volume_t *desc
     const char *wrong = mesh_common_check(vol, desc, lo, hi, min_weight, ws, ws_bytes, l);
     OVO_REQUIRE(!wrong, wrong);
     OVO_REQUIRE(((uintptr_t)counts & 7) == 0, "counts not 8-byte aligned");
-    char *base = (char *)ws;
-    uint2 *rows = (uint2 *)(base + l.off_rows);
-    uint32_t *A = (uint32_t *)(base + l.off_a), *B = (uint32_t *)(base + l.off_b);
     int64_t key[2];
     mesh_key(desc, l.b, min_weight, key);
     const hipStream_t s = (hipStream_t)stream;
-    OVO_HIP(hipMemsetAsync(A, 0, (size_t)l.nvox * 4, s));
-    const int64_t units = (int64_t)l.nrows * ((l.b.bx + 63) / 64);
-    k_mesh_classify<<<mesh_grid(units), 256, 0, s>>>((const float2 *)vol, tsdf_vol(*desc), l.b, min_weight, A, B);
+    OVO_HIP(hipMemsetAsync(l.A(ws), 0, (size_t)l.nvox * 4, s));
+    k_mesh_classify<<<mesh_grid(l.units), 256, 0, s>>>((const float2 *)vol, tsdf_vol(*desc), l.b, min_weight, l.A(ws), l.B(ws));
     OVO_CHECK_LAUNCH();
-    k_mesh_rowscan<<<mesh_grid(l.nrows), 256, 0, s>>>(A, B, l.b, l.nrows, rows);
+    k_mesh_rowscan<<<mesh_grid(l.nrows), 256, 0, s>>>(l.A(ws), l.B(ws), l.b, l.nrows, l.rows(ws));
     OVO_CHECK_LAUNCH();
-    k_mesh_rowbase<<<1, 1024, 0, s>>>(rows, l.nrows, (int64_t *)base, counts, key[0], key[1]);
+    k_mesh_rowbase<<<1, 1024, 0, s>>>(l.rows(ws), l.nrows, (int64_t *)ws, counts, key[0], key[1]);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }
 
+// The three calls below: everything is checked before anything is queued -- the plan's head included (mesh_planned).
 extern "C" int ovo_tsdf_mesh_emit(const void *vol, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight, const void *ws,
                                   size_t ws_bytes, float *vertices, int32_t *faces, int64_t V, int64_t T, ovo_stream_t stream) {
-    // everything is checked HERE, before anything is queued -- the plan's head included: 32 bytes are read back from the workspace, which waits
-    // for the stream (the caller has waited for `counts` already: it could not have sized the outputs otherwise)
     MeshLayout l;
-    OVO_REQUIRE(vertices && faces, "null pointer");
-    const char *wrong = mesh_common_check(vol, desc, lo, hi, min_weight, ws, ws_bytes, l);
-    OVO_REQUIRE(!wrong, wrong);
-    OVO_REQUIRE(((uintptr_t)vertices & 3) == 0 && ((uintptr_t)faces & 3) == 0, "vertices or faces not 4-byte aligned");
-    OVO_REQUIRE(V >= 0 && V <= MESH_MAX_COUNT && T >= 0 && T <= MESH_MAX_COUNT, "V and T must be 0 .. 2^31 - 1");
+    const char *wrong;
     const hipStream_t s = (hipStream_t)stream;
-    int64_t head[4] = {0, 0, 0, 0}, key[2];
-    mesh_key(desc, l.b, min_weight, key);
-    OVO_HIP(hipMemcpyAsync(head, ws, sizeof(head), hipMemcpyDeviceToHost, s));
-    OVO_HIP(hipStreamSynchronize(s));
-    OVO_REQUIRE(head[2] == key[0] && head[3] == key[1], "the workspace holds no plan for this volume shape, box and min_weight");
-    OVO_REQUIRE(head[0] == V && head[1] == T, "V, T differ from the plan in the workspace");
-    const char *base = (const char *)ws;
-    const int64_t units = (int64_t)l.nrows * ((l.b.bx + 63) / 64);
-    k_mesh_emit<<<mesh_grid(units), 256, 0, s>>>((const float2 *)vol, tsdf_vol(*desc), l.b, (const uint32_t *)(base + l.off_a),
-                                                    (const uint32_t *)(base + l.off_b), (const uint2 *)(base + l.off_rows), vertices, faces, V, T);
+    OVO_REQUIRE(vertices && faces, "null pointer");
+    OVO_REQUIRE(((uintptr_t)vertices & 3) == 0 && ((uintptr_t)faces & 3) == 0, "vertices or faces not 4-byte aligned");
+    OVO_HIP(mesh_planned(vol, desc, lo, hi, min_weight, ws, ws_bytes, V, &T, s, l, wrong));
+    OVO_REQUIRE(!wrong, wrong);
+    k_mesh_emit<<<mesh_grid(l.units), 256, 0, s>>>((const float2 *)vol, tsdf_vol(*desc), l.b, l.A(ws), l.B(ws), l.rows(ws), vertices, faces, V, T);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }
 
 extern "C" int ovo_tsdf_mesh_colors(const void *vol, const void *col, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight,
                                     const void *ws, size_t ws_bytes, uint8_t *rgb_out, int64_t V, ovo_stream_t stream) {
-    // everything is checked HERE, before anything is queued -- the plan's head included, as ovo_tsdf_mesh_emit reads it
     MeshLayout l;
-    OVO_REQUIRE(col && rgb_out, "null pointer");
-    const char *wrong = mesh_common_check(vol, desc, lo, hi, min_weight, ws, ws_bytes, l);
-    OVO_REQUIRE(!wrong, wrong);
-    OVO_REQUIRE(((uintptr_t)col & 15) == 0, "colour volume not 16-byte aligned");
-    OVO_REQUIRE(V >= 0 && V <= MESH_MAX_COUNT, "V must be 0 .. 2^31 - 1");
+    const char *wrong;
     const hipStream_t s = (hipStream_t)stream;
-    int64_t head[4] = {0, 0, 0, 0}, key[2];
-    mesh_key(desc, l.b, min_weight, key);
-    OVO_HIP(hipMemcpyAsync(head, ws, sizeof(head), hipMemcpyDeviceToHost, s));
-    OVO_HIP(hipStreamSynchronize(s));
-    OVO_REQUIRE(head[2] == key[0] && head[3] == key[1], "the workspace holds no plan for this volume shape, box and min_weight");
-    OVO_REQUIRE(head[0] == V, "V differs from the plan in the workspace");
+    OVO_REQUIRE(col && rgb_out, "null pointer");
+    OVO_REQUIRE(((uintptr_t)col & 15) == 0, "colour volume not 16-byte aligned");
+    OVO_HIP(mesh_planned(vol, desc, lo, hi, min_weight, ws, ws_bytes, V, nullptr, s, l, wrong));
+    OVO_REQUIRE(!wrong, wrong);
     if (V == 0) return OVO_OK;                               // a plan without vertices: nothing to queue
-    const char *base = (const char *)ws;
-    const int64_t units = (int64_t)l.nrows * ((l.b.bx + 63) / 64);
-    k_mesh_colors<<<mesh_grid(units), 256, 0, s>>>((const float2 *)vol, (const uint2 *)col, tsdf_vol(*desc), l.b, (const uint32_t *)(base + l.off_a),
-                                                      (const uint2 *)(base + l.off_rows), rgb_out, V);
+    k_mesh_colors<<<mesh_grid(l.units), 256, 0, s>>>((const float2 *)vol, (const uint2 *)col, tsdf_vol(*desc), l.b, l.A(ws), l.rows(ws), rgb_out, V);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }
 
 extern "C" int ovo_tsdf_mesh_normals(const void *vol, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight, const void *ws,
                                      size_t ws_bytes, float *normals_out, int64_t V, ovo_stream_t stream) {
-    // everything is checked HERE, before anything is queued -- the plan's head included, as ovo_tsdf_mesh_emit reads it
     MeshLayout l;
-    OVO_REQUIRE(normals_out, "null pointer");
-    const char *wrong = mesh_common_check(vol, desc, lo, hi, min_weight, ws, ws_bytes, l);
-    OVO_REQUIRE(!wrong, wrong);
-    OVO_REQUIRE(((uintptr_t)normals_out & 3) == 0, "normals_out not 4-byte aligned");
-    OVO_REQUIRE(V >= 0 && V <= MESH_MAX_COUNT, "V must be 0 .. 2^31 - 1");
+    const char *wrong;
     const hipStream_t s = (hipStream_t)stream;
-    int64_t head[4] = {0, 0, 0, 0}, key[2];
-    mesh_key(desc, l.b, min_weight, key);
-    OVO_HIP(hipMemcpyAsync(head, ws, sizeof(head), hipMemcpyDeviceToHost, s));
-    OVO_HIP(hipStreamSynchronize(s));
-    OVO_REQUIRE(head[2] == key[0] && head[3] == key[1], "the workspace holds no plan for this volume shape, box and min_weight");
-    OVO_REQUIRE(head[0] == V, "V differs from the plan in the workspace");
+    OVO_REQUIRE(normals_out, "null pointer");
+    OVO_REQUIRE(((uintptr_t)normals_out & 3) == 0, "normals_out not 4-byte aligned");
+    OVO_HIP(mesh_planned(vol, desc, lo, hi, min_weight, ws, ws_bytes, V, nullptr, s, l, wrong));
+    OVO_REQUIRE(!wrong, wrong);
     if (V == 0) return OVO_OK;                               // a plan without vertices: nothing to queue
-    const char *base = (const char *)ws;
-    const int64_t units = (int64_t)l.nrows * ((l.b.bx + 63) / 64);
-    k_mesh_normals<<<mesh_grid(units), 256, 0, s>>>((const float2 *)vol, tsdf_vol(*desc), l.b, min_weight, (const uint32_t *)(base + l.off_a),
-                                                       (const uint2 *)(base + l.off_rows), normals_out, V);
+    k_mesh_normals<<<mesh_grid(l.units), 256, 0, s>>>((const float2 *)vol, tsdf_vol(*desc), l.b, min_weight, l.A(ws), l.rows(ws), normals_out, V);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }

@@ -1,24 +1,22 @@
 // tsdf.hip -- a fused geometric model: a dense truncated-signed-distance volume integrated from depth frames, and the ray caster that turns it back
 // into a depth image from any pose.  IcpTracker(model="tsdf") aligns every frame to that image instead of the keyframe's.
-//   ovo_tsdf_integrate   k_tsdf_integrate<V>   one launch over the index box [lo, hi): one thread owns a voxel (V = 1, 8 bytes) or two x-neighbours
-//                                              (V = 2, 16 bytes, volumes with an even nx: every pair is 16-byte aligned), lanes along x
-//   ovo_tsdf_raycast     k_tsdf_raycast        one launch, one thread per pixel, 16 x 16 pixel tiles: a fixed-step march, trilinear samples
-//   ovo_tsdf_integrate_color   k_tsdf_integrate_color<V>   the same launch with a colour volume beside the first: a voxel's colour
-//                                              is updated exactly when its (F, W) is, from the pixel the depth was read at
-//   ovo_tsdf_raycast_color     k_tsdf_raycast_color        the same march; at a hit, 16 eight-byte colour loads and three blends per channel
-//   ovo_tsdf_raycast_normals   k_tsdf_raycast_normals / k_tsdf_raycast_color_normals   the same march; at a hit, the gradient of F
-//                                              (tsdf_gradient.h) at the eight corners of the two bracketing samples, blended as F is, normalised
-// The volume is float2 [nz][ny][nx] = (F, W), x fastest; all-zero bytes are "unobserved".  No atomics, no cross-thread traffic: both results are pure
-// functions of their inputs, bit-equal from run to run and whatever OVO_TSDF_GRID_CAP says (it only changes which workgroup visits a voxel).
-// Every volume index is in range by construction: integrate's box is checked against the volume on the host, the ray caster tests a sample's base
-// cell against [0, n - 2] on all three axes BEFORE it forms an address, and issues no load for a sample that fails.
-// The colour volume is uint2 [nz][ny][nx] (four u16: R, G, B, spare) with the volume's indexing.  Every `col` address is formed from the index the `vol`
-// address is formed from: integrate adds one `idx` to both bases; the ray caster reads colour only at a hit, at the base cells of the samples k - 1 and
-// k, both of which passed the march's range test -- the march keeps no index alive from sample to sample, so both are formed again by the march's own
-// expressions (the same IEEE operations on the same values) and clamped to [0, n - 2], which changes nothing.  Every `rgb` address is formed from the (v, u) that
-// tsdf_sample has tested against the image; rgb_out is written at the pixel depth_out is.
-// A normal is read only at a hit too, around the same two base cells, formed again and clamped the same way; a corner's neighbour is addressed only after
-// its index has passed the test against [0, n) (tsdf_gradient), and normals_out is written at the pixel depth_out is.
+//   ovo_tsdf_integrate[_color]   k_tsdf_integrate<V, COLOR>   one launch over the index box [lo, hi): one thread owns a voxel (V = 1, 8 bytes) or two
+//                                x-neighbours (V = 2, 16 bytes, volumes with an even nx: every pair is 16-byte aligned), lanes along x.  COLOR: a colour
+//                                volume beside the first; a voxel's colour is updated exactly when its (F, W) is, from the pixel
+//                                the depth was read at
+//   ovo_tsdf_raycast[_color | _normals]   k_tsdf_raycast<COLOR, NORMALS>   one launch, one thread per pixel, 16 x 16 pixel tiles: a fixed-step march,
+//                                trilinear samples.  At a hit, COLOR: 16 eight-byte colour loads and three blends per channel; NORMALS (DESIGN.md
+//                                section 21): the gradient of F (tsdf_gradient.h) at the eight corners of the two bracketing samples, blended as F
+//                                is, normalised
+// The volume is float2 [nz][ny][nx] = (F, W), x fastest; all-zero bytes are "unobserved".  The colour volume is uint2 [nz][ny][nx] (four u16: R, G, B,
+// spare) with the volume's indexing.  No atomics, no cross-thread traffic: every result is a pure function of the inputs, bit-equal from run to run
+// and whatever OVO_TSDF_GRID_CAP says (it only changes which workgroup visits a voxel).
+// Every index is in range by construction.  Integrate: the box is checked against the volume on the host, one `idx` is added to both bases, and every
+// `rgb` address is formed from the (v, u) that tsdf_sample has tested against the image.  Ray cast: tsdf_cell tests a sample's base cell against
+// [0, n - 2] on all three axes and the march forms an address only after it passes; colour and gradient are read only at a hit, around the base cells
+// of the samples k - 1 and k, which both passed that test and are formed again by the same tsdf_cell (tsdf_cell_index says why that is safe); a
+// corner's neighbour is addressed only after its index has passed the test against [0, n) (tsdf_gradient); all three outputs are written at the one
+// pixel (pv, pu) that was tested against the image.
 // This file is compiled with -ffp-contract=off (projection.h): f32 operations are single IEEE operations in the order written, except the dot3 / dot4 chains.
 #include <math.h>
 
@@ -54,76 +52,39 @@ __device__ __forceinline__ bool tsdf_sample(const TsdfVol &v, const TsdfCam &c, 
     return true;
 }
 
-__device__ __forceinline__ void tsdf_update(float &F, float &W, float f, float max_weight) {
+// One channel: q <- rint((q W + 256 c) / W1), W the weight BEFORE this frame's update.  For an integer max_weight <= 127 both numerator terms and
+// their sum are integers below 2^24, so the only rounding is the division's, and rintf takes the quotient half to even (DESIGN.md section 20).
+__device__ __forceinline__ uint32_t color_mix(uint32_t q, float W, float W1, uint8_t c) { return (uint32_t)rintf(((float)q * W + 256.0f * (float)c) / W1); }
+
+// One voxel takes the sample f read at pixel `pix`: with COLOR its colour words (rg, bs) first, since they mix with the weight before the update.
+template <bool COLOR>
+__device__ __forceinline__ void tsdf_update(float &F, float &W, uint32_t &rg, uint32_t &bs, float f, int64_t pix, float max_weight, const uint8_t *__restrict__ rgb) {
     const float W1 = W + 1.0f;
+    if (COLOR) {
+        const uint8_t *s = rgb + pix * 3;
+        rg = color_mix(rg & 0xffffu, W, W1, s[0]) | color_mix(rg >> 16, W, W1, s[1]) << 16;
+        bs = color_mix(bs & 0xffffu, W, W1, s[2]) | (bs & 0xffff0000u);                        // the spare word is stored as it was read
+    }
     F = (F * W + f) / W1;
     W = fminf(W1, max_weight);
 }
 
 // Items are dealt lane by lane along x, then y, then z of the box: item -> (x item, row) with one 32-bit division, row -> (j, k) with another.
 // V = 2: x item q is the voxel pair (2 q, 2 q + 1); a pair with one voxel outside the box touches only the other one, with an 8-byte access.
-template <int V>
+// COLOR = false: `col` and `rgb` are null and never touched (they come last, so the plain form's kernel arguments lie as they would without them);
+// the items, the decisions and the (F, W) bits are the same either way.
+template <int V, bool COLOR>
 __global__ void __launch_bounds__(256) k_tsdf_integrate(float2 *__restrict__ vol, const TsdfVol v, const float *__restrict__ depth, const TsdfCam c,
-                                                        const TsdfBox b) {
+                                                        const TsdfBox b, uint2 *__restrict__ col, const uint8_t *__restrict__ rgb) {
     const uint32_t q0 = (uint32_t)(b.x0 / V), nq = (uint32_t)((b.x1 - 1) / V) - q0 + 1, by = (uint32_t)(b.y1 - b.y0);
     const uint64_t items = (uint64_t)nq * by * (uint32_t)(b.z1 - b.z0);                          // <= 2^31
     for (uint64_t it = (uint64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (uint64_t)gridDim.x * 256) {
         const uint32_t row = (uint32_t)it / nq, q = (uint32_t)it - row * nq;                     // (it < 2^32)
         const uint32_t kk = row / by, jj = row - kk * by;
         const int i = (int)(q0 + q) * V, j = b.y0 + (int)jj, k = b.z0 + (int)kk;
-        float2 *p = vol + ((int64_t)k * v.ny + j) * v.nx + i;
-        if (V == 2) {
-            const bool in0 = i >= b.x0, in1 = i + 1 < b.x1;                                      // (at least one of them)
-            float f0 = 0.0f, f1 = 0.0f;
-            int64_t px;
-            const bool up0 = in0 && tsdf_sample(v, c, depth, i, j, k, f0, px), up1 = in1 && tsdf_sample(v, c, depth, i + 1, j, k, f1, px);
-            if (!(up0 || up1)) continue;
-            if (in0 && in1) {
-                float4 a = *(float4 *)p;
-                if (up0) tsdf_update(a.x, a.y, f0, v.max_weight);
-                if (up1) tsdf_update(a.z, a.w, f1, v.max_weight);
-                *(float4 *)p = a;
-            } else {
-                float2 *one = p + (in0 ? 0 : 1);
-                float2 a = *one;
-                tsdf_update(a.x, a.y, in0 ? f0 : f1, v.max_weight);
-                *one = a;
-            }
-        } else {
-            float f = 0.0f;
-            int64_t px;
-            if (!tsdf_sample(v, c, depth, i, j, k, f, px)) continue;
-            float2 a = *p;
-            tsdf_update(a.x, a.y, f, v.max_weight);
-            *p = a;
-        }
-    }
-}
-
-// One channel: q <- rint((q W + 256 c) / W1), W the weight BEFORE this frame's update.  For an integer max_weight <= 127 both numerator terms and
-// their sum are integers below 2^24, so the only rounding is the division's, and rintf takes the quotient half to even (DESIGN.md section 20).
-__device__ __forceinline__ uint32_t color_mix(uint32_t q, float W, float W1, uint8_t c) { return (uint32_t)rintf(((float)q * W + 256.0f * (float)c) / W1); }
-
-__device__ __forceinline__ void tsdf_update_color(uint32_t &rg, uint32_t &bs, float W, const uint8_t *__restrict__ rgb, int64_t pix) {
-    const float W1 = W + 1.0f;
-    const uint8_t *s = rgb + pix * 3;
-    rg = color_mix(rg & 0xffffu, W, W1, s[0]) | color_mix(rg >> 16, W, W1, s[1]) << 16;
-    bs = color_mix(bs & 0xffffu, W, W1, s[2]) | (bs & 0xffff0000u);                            // the spare word is stored as it was read
-}
-
-// k_tsdf_integrate<V> with the colour volume beside it: the same items, the same decisions, the same (F, W) bits; `idx` serves both arrays.
-template <int V>
-__global__ void __launch_bounds__(256) k_tsdf_integrate_color(float2 *__restrict__ vol, uint2 *__restrict__ col, const TsdfVol v, const float *__restrict__ depth,
-                                                              const uint8_t *__restrict__ rgb, const TsdfCam c, const TsdfBox b) {
-    const uint32_t q0 = (uint32_t)(b.x0 / V), nq = (uint32_t)((b.x1 - 1) / V) - q0 + 1, by = (uint32_t)(b.y1 - b.y0);
-    const uint64_t items = (uint64_t)nq * by * (uint32_t)(b.z1 - b.z0);                          // <= 2^31
-    for (uint64_t it = (uint64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (uint64_t)gridDim.x * 256) {
-        const uint32_t row = (uint32_t)it / nq, q = (uint32_t)it - row * nq;                     // (it < 2^32)
-        const uint32_t kk = row / by, jj = row - kk * by;
-        const int i = (int)(q0 + q) * V, j = b.y0 + (int)jj, k = b.z0 + (int)kk;
-        const int64_t idx = ((int64_t)k * v.ny + j) * v.nx + i;
+        const int64_t idx = ((int64_t)k * v.ny + j) * v.nx + i;                                  // serves both arrays
         float2 *p = vol + idx;
-        uint2 *pc = col + idx;
+        uint2 *pc = COLOR ? col + idx : nullptr;
         if (V == 2) {
             const bool in0 = i >= b.x0, in1 = i + 1 < b.x1;                                      // (at least one of them)
             float f0 = 0.0f, f1 = 0.0f;
@@ -132,53 +93,71 @@ __global__ void __launch_bounds__(256) k_tsdf_integrate_color(float2 *__restrict
             if (!(up0 || up1)) continue;
             if (in0 && in1) {
                 float4 a = *(float4 *)p;
-                uint4 w = *(uint4 *)pc;
-                if (up0) { tsdf_update_color(w.x, w.y, a.y, rgb, px0); tsdf_update(a.x, a.y, f0, v.max_weight); }
-                if (up1) { tsdf_update_color(w.z, w.w, a.w, rgb, px1); tsdf_update(a.z, a.w, f1, v.max_weight); }
+                uint4 w = {0, 0, 0, 0};
+                if (COLOR) w = *(uint4 *)pc;
+                if (up0) tsdf_update<COLOR>(a.x, a.y, w.x, w.y, f0, px0, v.max_weight, rgb);
+                if (up1) tsdf_update<COLOR>(a.z, a.w, w.z, w.w, f1, px1, v.max_weight, rgb);
                 *(float4 *)p = a;
-                *(uint4 *)pc = w;
+                if (COLOR) *(uint4 *)pc = w;
             } else {
                 const int o = in0 ? 0 : 1;
                 float2 a = p[o];
-                uint2 w = pc[o];
-                tsdf_update_color(w.x, w.y, a.y, rgb, in0 ? px0 : px1);
-                tsdf_update(a.x, a.y, in0 ? f0 : f1, v.max_weight);
+                uint2 w = {0, 0};
+                if (COLOR) w = pc[o];
+                tsdf_update<COLOR>(a.x, a.y, w.x, w.y, in0 ? f0 : f1, in0 ? px0 : px1, v.max_weight, rgb);
                 p[o] = a;
-                pc[o] = w;
+                if (COLOR) pc[o] = w;
             }
         } else {
             float f = 0.0f;
             int64_t px = 0;
             if (!tsdf_sample(v, c, depth, i, j, k, f, px)) continue;
             float2 a = *p;
-            uint2 w = *pc;
-            tsdf_update_color(w.x, w.y, a.y, rgb, px);
-            tsdf_update(a.x, a.y, f, v.max_weight);
+            uint2 w = {0, 0};
+            if (COLOR) w = *pc;
+            tsdf_update<COLOR>(a.x, a.y, w.x, w.y, f, px, v.max_weight, rgb);
             *p = a;
-            *pc = w;
+            if (COLOR) *pc = w;
         }
     }
 }
 
-// The samples of pixel (v, u) lie at z_k = near + k dz, k = 0 .. kmax.  [k0, k1] is a range outside of which every sample is provably outside the volume
-// (slabs of the box grown by a voxel and a relative margin, two steps added at each end); inside it the validity test decides, as it would for every k.
-// The three channels of sample k of a ray, each the trilinear blend of the eight corners' (float) q with the sample's own t, along x, then y, then z.
-// Only called for a sample the march found valid: the base cell is then in [0, n - 2] already, and the clamp is a no-op that keeps every address in range.
-__device__ __forceinline__ void tsdf_cell_color(const uint2 *__restrict__ col, const TsdfVol &v, const TsdfCam &c, float dz, int k, const float t0[3],
-                                                const float dw[3], float out[3]) {
+// The samples of pixel (v, u) lie at z_k = near + k dz, k = 0 .. kmax, at t0 + z_k dw in the volume's frame.  tsdf_cell: sample k's base cell `bf`
+// (whole numbers, as floats) and its trilinear weights `tt`; returns whether the base cell lies in [0, n - 2] on all three axes, i.e. whether all
+// eight corners are voxels.  The march and the reads at a hit share this one statement of the expressions: a sample formed again is formed by the
+// same IEEE operations on the same values, which is what the bit-equality of depth, colour and normals across the four kernels rests on.
+__device__ __forceinline__ bool tsdf_cell(const TsdfVol &v, const TsdfCam &c, float dz, int k, const float t0[3], const float dw[3], float bf[3], float tt[3]) {
     const float org[3] = {v.ox, v.oy, v.oz};
     const int n[3] = {v.nx, v.ny, v.nz};
     const float zk = c.near + (float)k * dz;
-    float tt[3];
-    int b[3];
+    bool inside = true;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float pos = t0[a] + zk * dw[a];
         const float g = (pos - org[a]) / v.voxel;
-        const float bf = floorf(g);
-        tt[a] = g - bf;
-        b[a] = (int)fminf(fmaxf(bf, 0.0f), (float)(n[a] - 2));
+        bf[a] = floorf(g);
+        tt[a] = g - bf[a];
+        inside &= (bf[a] >= 0.0f) & (bf[a] <= (float)(n[a] - 2));            // (NaN and the infinities fail; no short circuit: all three axes are computed anyway)
     }
+    return inside;
+}
+
+// The base cell of a sample as an index triple, for the reads at a hit.  They are only made for a sample the march found valid: the base cell is then
+// in [0, n - 2] already, and the clamp is a no-op that keeps every address in range without a second verdict to act on.
+__device__ __forceinline__ void tsdf_cell_index(const TsdfVol &v, const TsdfCam &c, float dz, int k, const float t0[3], const float dw[3], int b[3], float tt[3]) {
+    const int n[3] = {v.nx, v.ny, v.nz};
+    float bf[3];
+    tsdf_cell(v, c, dz, k, t0, dw, bf, tt);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) b[a] = (int)fminf(fmaxf(bf[a], 0.0f), (float)(n[a] - 2));
+}
+
+// The three channels of sample k of a ray, each the trilinear blend of the eight corners' (float) q with the sample's own t, along x, then y, then z.
+__device__ __forceinline__ void tsdf_cell_color(const uint2 *__restrict__ col, const TsdfVol &v, const TsdfCam &c, float dz, int k, const float t0[3],
+                                                const float dw[3], float out[3]) {
+    float tt[3];
+    int b[3];
+    tsdf_cell_index(v, c, dz, k, t0, dw, b, tt);
     const uint2 *p = col + ((int64_t)b[2] * v.ny + b[1]) * v.nx + b[0];
     const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
     const uint2 c000 = p[0], c100 = p[1], c010 = p[sy], c110 = p[sy + 1], c001 = p[sz], c101 = p[sz + 1], c011 = p[sz + sy], c111 = p[sz + sy + 1];
@@ -190,22 +169,12 @@ __device__ __forceinline__ void tsdf_cell_color(const uint2 *__restrict__ col, c
 }
 
 // The gradient at sample k of a ray: each component the trilinear blend (x, then y, then z, the sample's own t) of grad(corner; W > 0) over the eight
-// corners.  Only called for a sample the march found valid, as tsdf_cell_color: the same expressions, the same no-op clamp.
+// corners.
 __device__ __forceinline__ void tsdf_cell_gradient(const float2 *__restrict__ vol, const TsdfVol &v, const TsdfCam &c, float dz, int k, const float t0[3],
                                                    const float dw[3], float out[3]) {
-    const float org[3] = {v.ox, v.oy, v.oz};
-    const int n[3] = {v.nx, v.ny, v.nz};
-    const float zk = c.near + (float)k * dz;
     float tt[3];
     int b[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float pos = t0[a] + zk * dw[a];
-        const float g = (pos - org[a]) / v.voxel;
-        const float bf = floorf(g);
-        tt[a] = g - bf;
-        b[a] = (int)fminf(fmaxf(bf, 0.0f), (float)(n[a] - 2));
-    }
+    tsdf_cell_index(v, c, dz, k, t0, dw, b, tt);
     float gc[8][3];                                          // corner x + 2 y + 4 z; every index below is a compile-time constant
 #pragma unroll
     for (int cn = 0; cn < 8; ++cn) {
@@ -221,9 +190,11 @@ __device__ __forceinline__ void tsdf_cell_gradient(const float2 *__restrict__ vo
 
 // COLOR: at a hit the colour volume is read at the base cells of the two bracketing samples; the march itself is the same code for all four kernels.
 // NORMALS: the gradient is read around the same two cells of a hit, after the march (the loop only notes k and s); three +0.0f without a hit.
+// A pointer that a form does not use (`col` and `rgb_out` without COLOR, `normals_out` without NORMALS) is null and never touched.
 template <bool COLOR, bool NORMALS>
-__device__ __forceinline__ void tsdf_march(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v, const TsdfCam c, float dz, int kmax,
-                                           int tiles_x, float *__restrict__ out, uint8_t *__restrict__ rgb_out, float *__restrict__ normals_out) {
+__global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v, const TsdfCam c,
+                                                                        float dz, int kmax, int tiles_x, float *__restrict__ out, uint8_t *__restrict__ rgb_out,
+                                                                        float *__restrict__ normals_out) {
     const int tile = blockIdx.x, ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const int pu = tx * TSDF_TILE + (threadIdx.x & (TSDF_TILE - 1)), pv = ty * TSDF_TILE + (threadIdx.x / TSDF_TILE);
     if (pu >= c.w || pv >= c.h) return;
@@ -233,7 +204,8 @@ __device__ __forceinline__ void tsdf_march(const float2 *__restrict__ vol, const
     for (int r = 0; r < 3; ++r) { dw[r] = dot3(c.c2w + 4 * r, dc[0], dc[1], dc[2]); t0[r] = c.c2w[4 * r + 3]; }
     const float org[3] = {v.ox, v.oy, v.oz};
     const int n[3] = {v.nx, v.ny, v.nz};
-    // ---- the clip: only ever skips samples that are outside the volume
+    // ---- the clip: [k0, k1] is a range outside of which every sample is provably outside the volume (slabs of the box grown by a voxel and a relative
+    // margin, two steps added at each end); inside it tsdf_cell decides, as it would for every k
     float z_lo = c.near, z_hi = c.far + dz;
     bool any = true;
 #pragma unroll
@@ -259,18 +231,8 @@ __device__ __forceinline__ void tsdf_march(const float2 *__restrict__ vol, const
     int hit_k = -1;
     bool valid_prev = false;
     for (int k = k0; k <= k1; ++k) {
-        const float zk = c.near + (float)k * dz;
         float bf[3], tt[3];
-        bool inside = true;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float pos = t0[a] + zk * dw[a];
-            const float g = (pos - org[a]) / v.voxel;
-            bf[a] = floorf(g);
-            tt[a] = g - bf[a];
-            inside = inside && bf[a] >= 0.0f && bf[a] <= (float)(n[a] - 2);      // (NaN and the infinities fail)
-        }
-        if (!inside) { valid_prev = false; continue; }      // no address is formed for such a sample
+        if (!tsdf_cell(v, c, dz, k, t0, dw, bf, tt)) { valid_prev = false; continue; }      // no address is formed for such a sample
         const float2 *p = vol + ((int64_t)(int)bf[2] * v.ny + (int)bf[1]) * v.nx + (int)bf[0];
         const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
         const float2 c000 = p[0], c100 = p[1], c010 = p[sy], c110 = p[sy + 1], c001 = p[sz], c101 = p[sz + 1], c011 = p[sz + sy], c111 = p[sz + sy + 1];
@@ -307,7 +269,7 @@ __device__ __forceinline__ void tsdf_march(const float2 *__restrict__ vol, const
         for (int e = 0; e < 2; ++e) {                        // one sample at a time: this runs once a pixel, and the kernel keeps the march's occupancy
 #pragma unroll
             for (int a = 0; a < 3; ++a) { ga[a] = gb[a]; ca[a] = cb[a]; }
-            if (COLOR) tsdf_cell_color(col, v, c, dz, hit_k - 1 + e, t0, dw, cb);      // the same operations on the same values as k_tsdf_raycast_color's
+            if (COLOR) tsdf_cell_color(col, v, c, dz, hit_k - 1 + e, t0, dw, cb);      // the same operations on the same values as the colour-only form's
             tsdf_cell_gradient(vol, v, c, dz, hit_k - 1 + e, t0, dw, gb);
         }
 #pragma unroll
@@ -331,28 +293,6 @@ __device__ __forceinline__ void tsdf_march(const float2 *__restrict__ vol, const
     }
 }
 
-__global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const float2 *__restrict__ vol, const TsdfVol v, const TsdfCam c, float dz, int kmax,
-                                                                        int tiles_x, float *__restrict__ out) {
-    tsdf_march<false, false>(vol, nullptr, v, c, dz, kmax, tiles_x, out, nullptr, nullptr);
-}
-
-__global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast_color(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v,
-                                                                              const TsdfCam c, float dz, int kmax, int tiles_x, float *__restrict__ out,
-                                                                              uint8_t *__restrict__ rgb_out) {
-    tsdf_march<true, false>(vol, col, v, c, dz, kmax, tiles_x, out, rgb_out, nullptr);
-}
-
-__global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast_normals(const float2 *__restrict__ vol, const TsdfVol v, const TsdfCam c, float dz, int kmax,
-                                                                                int tiles_x, float *__restrict__ out, float *__restrict__ normals_out) {
-    tsdf_march<false, true>(vol, nullptr, v, c, dz, kmax, tiles_x, out, nullptr, normals_out);
-}
-
-__global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast_color_normals(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v,
-                                                                                      const TsdfCam c, float dz, int kmax, int tiles_x, float *__restrict__ out,
-                                                                                      uint8_t *__restrict__ rgb_out, float *__restrict__ normals_out) {
-    tsdf_march<true, true>(vol, col, v, c, dz, kmax, tiles_x, out, rgb_out, normals_out);
-}
-
 const char *tsdf_camera_check(const ovo_tsdf_camera_t *c) {
     if (!c) return "null pointer";
     if (!(c->h >= 1 && c->w >= 1 && (int64_t)c->h * c->w <= TSDF_MAX_PIXELS)) return "h, w >= 1 and h * w <= 2^26";
@@ -368,125 +308,100 @@ TsdfCam tsdf_cam(const ovo_tsdf_camera_t &s) {
     return c;
 }
 
-}  // namespace
-
-extern "C" size_t ovo_tsdf_volume_bytes(const ovo_tsdf_volume_t *desc) {
-    return tsdf_volume_check(desc) ? 0 : (size_t)desc->nx * (size_t)desc->ny * (size_t)desc->nz * sizeof(float2);
-}
-
-extern "C" int ovo_tsdf_integrate(void *vol, const ovo_tsdf_volume_t *desc, const float *depth, const ovo_tsdf_camera_t *cam, const int32_t *lo,
-                                  const int32_t *hi, ovo_stream_t stream) {
-    // everything is checked HERE, before anything is queued
-    OVO_REQUIRE(vol && desc && depth && cam && lo && hi, "null pointer");
+// Both integrate entry points: everything is checked HERE, before the one launch is queued.  Returns what is wrong, for the entry point to report under
+// its own name, or nullptr after the launch.  `col` and `rgb` are null for the colourless form (the entry points refuse a null pointer of their own).
+const char *tsdf_integrate(void *vol, void *col, const ovo_tsdf_volume_t *desc, const float *depth, const uint8_t *rgb, const ovo_tsdf_camera_t *cam,
+                           const int32_t *lo, const int32_t *hi, ovo_stream_t stream) {
+    if (!vol || !depth || !lo || !hi) return "null pointer";
     const char *wrong = tsdf_volume_check(desc);
-    OVO_REQUIRE(!wrong, wrong);
-    wrong = tsdf_camera_check(cam);
-    OVO_REQUIRE(!wrong, wrong);
-    OVO_REQUIRE(((uintptr_t)vol & 15) == 0 && ((uintptr_t)depth & 3) == 0, "volume not 16-byte aligned (depth: 4)");
+    if (!wrong) wrong = tsdf_camera_check(cam);
+    if (wrong) return wrong;
+    if (((uintptr_t)vol & 15) != 0 || ((uintptr_t)col & 15) != 0 || ((uintptr_t)depth & 3) != 0) return "volume or colour volume not 16-byte aligned (depth: 4)";
     const int n[3] = {desc->nx, desc->ny, desc->nz};
-    for (int a = 0; a < 3; ++a) OVO_REQUIRE(lo[a] >= 0 && lo[a] < hi[a] && hi[a] <= n[a], "the box must lie inside the volume with lo < hi on every axis");
+    for (int a = 0; a < 3; ++a)
+        if (!(lo[a] >= 0 && lo[a] < hi[a] && hi[a] <= n[a])) return "the box must lie inside the volume with lo < hi on every axis";
     const TsdfBox b{lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
     const bool pairs = (desc->nx & 1) == 0;                 // an even nx: every pair (2 q, 2 q + 1) of every row starts on a 16-byte boundary
     const int64_t nq = pairs ? (int64_t)((b.x1 - 1) / 2 - b.x0 / 2 + 1) : (int64_t)(b.x1 - b.x0);
     const int64_t items = nq * (b.y1 - b.y0) * (b.z1 - b.z0);
     const int cap = ovo_knob_int("OVO_TSDF_GRID_CAP", 256 * 16);      // (tests: 2, so that every workgroup loops)
     const int grid = ovo_grid(items, 256, cap > 0 ? cap : 256 * 16);
-    if (pairs) k_tsdf_integrate<2><<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, tsdf_vol(*desc), depth, tsdf_cam(*cam), b);
-    else k_tsdf_integrate<1><<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, tsdf_vol(*desc), depth, tsdf_cam(*cam), b);
-    OVO_CHECK_LAUNCH();
-    return OVO_OK;
+    const auto kernel = pairs ? (col ? k_tsdf_integrate<2, true> : k_tsdf_integrate<2, false>) : (col ? k_tsdf_integrate<1, true> : k_tsdf_integrate<1, false>);
+    kernel<<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, tsdf_vol(*desc), depth, tsdf_cam(*cam), b, (uint2 *)col, rgb);
+    return nullptr;
+}
+
+// The three ray-cast entry points, likewise: the checks, kmax and the tiles, and the one launch of the form that (col, normals_out) ask for.
+const char *tsdf_raycast(const void *vol, const void *col, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, float *depth_out,
+                         uint8_t *rgb_out, float *normals_out, ovo_stream_t stream) {
+    if (!vol || !depth_out) return "null pointer";
+    const char *wrong = tsdf_volume_check(desc);
+    if (!wrong) wrong = tsdf_camera_check(cam);
+    if (wrong) return wrong;
+    if (!finite_f(cam->far)) return "far must be finite for a march";
+    if (((uintptr_t)vol & 15) != 0 || ((uintptr_t)col & 15) != 0 || ((uintptr_t)depth_out & 3) != 0 || ((uintptr_t)normals_out & 3) != 0)
+        return "volume or colour volume not 16-byte aligned (depth_out, normals_out: 4)";
+    if (!(dz > 0.0f && finite_f(dz))) return "dz must be > 0";
+    const double steps = ceil(((double)cam->far - (double)cam->near) / (double)dz);
+    if (!(steps <= (double)TSDF_MAX_STEPS)) return "more than 4096 steps between near and far";
+    const int tiles_x = (cam->w + TSDF_TILE - 1) / TSDF_TILE, tiles_y = (cam->h + TSDF_TILE - 1) / TSDF_TILE;      // (tiles_x * tiles_y < 2^27)
+    const auto kernel = col ? (normals_out ? k_tsdf_raycast<true, true> : k_tsdf_raycast<true, false>)
+                            : (normals_out ? k_tsdf_raycast<false, true> : k_tsdf_raycast<false, false>);
+    kernel<<<tiles_x * tiles_y, TSDF_TILE * TSDF_TILE, 0, (hipStream_t)stream>>>((const float2 *)vol, (const uint2 *)col, tsdf_vol(*desc), tsdf_cam(*cam), dz,
+                                                                                (int)steps, tiles_x, depth_out, rgb_out, normals_out);
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" size_t ovo_tsdf_volume_bytes(const ovo_tsdf_volume_t *desc) {
+    return tsdf_volume_check(desc) ? 0 : (size_t)desc->nx * (size_t)desc->ny * (size_t)desc->nz * sizeof(float2);
 }
 
 extern "C" size_t ovo_tsdf_color_bytes(const ovo_tsdf_volume_t *desc) {
     return tsdf_volume_check(desc) ? 0 : (size_t)desc->nx * (size_t)desc->ny * (size_t)desc->nz * sizeof(uint2);
 }
 
-extern "C" int ovo_tsdf_integrate_color(void *vol, void *col, const ovo_tsdf_volume_t *desc, const float *depth, const uint8_t *rgb,
-                                        const ovo_tsdf_camera_t *cam, const int32_t *lo, const int32_t *hi, ovo_stream_t stream) {
-    // everything is checked HERE, before anything is queued
-    OVO_REQUIRE(vol && col && desc && depth && rgb && cam && lo && hi, "null pointer");
-    const char *wrong = tsdf_volume_check(desc);
+extern "C" int ovo_tsdf_integrate(void *vol, const ovo_tsdf_volume_t *desc, const float *depth, const ovo_tsdf_camera_t *cam, const int32_t *lo,
+                                  const int32_t *hi, ovo_stream_t stream) {
+    const char *wrong = tsdf_integrate(vol, nullptr, desc, depth, nullptr, cam, lo, hi, stream);
     OVO_REQUIRE(!wrong, wrong);
-    wrong = tsdf_camera_check(cam);
-    OVO_REQUIRE(!wrong, wrong);
-    OVO_REQUIRE(((uintptr_t)vol & 15) == 0 && ((uintptr_t)col & 15) == 0 && ((uintptr_t)depth & 3) == 0, "volume or colour volume not 16-byte aligned (depth: 4)");
-    const int n[3] = {desc->nx, desc->ny, desc->nz};
-    for (int a = 0; a < 3; ++a) OVO_REQUIRE(lo[a] >= 0 && lo[a] < hi[a] && hi[a] <= n[a], "the box must lie inside the volume with lo < hi on every axis");
-    const TsdfBox b{lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
-    const bool pairs = (desc->nx & 1) == 0;                 // as ovo_tsdf_integrate: the same items, the same grid
-    const int64_t nq = pairs ? (int64_t)((b.x1 - 1) / 2 - b.x0 / 2 + 1) : (int64_t)(b.x1 - b.x0);
-    const int64_t items = nq * (b.y1 - b.y0) * (b.z1 - b.z0);
-    const int cap = ovo_knob_int("OVO_TSDF_GRID_CAP", 256 * 16);
-    const int grid = ovo_grid(items, 256, cap > 0 ? cap : 256 * 16);
-    if (pairs) k_tsdf_integrate_color<2><<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, (uint2 *)col, tsdf_vol(*desc), depth, rgb, tsdf_cam(*cam), b);
-    else k_tsdf_integrate_color<1><<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, (uint2 *)col, tsdf_vol(*desc), depth, rgb, tsdf_cam(*cam), b);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }
 
-extern "C" int ovo_tsdf_raycast_color(const void *vol, const void *col, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, float *depth_out,
-                                      uint8_t *rgb_out, ovo_stream_t stream) {
-    // everything is checked HERE, before anything is queued
-    OVO_REQUIRE(vol && col && desc && cam && depth_out && rgb_out, "null pointer");
-    const char *wrong = tsdf_volume_check(desc);
+extern "C" int ovo_tsdf_integrate_color(void *vol, void *col, const ovo_tsdf_volume_t *desc, const float *depth, const uint8_t *rgb,
+                                        const ovo_tsdf_camera_t *cam, const int32_t *lo, const int32_t *hi, ovo_stream_t stream) {
+    OVO_REQUIRE(col && rgb, "null pointer");
+    const char *wrong = tsdf_integrate(vol, col, desc, depth, rgb, cam, lo, hi, stream);
     OVO_REQUIRE(!wrong, wrong);
-    wrong = tsdf_camera_check(cam);
-    OVO_REQUIRE(!wrong, wrong);
-    OVO_REQUIRE(finite_f(cam->far), "far must be finite for a march");
-    OVO_REQUIRE(((uintptr_t)vol & 15) == 0 && ((uintptr_t)col & 15) == 0 && ((uintptr_t)depth_out & 3) == 0,
-                "volume or colour volume not 16-byte aligned (depth_out: 4)");
-    OVO_REQUIRE(dz > 0.0f && finite_f(dz), "dz must be > 0");
-    const double steps = ceil(((double)cam->far - (double)cam->near) / (double)dz);
-    OVO_REQUIRE(steps <= (double)TSDF_MAX_STEPS, "more than 4096 steps between near and far");
-    const int tiles_x = (cam->w + TSDF_TILE - 1) / TSDF_TILE, tiles_y = (cam->h + TSDF_TILE - 1) / TSDF_TILE;      // (tiles_x * tiles_y < 2^27)
-    k_tsdf_raycast_color<<<tiles_x * tiles_y, TSDF_TILE * TSDF_TILE, 0, (hipStream_t)stream>>>((const float2 *)vol, (const uint2 *)col, tsdf_vol(*desc),
-                                                                                              tsdf_cam(*cam), dz, (int)steps, tiles_x, depth_out, rgb_out);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }
 
 extern "C" int ovo_tsdf_raycast(const void *vol, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, float *depth_out,
                                 ovo_stream_t stream) {
-    // everything is checked HERE, before anything is queued
-    OVO_REQUIRE(vol && desc && cam && depth_out, "null pointer");
-    const char *wrong = tsdf_volume_check(desc);
+    const char *wrong = tsdf_raycast(vol, nullptr, desc, cam, dz, depth_out, nullptr, nullptr, stream);
     OVO_REQUIRE(!wrong, wrong);
-    wrong = tsdf_camera_check(cam);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
+
+extern "C" int ovo_tsdf_raycast_color(const void *vol, const void *col, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, float *depth_out,
+                                      uint8_t *rgb_out, ovo_stream_t stream) {
+    OVO_REQUIRE(col && rgb_out, "null pointer");
+    const char *wrong = tsdf_raycast(vol, col, desc, cam, dz, depth_out, rgb_out, nullptr, stream);
     OVO_REQUIRE(!wrong, wrong);
-    OVO_REQUIRE(finite_f(cam->far), "far must be finite for a march");
-    OVO_REQUIRE(((uintptr_t)vol & 15) == 0 && ((uintptr_t)depth_out & 3) == 0, "volume not 16-byte aligned (depth_out: 4)");
-    OVO_REQUIRE(dz > 0.0f && finite_f(dz), "dz must be > 0");
-    const double steps = ceil(((double)cam->far - (double)cam->near) / (double)dz);
-    OVO_REQUIRE(steps <= (double)TSDF_MAX_STEPS, "more than 4096 steps between near and far");
-    const int tiles_x = (cam->w + TSDF_TILE - 1) / TSDF_TILE, tiles_y = (cam->h + TSDF_TILE - 1) / TSDF_TILE;      // (tiles_x * tiles_y < 2^27)
-    k_tsdf_raycast<<<tiles_x * tiles_y, TSDF_TILE * TSDF_TILE, 0, (hipStream_t)stream>>>((const float2 *)vol, tsdf_vol(*desc), tsdf_cam(*cam), dz, (int)steps,
-                                                                                        tiles_x, depth_out);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }
 
 extern "C" int ovo_tsdf_raycast_normals(const void *vol, const void *col, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, float *depth_out,
                                         uint8_t *rgb_out, float *normals_out, ovo_stream_t stream) {
-    // everything is checked HERE, before anything is queued
-    OVO_REQUIRE(vol && desc && cam && depth_out && normals_out, "null pointer");
+    OVO_REQUIRE(normals_out, "null pointer");
     OVO_REQUIRE((col == nullptr) == (rgb_out == nullptr), "col and rgb_out go together: both null or both given");
-    const char *wrong = tsdf_volume_check(desc);
+    const char *wrong = tsdf_raycast(vol, col, desc, cam, dz, depth_out, rgb_out, normals_out, stream);
     OVO_REQUIRE(!wrong, wrong);
-    wrong = tsdf_camera_check(cam);
-    OVO_REQUIRE(!wrong, wrong);
-    OVO_REQUIRE(finite_f(cam->far), "far must be finite for a march");
-    OVO_REQUIRE(((uintptr_t)vol & 15) == 0 && ((uintptr_t)col & 15) == 0 && ((uintptr_t)depth_out & 3) == 0 && ((uintptr_t)normals_out & 3) == 0,
-                "volume or colour volume not 16-byte aligned (depth_out, normals_out: 4)");
-    OVO_REQUIRE(dz > 0.0f && finite_f(dz), "dz must be > 0");
-    const double steps = ceil(((double)cam->far - (double)cam->near) / (double)dz);
-    OVO_REQUIRE(steps <= (double)TSDF_MAX_STEPS, "more than 4096 steps between near and far");
-    const int tiles_x = (cam->w + TSDF_TILE - 1) / TSDF_TILE, tiles_y = (cam->h + TSDF_TILE - 1) / TSDF_TILE;      // (tiles_x * tiles_y < 2^27)
-    if (col)
-        k_tsdf_raycast_color_normals<<<tiles_x * tiles_y, TSDF_TILE * TSDF_TILE, 0, (hipStream_t)stream>>>(
-            (const float2 *)vol, (const uint2 *)col, tsdf_vol(*desc), tsdf_cam(*cam), dz, (int)steps, tiles_x, depth_out, rgb_out, normals_out);
-    else
-        k_tsdf_raycast_normals<<<tiles_x * tiles_y, TSDF_TILE * TSDF_TILE, 0, (hipStream_t)stream>>>((const float2 *)vol, tsdf_vol(*desc), tsdf_cam(*cam), dz,
-                                                                                                    (int)steps, tiles_x, depth_out, normals_out);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }

@@ -156,10 +156,16 @@ class TsdfVolume:
             raise L.OvoHipError("TsdfVolume.refuse: a colour volume needs a TsdfHistory made with color=True")
         self.reset()
         for e, c2w in zip(entries, poses):
-            if color:
-                self.integrate(history.depths[e["slot"]], K, c2w, near, far, rgb=history.colors[e["slot"]])
-            else:
-                self.integrate(history.depths[e["slot"]], K, c2w, near, far)
+            rgb = {"rgb": history.colors[e["slot"]]} if color else {}      # (a plain volume is called as before colour existed: stand-ins take no `rgb`)
+            self.integrate(history.depths[e["slot"]], K, c2w, near, far, **rgb)
+
+    def _image(self, given: Optional[torch.Tensor], shape: tuple, dtype: torch.dtype, name: str) -> torch.Tensor:
+        """An output image of a ray cast: `given`, checked to be on the device with this shape and dtype, or a new one."""
+        out = torch.empty(shape, dtype=dtype, device=self.vol.device) if given is None else given
+        L.dev(out, dtype, name)
+        if tuple(out.shape) != shape:
+            raise L.OvoHipError(f"TsdfVolume.raycast: {name} must be {list(shape)} (got {tuple(out.shape)})")
+        return out
 
     def raycast(self, K, h: int, w: int, c2w, near: float, far: float, dz: Optional[float] = None, out: Optional[torch.Tensor] = None,
                 color: bool = False, out_rgb: Optional[torch.Tensor] = None, normals: bool = False, out_normals: Optional[torch.Tensor] = None):
@@ -174,37 +180,18 @@ class TsdfVolume:
             raise L.OvoHipError("TsdfVolume.raycast: out_rgb is only written with color=True")
         if out_normals is not None and not normals:
             raise L.OvoHipError("TsdfVolume.raycast: out_normals is only written with normals=True")
-        if out is None:
-            out = torch.empty((int(h), int(w)), dtype=torch.float32, device=self.vol.device)
-        L.dev(out, torch.float32, "out")
-        if tuple(out.shape) != (int(h), int(w)):
-            raise L.OvoHipError(f"TsdfVolume.raycast: out must be [{h}, {w}] (got {tuple(out.shape)})")
+        h, w = int(h), int(w)
+        out = self._image(out, (h, w), torch.float32, "out")
         cam = camera_desc(K, h, w, c2w, near, far)
-        if normals:
-            if out_normals is None:
-                out_normals = torch.empty((int(h), int(w), 3), dtype=torch.float32, device=self.vol.device)
-            L.dev(out_normals, torch.float32, "out_normals")
-            if tuple(out_normals.shape) != (int(h), int(w), 3):
-                raise L.OvoHipError(f"TsdfVolume.raycast: out_normals must be [{h}, {w}, 3] (got {tuple(out_normals.shape)})")
-            if color:
-                if out_rgb is None:
-                    out_rgb = torch.empty((int(h), int(w), 3), dtype=torch.uint8, device=self.vol.device)
-                L.dev(out_rgb, torch.uint8, "out_rgb")
-                if tuple(out_rgb.shape) != (int(h), int(w), 3):
-                    raise L.OvoHipError(f"TsdfVolume.raycast: out_rgb must be [{h}, {w}, 3] (got {tuple(out_rgb.shape)})")
-            L.check(L.load().ovo_tsdf_raycast_normals(L.ptr(self.vol), L.ptr(self.col) if color else None, C.byref(self.desc), C.byref(cam), dz, L.ptr(out),
-                                                      L.ptr(out_rgb) if color else None, L.ptr(out_normals), L.stream()))
-            return (out, out_rgb, out_normals) if color else (out, out_normals)
-        if not color:
-            L.check(L.load().ovo_tsdf_raycast(L.ptr(self.vol), C.byref(self.desc), C.byref(cam), dz, L.ptr(out), L.stream()))
-            return out
-        if out_rgb is None:
-            out_rgb = torch.empty((int(h), int(w), 3), dtype=torch.uint8, device=self.vol.device)
-        L.dev(out_rgb, torch.uint8, "out_rgb")
-        if tuple(out_rgb.shape) != (int(h), int(w), 3):
-            raise L.OvoHipError(f"TsdfVolume.raycast: out_rgb must be [{h}, {w}, 3] (got {tuple(out_rgb.shape)})")
-        L.check(L.load().ovo_tsdf_raycast_color(L.ptr(self.vol), L.ptr(self.col), C.byref(self.desc), C.byref(cam), dz, L.ptr(out), L.ptr(out_rgb), L.stream()))
-        return out, out_rgb
+        out_normals = self._image(out_normals, (h, w, 3), torch.float32, "out_normals") if normals else None
+        out_rgb = self._image(out_rgb, (h, w, 3), torch.uint8, "out_rgb") if color else None
+        vol, col, desc, cam, d, c, n = L.ptr(self.vol), L.ptr(self.col), C.byref(self.desc), C.byref(cam), L.ptr(out), L.ptr(out_rgb), L.ptr(out_normals)
+        name, args, result = {(False, False): ("ovo_tsdf_raycast", (vol, desc, cam, dz, d), out),
+                              (True, False): ("ovo_tsdf_raycast_color", (vol, col, desc, cam, dz, d, c), (out, out_rgb)),
+                              (False, True): ("ovo_tsdf_raycast_normals", (vol, None, desc, cam, dz, d, None, n), (out, out_normals)),
+                              (True, True): ("ovo_tsdf_raycast_normals", (vol, col, desc, cam, dz, d, c, n), (out, out_rgb, out_normals))}[bool(color), bool(normals)]
+        L.check(getattr(L.load(), name)(*args, L.stream()))
+        return result
 
     def extract_mesh(self, box: Optional[Box] = None, min_weight: float = 1.0, colors: bool = False, normals: bool = False):
         """The surface inside the index box (None: the whole volume) as a welded triangle mesh on the device: (vertices f32[V, 3] in the volume's
