@@ -1027,6 +1027,46 @@ int ovo_tsdf_mesh_normals(const void *vol, const ovo_tsdf_volume_t *desc, const 
 int ovo_tsdf_raycast_normals(const void *vol, const void *col /* may be NULL */, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz,
                              float *depth_out, uint8_t *rgb_out /* NULL iff col is NULL */, float *normals_out, ovo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Instance labels in the volume (still ABI v23: entry points added, none changed; restated in
+ * tests/tsdf_label_restatement.py).  The vote is that of PanopticFusion / Voxblox++: integers only, so every result below is exact.
+ *
+ * The label volume: a device array beside `vol`, int32 [nz][ny][nx][2] = (L, C), x fastest, 8 bytes a voxel, the volume's indexing and its 16-byte
+ * alignment rule; all-zero bytes mean "no label".  L = instance id + 1 (0: none), C >= 0 the label's confidence count.
+ * ovo_tsdf_label_bytes: its size, or 0 for a descriptor the entry points would refuse.
+ *
+ * ovo_tsdf_integrate_labels: a pass over the label volume alone (`vol` is not an argument: labels arrive per keyframe, after the frame's geometry
+ * has been fused).  ins int32 [h][w] (dense), any negative value = "no label".  A voxel of [lo, hi) VOTES iff ovo_tsdf_integrate would update it
+ * from this depth image (the same expressions, the same pixel (v, u)), its sample f = min(1, sdf / trunc) is < 1 (free space in front of a surface
+ * says nothing about that surface's instance) and l = ins[v][u] >= 0.  The vote:
+ *   L == 0 or C == 0:  (L, C) <- (l + 1, 1)        L == l + 1:  C <- min(C + 1, max_count)        otherwise:  C <- C - 1, L stays
+ * (a count that reaches 0 is replaced by the next vote).  A voxel that does not vote keeps its bytes; nothing outside [lo, hi) is touched.
+ *
+ * ovo_tsdf_raycast_labels: ovo_tsdf_raycast (depth_out bit-equal) and ins_out int32 [h][w], -1 without a hit.  At a hit found at sample k, with
+ * s = f_prev / (f_prev - f_k), the depth's own quotient: the sample k - 1 if s < 0.5f, else the sample k; in that sample's cell (b, t) the corner
+ * b + (t[a] >= 0.5f) on every axis a; the pixel is that voxel's L - 1 if L > 0 and C >= min_count, else -1.  One label voxel a pixel is read, and
+ * only at a hit.
+ *
+ * ovo_tsdf_mesh_labels: after ovo_tsdf_mesh_plan, with the same vol, desc, lo, hi, min_weight and workspace; ins_out int32 [V].  Vertex n of the
+ * emit order lies on the edge from its owner p to q = p + offset at t = F_p / (F_p - F_q), emit's own bits.  The nearer end is p if t < 0.5f, else
+ * q; the vertex takes that end's L - 1 if it has L > 0 and C >= min_count, otherwise the other end's under the same test, otherwise -1.  The
+ * plan's head is read back as by ovo_tsdf_mesh_colors; V == 0 queues nothing; every store is bounded by V.
+ *
+ * ovo_tsdf_labels_remap: every voxel of the volume with 0 < L <= n_table: r = table[L - 1] (device int32 [n_table], r < 2^31 - 1); r < 0 clears
+ * the voxel to (0, 0), otherwise L <- r + 1 and C stays.  A voxel whose L stays is not stored to.  n_table == 0 queues nothing.
+ *
+ * OVO_E_ARG, nothing launched: what the colourless counterpart refuses (integrate_labels: ovo_tsdf_integrate without its vol; remap: a descriptor
+ * outside its limits); a null or not 16-byte aligned lab; a null ins / ins_out / table; max_count outside 1 .. 2^30; min_count < 1; n_table < 0;
+ * mesh_labels: V negative, above 2^31 - 1 or not the plan's. */
+size_t ovo_tsdf_label_bytes(const ovo_tsdf_volume_t *desc);
+int ovo_tsdf_integrate_labels(void *lab, const ovo_tsdf_volume_t *desc, const float *depth, const int32_t *ins, const ovo_tsdf_camera_t *cam,
+                              const int32_t *lo, const int32_t *hi, int32_t max_count, ovo_stream_t stream);
+int ovo_tsdf_raycast_labels(const void *vol, const void *lab, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, int32_t min_count,
+                            float *depth_out, int32_t *ins_out, ovo_stream_t stream);
+int ovo_tsdf_mesh_labels(const void *vol, const void *lab, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight,
+                         const void *ws, size_t ws_bytes, int32_t min_count, int32_t *ins_out, int64_t V, ovo_stream_t stream);
+int ovo_tsdf_labels_remap(void *lab, const ovo_tsdf_volume_t *desc, const int32_t *table, int32_t n_table, ovo_stream_t stream);
+
 
 /* =============================================================================================
  * The keyframe chain without host round trips (MI355X extension of a6 / a9; what the reference does with a `.sum()` / vstack

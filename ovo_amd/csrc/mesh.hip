@@ -15,6 +15,8 @@
 //                                          all three kernels): a voxel blends its own colour and that of each used slot's other end, one u8 triple a vertex
 //   ovo_tsdf_mesh_normals k_mesh_normals    the same walk: a voxel takes the gradient of F (tsdf_gradient.h) at itself and at each used
 //                                          slot's other end, blends the two and normalises, one f32 triple a vertex
+//   ovo_tsdf_mesh_labels k_mesh_labels      the same walk over a label array int2 (L, C) beside the volume: the instance id of the
+//                                          edge's nearer end (t < 0.5: the owner), of the other end where that one has none, one i32 a vertex
 // A word: bits 0-6 the used slots, bits 8-22 the in-row vertex offset (<= 7 * 4095).  B word: bits 0-15 the in-row triangle offset (<= 12 * 4095),
 // bits 16-19 the cell's triangle count, bits 20-27 its corner mask (corner x + 2 y + 4 z inside).
 // The only atomic is the OR into A, whose result does not depend on order: plan and emit are pure functions of their inputs, bit-equal from run to
@@ -271,6 +273,17 @@ struct MeshNormal {                                        // k_mesh_normals: un
     }
 };
 
+struct MeshLabel {                                         // k_mesh_labels: the nearer end's instance id, else the other end's, else -1; `idx` and `off` serve both arrays
+    const int2 *__restrict__ lab; int min_count; int32_t *__restrict__ ins; const int2 *pl; int2 lp;
+    __device__ __forceinline__ void voxel(int, int, int, int64_t idx, float) { pl = lab + idx; lp = *pl; }
+    __device__ __forceinline__ void vertex(int64_t vi, int, int64_t off, float, float t) const {
+        const int2 lq = pl[off];
+        const bool p_near = t < 0.5f;                        // (a NaN t: q)
+        const int2 a = p_near ? lp : lq, o = p_near ? lq : lp;
+        ins[vi] = a.x > 0 && a.y >= min_count ? a.x - 1 : (o.x > 0 && o.y >= min_count ? o.x - 1 : -1);
+    }
+};
+
 __global__ void __launch_bounds__(256) k_mesh_emit(const float2 *__restrict__ vol, const TsdfVol v, const MeshBox b, const uint32_t *__restrict__ A,
                                                    const uint32_t *__restrict__ B, const uint2 *__restrict__ rows, float *__restrict__ verts,
                                                    int32_t *__restrict__ faces, int64_t V, int64_t T) {
@@ -348,6 +361,11 @@ __global__ void __launch_bounds__(256) k_mesh_colors(const float2 *__restrict__ 
 __global__ void __launch_bounds__(256) k_mesh_normals(const float2 *__restrict__ vol, const TsdfVol v, const MeshBox b, float min_weight,
                                                       const uint32_t *__restrict__ A, const uint2 *__restrict__ rows, float *__restrict__ normals, int64_t V) {
     mesh_vertex_pass(vol, v, b, A, rows, V, MeshNormal{vol, v, TsdfObserved{min_weight}, normals});
+}
+
+__global__ void __launch_bounds__(256) k_mesh_labels(const float2 *__restrict__ vol, const int2 *__restrict__ lab, const TsdfVol v, const MeshBox b,
+                                                     const uint32_t *__restrict__ A, const uint2 *__restrict__ rows, int min_count, int32_t *__restrict__ ins, int64_t V) {
+    mesh_vertex_pass(vol, v, b, A, rows, V, MeshLabel{lab, min_count, ins});
 }
 
 // ---- host
@@ -448,7 +466,7 @@ extern "C" int ovo_tsdf_mesh_plan(const void *vol, const ovo_tsdf_volume_t *desc
     return OVO_OK;
 }
 
-// The three calls below: everything is checked before anything is queued -- the plan's head included (mesh_planned).
+// The four calls below: everything is checked before anything is queued -- the plan's head included (mesh_planned).
 extern "C" int ovo_tsdf_mesh_emit(const void *vol, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight, const void *ws,
                                   size_t ws_bytes, float *vertices, int32_t *faces, int64_t V, int64_t T, ovo_stream_t stream) {
     MeshLayout l;
@@ -489,6 +507,22 @@ extern "C" int ovo_tsdf_mesh_normals(const void *vol, const ovo_tsdf_volume_t *d
     OVO_REQUIRE(!wrong, wrong);
     if (V == 0) return OVO_OK;                               // a plan without vertices: nothing to queue
     k_mesh_normals<<<mesh_grid(l.units), 256, 0, s>>>((const float2 *)vol, tsdf_vol(*desc), l.b, min_weight, l.A(ws), l.rows(ws), normals_out, V);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
+
+extern "C" int ovo_tsdf_mesh_labels(const void *vol, const void *lab, const ovo_tsdf_volume_t *desc, const int32_t *lo, const int32_t *hi, float min_weight,
+                                    const void *ws, size_t ws_bytes, int32_t min_count, int32_t *ins_out, int64_t V, ovo_stream_t stream) {
+    MeshLayout l;
+    const char *wrong;
+    const hipStream_t s = (hipStream_t)stream;
+    OVO_REQUIRE(lab && ins_out, "null pointer");
+    OVO_REQUIRE(((uintptr_t)lab & 15) == 0 && ((uintptr_t)ins_out & 3) == 0, "label volume not 16-byte aligned (ins_out: 4)");
+    OVO_REQUIRE(min_count >= 1, "min_count must be >= 1");
+    OVO_HIP(mesh_planned(vol, desc, lo, hi, min_weight, ws, ws_bytes, V, nullptr, s, l, wrong));
+    OVO_REQUIRE(!wrong, wrong);
+    if (V == 0) return OVO_OK;                               // a plan without vertices: nothing to queue
+    k_mesh_labels<<<mesh_grid(l.units), 256, 0, s>>>((const float2 *)vol, (const int2 *)lab, tsdf_vol(*desc), l.b, l.A(ws), l.rows(ws), min_count, ins_out, V);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }

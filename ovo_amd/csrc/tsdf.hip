@@ -1,13 +1,18 @@
 // tsdf.hip -- a fused geometric model: a dense truncated-signed-distance volume integrated from depth frames, and the ray caster that turns it back
 // into a depth image from any pose.  IcpTracker(model="tsdf") aligns every frame to that image instead of the keyframe's.
-//   ovo_tsdf_integrate[_color]   k_tsdf_integrate<V, COLOR>   one launch over the index box [lo, hi): one thread owns a voxel (V = 1, 8 bytes) or two
-//                                x-neighbours (V = 2, 16 bytes, volumes with an even nx: every pair is 16-byte aligned), lanes along x.  COLOR: a colour
+//   ovo_tsdf_integrate[_color]   k_tsdf_integrate<V, MODE>    one launch over the index box [lo, hi): one thread owns a voxel (V = 1, 8 bytes) or two
+//                                x-neighbours (V = 2, 16 bytes, volumes with an even nx: every pair is 16-byte aligned), lanes along x.  TSDF_COLOR: a colour
 //                                volume beside the first; a voxel's colour is updated exactly when its (F, W) is, from the pixel
 //                                the depth was read at
-//   ovo_tsdf_raycast[_color | _normals]   k_tsdf_raycast<COLOR, NORMALS>   one launch, one thread per pixel, 16 x 16 pixel tiles: a fixed-step march,
+//   ovo_tsdf_raycast[_color | _normals]   k_tsdf_raycast<COLOR, NORMALS, LABELS>   one launch, one thread per pixel, 16 x 16 pixel tiles: a fixed-step march,
 //                                trilinear samples.  At a hit, COLOR: 16 eight-byte colour loads and three blends per channel; NORMALS (DESIGN.md
 //                                section 21): the gradient of F (tsdf_gradient.h) at the eight corners of the two bracketing samples, blended as F
 //                                is, normalised
+//   ovo_tsdf_integrate_labels    k_tsdf_integrate<V, TSDF_LABELS>    the same items and the same tsdf_sample, over a label array
+//                                int2 [nz][ny][nx] = (L, C) alone: a voxel whose sample is f < 1 and whose pixel carries an instance id votes, in
+//                                integers; `vol` is neither read nor written
+//   ovo_tsdf_raycast_labels      k_tsdf_raycast<false, false, true>   the same march; at a hit the label of the one voxel nearest to the surface point
+//   ovo_tsdf_labels_remap        k_tsdf_labels_remap   a grid-stride pass over voxel pairs: L <- table[L - 1] + 1, stored only where it changes
 // The volume is float2 [nz][ny][nx] = (F, W), x fastest; all-zero bytes are "unobserved".  The colour volume is uint2 [nz][ny][nx] (four u16: R, G, B,
 // spare) with the volume's indexing.  No atomics, no cross-thread traffic: every result is a pure function of the inputs, bit-equal from run to run
 // and whatever OVO_TSDF_GRID_CAP says (it only changes which workgroup visits a voxel).
@@ -69,13 +74,38 @@ __device__ __forceinline__ void tsdf_update(float &F, float &W, uint32_t &rg, ui
     W = fminf(W1, max_weight);
 }
 
+// The label vote of one depth frame for the voxel at (i, j, k): whether it votes, and for which instance id l >= 0.  tsdf_sample decides as it does for
+// ovo_tsdf_integrate; free space in front of the surface (f == 1) and a pixel without an instance (l < 0) say nothing.
+__device__ __forceinline__ bool tsdf_label_sample(const TsdfVol &v, const TsdfCam &c, const float *__restrict__ depth, const int32_t *__restrict__ ins, int i, int j,
+                                                  int k, int &l) {
+    float f = 0.0f;
+    int64_t pix = 0;
+    if (!tsdf_sample(v, c, depth, i, j, k, f, pix) || !(f < 1.0f)) return false;
+    l = ins[pix];
+    return l >= 0;
+}
+
+// (L, C) takes a vote for l: L = instance id + 1 (0: none), C its confidence count.  Integers only.
+__device__ __forceinline__ void tsdf_vote(int &L, int &C, int l, int max_count) {
+    if (L == 0 || C == 0) { L = l + 1; C = 1; }
+    else if (L == l + 1) C = C < max_count ? C + 1 : max_count;
+    else C = C - 1;
+}
+
+enum { TSDF_PLAIN = 0, TSDF_COLOR = 1, TSDF_LABELS = 2 };      // what k_tsdf_integrate updates
+
 // Items are dealt lane by lane along x, then y, then z of the box: item -> (x item, row) with one 32-bit division, row -> (j, k) with another.
 // V = 2: x item q is the voxel pair (2 q, 2 q + 1); a pair with one voxel outside the box touches only the other one, with an 8-byte access.
 // COLOR = false: `col` and `rgb` are null and never touched (they come last, so the plain form's kernel arguments lie as they would without them);
 // the items, the decisions and the (F, W) bits are the same either way.
-template <int V, bool COLOR>
+// MODE == TSDF_LABELS: `vol`, `col` and `rgb` are null and never touched; `lab` takes `idx` as `vol` does, a whole pair of which at least one voxel votes
+// is one 16-byte load and store, a split pair 8 bytes, and a pair or voxel that does not vote is neither loaded nor stored.  (`lab`, `ins` and
+// `max_count` come after everything else for the same reason as `col` and `rgb`.)
+template <int V, int MODE>
 __global__ void __launch_bounds__(256) k_tsdf_integrate(float2 *__restrict__ vol, const TsdfVol v, const float *__restrict__ depth, const TsdfCam c,
-                                                        const TsdfBox b, uint2 *__restrict__ col, const uint8_t *__restrict__ rgb) {
+                                                        const TsdfBox b, uint2 *__restrict__ col, const uint8_t *__restrict__ rgb, int2 *__restrict__ lab,
+                                                        const int32_t *__restrict__ ins, int max_count) {
+    constexpr bool COLOR = MODE == TSDF_COLOR;
     const uint32_t q0 = (uint32_t)(b.x0 / V), nq = (uint32_t)((b.x1 - 1) / V) - q0 + 1, by = (uint32_t)(b.y1 - b.y0);
     const uint64_t items = (uint64_t)nq * by * (uint32_t)(b.z1 - b.z0);                          // <= 2^31
     for (uint64_t it = (uint64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (uint64_t)gridDim.x * 256) {
@@ -83,6 +113,33 @@ __global__ void __launch_bounds__(256) k_tsdf_integrate(float2 *__restrict__ vol
         const uint32_t kk = row / by, jj = row - kk * by;
         const int i = (int)(q0 + q) * V, j = b.y0 + (int)jj, k = b.z0 + (int)kk;
         const int64_t idx = ((int64_t)k * v.ny + j) * v.nx + i;                                  // serves both arrays
+        if (MODE == TSDF_LABELS) {
+            int2 *pl = lab + idx;
+            if (V == 2) {
+                const bool in0 = i >= b.x0, in1 = i + 1 < b.x1;                                  // (at least one of them)
+                int l0 = -1, l1 = -1;
+                const bool up0 = in0 && tsdf_label_sample(v, c, depth, ins, i, j, k, l0), up1 = in1 && tsdf_label_sample(v, c, depth, ins, i + 1, j, k, l1);
+                if (!(up0 || up1)) continue;
+                if (in0 && in1) {
+                    int4 a = *(int4 *)pl;
+                    if (up0) tsdf_vote(a.x, a.y, l0, max_count);
+                    if (up1) tsdf_vote(a.z, a.w, l1, max_count);
+                    *(int4 *)pl = a;
+                } else {
+                    const int o = in0 ? 0 : 1;
+                    int2 a = pl[o];
+                    tsdf_vote(a.x, a.y, in0 ? l0 : l1, max_count);
+                    pl[o] = a;
+                }
+            } else {
+                int l = -1;
+                if (!tsdf_label_sample(v, c, depth, ins, i, j, k, l)) continue;
+                int2 a = *pl;
+                tsdf_vote(a.x, a.y, l, max_count);
+                *pl = a;
+            }
+            continue;
+        }
         float2 *p = vol + idx;
         uint2 *pc = COLOR ? col + idx : nullptr;
         if (V == 2) {
@@ -191,10 +248,14 @@ __device__ __forceinline__ void tsdf_cell_gradient(const float2 *__restrict__ vo
 // COLOR: at a hit the colour volume is read at the base cells of the two bracketing samples; the march itself is the same code for all four kernels.
 // NORMALS: the gradient is read around the same two cells of a hit, after the march (the loop only notes k and s); three +0.0f without a hit.
 // A pointer that a form does not use (`col` and `rgb_out` without COLOR, `normals_out` without NORMALS) is null and never touched.
-template <bool COLOR, bool NORMALS>
+// LABELS (without COLOR and NORMALS): the loop notes k and s as for NORMALS; after it, one voxel of `lab` is read at a hit -- in the
+// cell of sample k - 1 if s < 0.5f, else of sample k, formed again by tsdf_cell_index, the corner with offset bit t[a] >= 0.5f on axis a -- and its
+// instance id, or -1, goes to ins_out at the pixel the depth goes to.  `lab`, `min_count` and `ins_out` come last and are null / unused otherwise.
+template <bool COLOR, bool NORMALS, bool LABELS>
 __global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v, const TsdfCam c,
                                                                         float dz, int kmax, int tiles_x, float *__restrict__ out, uint8_t *__restrict__ rgb_out,
-                                                                        float *__restrict__ normals_out) {
+                                                                        float *__restrict__ normals_out, const int2 *__restrict__ lab, int min_count,
+                                                                        int32_t *__restrict__ ins_out) {
     const int tile = blockIdx.x, ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const int pu = tx * TSDF_TILE + (threadIdx.x & (TSDF_TILE - 1)), pv = ty * TSDF_TILE + (threadIdx.x / TSDF_TILE);
     if (pu >= c.w || pv >= c.h) return;
@@ -254,7 +315,7 @@ __global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const flo
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) rgbf[ch] = lerp1(ca[ch], cb[ch], s);
                 }
-                if (NORMALS) { hit_k = k; hit_s = s; }      // read after the march, when the lanes of a wave that hit at different k have met again
+                if (NORMALS || LABELS) { hit_k = k; hit_s = s; }      // read after the march, when the lanes of a wave that hit at different k have met again
                 break;
             }
             if (f_prev <= 0.0f && f > 0.0f) break;           // a back face: no hit
@@ -291,6 +352,46 @@ __global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const flo
 #pragma unroll
         for (int a = 0; a < 3; ++a) o[a] = nrm[a];
     }
+    if (LABELS) {
+        int label = -1;
+        if (hit_k >= 0) {                                    // both samples passed tsdf_cell in the march: base cell + {0, 1} is a voxel on every axis
+            float tt[3];
+            int bc[3];
+            tsdf_cell_index(v, c, dz, hit_s < 0.5f ? hit_k - 1 : hit_k, t0, dw, bc, tt);
+            const int i = bc[0] + (tt[0] >= 0.5f ? 1 : 0), j = bc[1] + (tt[1] >= 0.5f ? 1 : 0), kk = bc[2] + (tt[2] >= 0.5f ? 1 : 0);      // within [0, n - 1]
+            const int2 e = lab[((int64_t)kk * v.ny + j) * v.nx + i];
+            if (e.x > 0 && e.y >= min_count) label = e.x - 1;
+        }
+        ins_out[(int64_t)pv * c.w + pu] = label;
+    }
+}
+
+// Every voxel with 0 < L <= n_table: r = table[L - 1]; r < 0 clears the voxel to (0, 0), else L <- r + 1 and C stays.  Item `it` is the voxel pair
+// (2 it, 2 it + 1), one 16-byte load (`lab` is 16-byte aligned, so every pair is), or the last voxel alone when the volume has an odd number of them.
+// A voxel is stored to, 8 bytes, only where its L changes; a pair of which both change is one 16-byte store.
+__device__ __forceinline__ bool tsdf_remap_one(int &L, int &C, const int32_t *__restrict__ table, int n_table) {
+    if (!(L > 0 && L <= n_table)) return false;
+    const int r = table[L - 1];
+    if (r + 1 == L) return false;
+    if (r < 0) { L = 0; C = 0; } else L = r + 1;
+    return true;
+}
+
+__global__ void __launch_bounds__(256) k_tsdf_labels_remap(int2 *__restrict__ lab, int64_t nvox, const int32_t *__restrict__ table, int n_table) {
+    const uint64_t items = (uint64_t)(nvox + 1) >> 1;
+    for (uint64_t it = (uint64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (uint64_t)gridDim.x * 256) {
+        int2 *p = lab + 2 * it;
+        if ((int64_t)(2 * it + 1) < nvox) {
+            int4 a = *(int4 *)p;
+            const bool ch0 = tsdf_remap_one(a.x, a.y, table, n_table), ch1 = tsdf_remap_one(a.z, a.w, table, n_table);
+            if (ch0 && ch1) *(int4 *)p = a;
+            else if (ch0) p[0] = make_int2(a.x, a.y);
+            else if (ch1) p[1] = make_int2(a.z, a.w);
+        } else {
+            int2 a = *p;
+            if (tsdf_remap_one(a.x, a.y, table, n_table)) *p = a;
+        }
+    }
 }
 
 const char *tsdf_camera_check(const ovo_tsdf_camera_t *c) {
@@ -308,15 +409,22 @@ TsdfCam tsdf_cam(const ovo_tsdf_camera_t &s) {
     return c;
 }
 
-// Both integrate entry points: everything is checked HERE, before the one launch is queued.  Returns what is wrong, for the entry point to report under
+int tsdf_grid(int64_t items) {                             // of the grid-stride kernels: integrate and the label remap
+    const int cap = ovo_knob_int("OVO_TSDF_GRID_CAP", 256 * 16);      // (tests: 2, so that every workgroup loops)
+    return ovo_grid(items, 256, cap > 0 ? cap : 256 * 16);
+}
+
+// The integrate entry points: everything is checked HERE, before the one launch is queued.  Returns what is wrong, for the entry point to report under
 // its own name, or nullptr after the launch.  `col` and `rgb` are null for the colourless form (the entry points refuse a null pointer of their own).
+// The label vote gives `lab`, `ins` and `max_count` and no `vol` (it is not looked at then).
 const char *tsdf_integrate(void *vol, void *col, const ovo_tsdf_volume_t *desc, const float *depth, const uint8_t *rgb, const ovo_tsdf_camera_t *cam,
-                           const int32_t *lo, const int32_t *hi, ovo_stream_t stream) {
-    if (!vol || !depth || !lo || !hi) return "null pointer";
+                           const int32_t *lo, const int32_t *hi, ovo_stream_t stream, void *lab = nullptr, const int32_t *ins = nullptr, int max_count = 0) {
+    if (!(lab ? lab : vol) || !depth || !lo || !hi) return "null pointer";
     const char *wrong = tsdf_volume_check(desc);
     if (!wrong) wrong = tsdf_camera_check(cam);
     if (wrong) return wrong;
     if (((uintptr_t)vol & 15) != 0 || ((uintptr_t)col & 15) != 0 || ((uintptr_t)depth & 3) != 0) return "volume or colour volume not 16-byte aligned (depth: 4)";
+    if (((uintptr_t)lab & 15) != 0 || ((uintptr_t)ins & 3) != 0) return "label volume not 16-byte aligned (ins: 4)";
     const int n[3] = {desc->nx, desc->ny, desc->nz};
     for (int a = 0; a < 3; ++a)
         if (!(lo[a] >= 0 && lo[a] < hi[a] && hi[a] <= n[a])) return "the box must lie inside the volume with lo < hi on every axis";
@@ -324,16 +432,17 @@ const char *tsdf_integrate(void *vol, void *col, const ovo_tsdf_volume_t *desc, 
     const bool pairs = (desc->nx & 1) == 0;                 // an even nx: every pair (2 q, 2 q + 1) of every row starts on a 16-byte boundary
     const int64_t nq = pairs ? (int64_t)((b.x1 - 1) / 2 - b.x0 / 2 + 1) : (int64_t)(b.x1 - b.x0);
     const int64_t items = nq * (b.y1 - b.y0) * (b.z1 - b.z0);
-    const int cap = ovo_knob_int("OVO_TSDF_GRID_CAP", 256 * 16);      // (tests: 2, so that every workgroup loops)
-    const int grid = ovo_grid(items, 256, cap > 0 ? cap : 256 * 16);
-    const auto kernel = pairs ? (col ? k_tsdf_integrate<2, true> : k_tsdf_integrate<2, false>) : (col ? k_tsdf_integrate<1, true> : k_tsdf_integrate<1, false>);
-    kernel<<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, tsdf_vol(*desc), depth, tsdf_cam(*cam), b, (uint2 *)col, rgb);
+    const int grid = tsdf_grid(items);
+    const auto kernel = lab ? (pairs ? k_tsdf_integrate<2, TSDF_LABELS> : k_tsdf_integrate<1, TSDF_LABELS>)
+                            : pairs ? (col ? k_tsdf_integrate<2, TSDF_COLOR> : k_tsdf_integrate<2, TSDF_PLAIN>)
+                                    : (col ? k_tsdf_integrate<1, TSDF_COLOR> : k_tsdf_integrate<1, TSDF_PLAIN>);
+    kernel<<<grid, 256, 0, (hipStream_t)stream>>>((float2 *)vol, tsdf_vol(*desc), depth, tsdf_cam(*cam), b, (uint2 *)col, rgb, (int2 *)lab, ins, max_count);
     return nullptr;
 }
 
 // The three ray-cast entry points, likewise: the checks, kmax and the tiles, and the one launch of the form that (col, normals_out) ask for.
 const char *tsdf_raycast(const void *vol, const void *col, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, float *depth_out,
-                         uint8_t *rgb_out, float *normals_out, ovo_stream_t stream) {
+                         uint8_t *rgb_out, float *normals_out, ovo_stream_t stream, const void *lab = nullptr, int min_count = 0, int32_t *ins_out = nullptr) {
     if (!vol || !depth_out) return "null pointer";
     const char *wrong = tsdf_volume_check(desc);
     if (!wrong) wrong = tsdf_camera_check(cam);
@@ -341,14 +450,17 @@ const char *tsdf_raycast(const void *vol, const void *col, const ovo_tsdf_volume
     if (!finite_f(cam->far)) return "far must be finite for a march";
     if (((uintptr_t)vol & 15) != 0 || ((uintptr_t)col & 15) != 0 || ((uintptr_t)depth_out & 3) != 0 || ((uintptr_t)normals_out & 3) != 0)
         return "volume or colour volume not 16-byte aligned (depth_out, normals_out: 4)";
+    if (((uintptr_t)lab & 15) != 0 || ((uintptr_t)ins_out & 3) != 0) return "label volume not 16-byte aligned (ins_out: 4)";
     if (!(dz > 0.0f && finite_f(dz))) return "dz must be > 0";
     const double steps = ceil(((double)cam->far - (double)cam->near) / (double)dz);
     if (!(steps <= (double)TSDF_MAX_STEPS)) return "more than 4096 steps between near and far";
     const int tiles_x = (cam->w + TSDF_TILE - 1) / TSDF_TILE, tiles_y = (cam->h + TSDF_TILE - 1) / TSDF_TILE;      // (tiles_x * tiles_y < 2^27)
-    const auto kernel = col ? (normals_out ? k_tsdf_raycast<true, true> : k_tsdf_raycast<true, false>)
-                            : (normals_out ? k_tsdf_raycast<false, true> : k_tsdf_raycast<false, false>);
+    const auto kernel = lab ? k_tsdf_raycast<false, false, true>
+                            : col ? (normals_out ? k_tsdf_raycast<true, true, false> : k_tsdf_raycast<true, false, false>)
+                                  : (normals_out ? k_tsdf_raycast<false, true, false> : k_tsdf_raycast<false, false, false>);
     kernel<<<tiles_x * tiles_y, TSDF_TILE * TSDF_TILE, 0, (hipStream_t)stream>>>((const float2 *)vol, (const uint2 *)col, tsdf_vol(*desc), tsdf_cam(*cam), dz,
-                                                                                (int)steps, tiles_x, depth_out, rgb_out, normals_out);
+                                                                                (int)steps, tiles_x, depth_out, rgb_out, normals_out, (const int2 *)lab,
+                                                                                min_count, ins_out);
     return nullptr;
 }
 
@@ -402,6 +514,45 @@ extern "C" int ovo_tsdf_raycast_normals(const void *vol, const void *col, const 
     OVO_REQUIRE((col == nullptr) == (rgb_out == nullptr), "col and rgb_out go together: both null or both given");
     const char *wrong = tsdf_raycast(vol, col, desc, cam, dz, depth_out, rgb_out, normals_out, stream);
     OVO_REQUIRE(!wrong, wrong);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
+
+constexpr int TSDF_MAX_COUNT = 1 << 30;                    // of a label's confidence
+
+extern "C" size_t ovo_tsdf_label_bytes(const ovo_tsdf_volume_t *desc) {
+    return tsdf_volume_check(desc) ? 0 : (size_t)desc->nx * (size_t)desc->ny * (size_t)desc->nz * sizeof(int2);
+}
+
+extern "C" int ovo_tsdf_integrate_labels(void *lab, const ovo_tsdf_volume_t *desc, const float *depth, const int32_t *ins, const ovo_tsdf_camera_t *cam,
+                                         const int32_t *lo, const int32_t *hi, int32_t max_count, ovo_stream_t stream) {
+    OVO_REQUIRE(lab && ins, "null pointer");
+    OVO_REQUIRE(max_count >= 1 && max_count <= TSDF_MAX_COUNT, "max_count must be 1 .. 2^30");
+    const char *wrong = tsdf_integrate(nullptr, nullptr, desc, depth, nullptr, cam, lo, hi, stream, lab, ins, max_count);
+    OVO_REQUIRE(!wrong, wrong);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
+
+extern "C" int ovo_tsdf_raycast_labels(const void *vol, const void *lab, const ovo_tsdf_volume_t *desc, const ovo_tsdf_camera_t *cam, float dz, int32_t min_count,
+                                       float *depth_out, int32_t *ins_out, ovo_stream_t stream) {
+    OVO_REQUIRE(lab && ins_out, "null pointer");
+    OVO_REQUIRE(min_count >= 1, "min_count must be >= 1");
+    const char *wrong = tsdf_raycast(vol, nullptr, desc, cam, dz, depth_out, nullptr, nullptr, stream, lab, min_count, ins_out);
+    OVO_REQUIRE(!wrong, wrong);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
+
+extern "C" int ovo_tsdf_labels_remap(void *lab, const ovo_tsdf_volume_t *desc, const int32_t *table, int32_t n_table, ovo_stream_t stream) {
+    OVO_REQUIRE(lab && table, "null pointer");
+    const char *wrong = tsdf_volume_check(desc);
+    OVO_REQUIRE(!wrong, wrong);
+    OVO_REQUIRE(((uintptr_t)lab & 15) == 0 && ((uintptr_t)table & 3) == 0, "label volume not 16-byte aligned (table: 4)");
+    OVO_REQUIRE(n_table >= 0, "n_table must be >= 0");
+    if (n_table == 0) return OVO_OK;                         // no voxel has 0 < L <= 0: nothing to queue
+    const int64_t nvox = (int64_t)desc->nx * desc->ny * desc->nz;
+    k_tsdf_labels_remap<<<tsdf_grid((nvox + 1) / 2), 256, 0, (hipStream_t)stream>>>((int2 *)lab, nvox, table, n_table);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }

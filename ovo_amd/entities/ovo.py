@@ -89,6 +89,7 @@ class OVO:
         self._time_cache: List[float] = []
         self.next_ins_id = 0
         self.kf_id = 0
+        self.last_instance_table: Optional[torch.Tensor] = None     # i32[n_slots]: what the last update_map did to the instance ids (None: nothing)
         self.last_point_seg: Optional[torch.Tensor] = None     # i16[N] mask id per map point of the last keyframe
         self.last_mask_rows: Optional[List[int]] = None
         # (rank, world, block) of the dense accumulators' point shards: the tracking chain then lists the points its masks cover (`ovo_track_step_t.hits`)
@@ -416,6 +417,43 @@ class OVO:
             self.keyframes["ins_maps"].append(ins_maps.cpu().numpy())
         return matched_ins_ids, binary_maps, n_matched, updated
 
+    @staticmethod
+    def instance_image(matched_ins_ids, binary_maps: torch.Tensor, hw=None) -> torch.Tensor:
+        """The instance image of a keyframe, i32[H, W] on the masks' device, from what `track_finish` returns: the id of the FIRST kept mask that
+        covers the pixel, -1 where none does -- what `TsdfVolume.integrate_labels` / `IcpTracker.fuse_labels` take.  One `ovo_paint_segmap` and one
+        gather, no host round trip (the `debug_info` loop that fills `keyframes["ins_maps"]` goes through the host and stays as it is).
+        `hw` = (h, w): resampled to that size, nearest neighbour: out[y, x] = image[y * H // h, x * W // w]."""
+        if binary_maps.dim() != 3 or binary_maps.dtype not in (torch.bool, torch.uint8) or len(matched_ins_ids) != binary_maps.shape[0]:
+            raise ValueError(f"OVO.instance_image: binary_maps must be bool [n, H, W] with one id a mask (got {binary_maps.dtype} {tuple(binary_maps.shape)} "
+                             f"for {len(matched_ins_ids)} ids)")
+        n, H, W = (int(x) for x in binary_maps.shape)
+        dev = binary_maps.device
+        if n == 0:
+            out = torch.full((H, W), -1, dtype=torch.int32, device=dev)
+        else:
+            maps = L.dev(binary_maps.view(torch.uint8) if binary_maps.dtype == torch.bool else binary_maps, torch.uint8, "binary_maps")
+            seg = torch.empty((H, W), dtype=torch.int32, device=dev)
+            L.check(L.load().ovo_paint_segmap(L.ptr(maps), n, H * W, L.ptr(seg), L.stream()))
+            ids = torch.tensor([int(i) for i in matched_ins_ids] + [-1], dtype=torch.int32).to(dev, non_blocking=True)
+            out = ids[torch.where(seg >= 0, seg, torch.full_like(seg, n)).long()]
+        if hw is not None and (int(hw[0]), int(hw[1])) != (H, W):
+            h, w = int(hw[0]), int(hw[1])
+            ys = (torch.arange(h, device=dev) * H) // h
+            xs = (torch.arange(w, device=dev) * W) // w
+            out = out[ys[:, None], xs[None, :]]
+        return out.contiguous()
+
+    @staticmethod
+    def instance_table(n_slots: int, fused: Dict[int, int], removed) -> np.ndarray:
+        """What a loop-closure update did to the instance ids, i32[n_slots]: the identity, but a fused instance b -> the a it went into and a removed
+        one -> -1.  `TsdfVolume.remap_labels` takes it."""
+        table = np.arange(int(n_slots), dtype=np.int32)
+        for b_id, a_id in fused.items():
+            table[b_id] = a_id
+        for r_id in removed:
+            table[r_id] = -1
+        return table
+
     def _fuse_masks_with_same_ins_id(self, binary_maps: torch.Tensor, matched_info) -> Dict[int, int]:
         """The ORs of ovo.py:299-306: every further mask of an instance is fused into its first one, in place.  Returns {first mask: fused
         area} when the top-k view heap wants the areas (n_top_views > 0)."""
@@ -637,8 +675,12 @@ class OVO:
         pair predicate is static during the merge loop (it only reads centroids, point sets and descriptors taken BEFORE
         any merge), so centroid distances and descriptor cosines are evaluated for all pairs at once, the nearest-neighbour
         test (`(dists < th).mean()` over an Open3D KD-tree in the reference) runs for the surviving pairs in one launch
-        (`ovo_near_fraction`), and the per-merge relabelling of the map becomes one `ovo_remap_instances` pass."""
+        (`ovo_near_fraction`), and the per-merge relabelling of the map becomes one `ovo_remap_instances` pass.
+
+        `self.last_instance_table` records what happened to the ids (`instance_table`: i32[n_slots] on the map's device, fused b -> a, removed -> -1),
+        or None when nothing changed: a label volume follows with `TsdfVolume.remap_labels(ovo.last_instance_table)`."""
         lib = L.load()
+        self.last_instance_table = None
         self.complete_semantic_info()
         points_3d, _, points_ins_ids = map_data
         for i, kf in enumerate(self.keyframes["frame_id"]):           # 0.1 keyframes the SLAM back end deleted
@@ -720,6 +762,9 @@ class OVO:
                 fused[b.id] = a.id
             objects[a.id] = a
         print(f"Semantic Map update: removed {n_removed}, fused {len(fused)} instances")
+        if fused or n_removed:
+            removed = [i for i in self.objects if cnt_h[i] <= 0]
+            self.last_instance_table = torch.from_numpy(self.instance_table(n_slots, fused, removed)).to(dev)
         if fused:
             table = np.arange(n_slots, dtype=np.int32)
             for b_id, a_id in fused.items():
@@ -849,12 +894,14 @@ class OVO:
     # ------------------------------------------------------------------ a labelled surface (no reference counterpart: it shows its result in a window)
     @torch.no_grad()
     def semantic_mesh(self, map_data, vertices: torch.Tensor, faces: torch.Tensor, transform=None, classes: Optional[List[str]] = None,
-                      template="This is a photo of a {}", th: float = 0.0, max_dist: Optional[float] = None, rgb=None, normals=None) -> Dict[str, Any]:
+                      template="This is a photo of a {}", th: float = 0.0, max_dist: Optional[float] = None, rgb=None, normals=None,
+                      instance=None) -> Dict[str, Any]:
         """The map's labels on a mesh (e.g. `IcpTracker.extract_mesh()`), ready for `mesh_utils.write_ply(path, **out)`:
           "vertices" f32[V,3]  `vertices` moved by the 4 x 4 `transform` (mesh frame -> map frame, e.g. the tracker's world_ref), in f32
           "faces"    i32[T,3]  as given
           "instance" i32[V]    the most frequent instance id among the vertex's 5 nearest ASSIGNED map points (`mesh_utils.label_mesh`), -1 where
-                               the nearest of them is farther than `max_dist`, or when the map has fewer than 5 assigned points
+                               the nearest of them is farther than `max_dist`, or when the map has fewer than 5 assigned points; or `instance`
+                               when given (the volume's own labels, `extract_mesh(labels=True)`: an i32 tensor [V], else ValueError), as it is
           "cls"      i32[V]    `classes` given: `classify_instances(classes, template, th)` of that instance, -1 without one; else None
           "rgb"      u8[V,3]   `rgb` when given (the scene's appearance, e.g. `extract_mesh(colors=True)`: u8[V,3], one row a vertex, else
                                ValueError); otherwise `mesh_utils.label_colors` of the class when `classes` is given, else of the instance
@@ -869,6 +916,9 @@ class OVO:
         if normals is not None and not (isinstance(normals, torch.Tensor) and normals.dtype == torch.float32 and tuple(normals.shape) == (v.shape[0], 3)):
             got = f"{normals.dtype} {tuple(normals.shape)}" if isinstance(normals, torch.Tensor) else type(normals).__name__
             raise ValueError(f"OVO.semantic_mesh: normals must be an f32 tensor [{v.shape[0]}, 3], one row a vertex (got {got})")
+        if instance is not None and not (isinstance(instance, torch.Tensor) and instance.dtype == torch.int32 and tuple(instance.shape) == (v.shape[0],)):
+            got = f"{instance.dtype} {tuple(instance.shape)}" if isinstance(instance, torch.Tensor) else type(instance).__name__
+            raise ValueError(f"OVO.semantic_mesh: instance must be an i32 tensor [{v.shape[0]}], one id a vertex (got {got})")
         if transform is not None:
             m = torch.as_tensor(np.asarray(transform.detach().cpu() if isinstance(transform, torch.Tensor) else transform, dtype=np.float32)).to(v.device)
             v = v @ m[:3, :3].t() + m[:3, 3]
@@ -876,7 +926,9 @@ class OVO:
                 normals = (normals @ m[:3, :3].t()).contiguous()
         v = v.contiguous()
         assigned = point_ins >= 0
-        if int(assigned.sum()) >= 5:
+        if instance is not None:
+            pass                                               # the volume's labels: nothing is transferred from the point map
+        elif int(assigned.sum()) >= 5:
             instance = M.label_mesh(v, pcd[assigned].contiguous(), point_ins[assigned], max_dist=max_dist)
         else:
             instance = torch.full((v.shape[0],), -1, dtype=torch.int32, device=v.device)

@@ -66,10 +66,13 @@ class TsdfReference:
     images, not model images.
 
     color: the volume and the history are made with color=True and every fused frame brings its colour image; the model
-    image the next frame is aligned to stays the depth-only ray cast, so poses do not depend on it.  `render(c2w)` casts depth and colour."""
+    image the next frame is aligned to stays the depth-only ray cast, so poses do not depend on it.  `render(c2w)` casts depth and colour.
+
+    labels: the volume and the history are made with labels=True.  Nothing in the frame loop votes: `fuse_labels(ins)` votes an
+    instance image with the depth and the pose of the most recent fused frame (`_last`), whenever the caller has one -- at keyframes."""
 
     def __init__(self, prepare, K, max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far, history=0,
-                 color=False) -> None:
+                 color=False, labels=False) -> None:
         self.prepare, self.K = prepare, K
         self.dims, self.voxel = tuple(int(d) for d in tsdf_dims), float(tsdf_voxel)
         self.origin = tuple(-0.5 * self.voxel * (n - 1) for n in self.dims) if tsdf_origin is None else tuple(float(o) for o in tsdf_origin)
@@ -79,7 +82,11 @@ class TsdfReference:
         self.volume = self.model_depth = self.frame = self.spare = self._eye = None
         self.history_capacity, self.history, self._kf = int(history), None, None
         self.color = bool(color)
+        self.labels = bool(labels)
         self._more = {"color": True} if self.color else {}     # a plain model is made by the very calls it was made by before there was colour
+        if self.labels:
+            self._more["labels"] = True
+        self._last = None                                  # (depth, c2w, history slot or None) of the most recent fused frame
 
     def start(self, depth, aligner, t=None, rgb=None) -> None:
         self.volume = tsdf_utils.TsdfVolume(self.dims, self.voxel, self.origin, self.trunc, self.max_weight, device=depth.device, **self._more)
@@ -87,7 +94,7 @@ class TsdfReference:
         if self.history_capacity > 0:                      # the first keyframe's own pyramid, and history entry 0
             self._kf = self.prepare(depth, None)
             self.history = tsdf_utils.TsdfHistory(self.history_capacity, int(depth.shape[0]), int(depth.shape[1]), device=depth.device, **self._more)
-            self.history.add(depth, t, 0, np.eye(4), **self._with(rgb))
+            self._slot = self.history.add(depth, t, 0, np.eye(4), **self._with(rgb))
         self._fuse(depth, EYE, rgb)
 
     def aim(self, aligner) -> None:
@@ -108,25 +115,41 @@ class TsdfReference:
             old, self._kf = self._kf, cur
             self.spare = old.pyramid
         if self.history is not None:
-            self.history.add(depth, t, kf, np.eye(4) if is_kf else relative, **self._with(rgb))
+            self._slot = self.history.add(depth, t, kf, np.eye(4) if is_kf else relative, **self._with(rgb))
         self._fuse(depth, c2w, rgb)
         return old
+
+    def fuse_labels(self, ins) -> None:
+        """Votes ins i32[h, w] (device) into the label volume with the depth and the pose of the most recent fused frame, and keeps it in that frame's
+        slot of the history, so that a re-fusion votes it again.  Queued, not waited for."""
+        depth, c2w, slot = self._last
+        if self.history is not None:
+            depth = self.history.depths[slot]              # the ring's own copy: the caller's tensor may have moved on
+            self.history.set_labels(slot, ins)
+        self.volume.integrate_labels(depth, ins, self.K, c2w, self.near, self.far)
 
     def corrected(self, X, c2w) -> None:
         """The keyframes moved to X: the volume is fused again from the history at X[kf] @ rel, and the model image is cast at the corrected pose.
         All of it is queued; nothing waits."""
         self.volume.refuse(self.history, self.K, self.history.poses(X), self.near, self.far)
+        if self._last is not None:
+            self._last = (self._last[0], c2w, self._last[2])
         self._cast(c2w)
 
     def _fuse(self, depth, c2w, rgb=None) -> None:
         """Fuses a tracked frame at its pose and ray-casts the model there for the next frame: queued, not waited for."""
         self._hw = (int(depth.shape[0]), int(depth.shape[1]))
         self.volume.integrate(depth, self.K, c2w, self.near, self.far, **self._with(rgb))
+        self._last = (depth, c2w, getattr(self, "_slot", None))
         self._cast(c2w)
 
-    def render(self, c2w, normals: bool = False):
+    def render(self, c2w, normals: bool = False, labels: bool = False):
         """(depth f32[h, w], rgb u8[h, w, 3]) of the colour model from c2w, into new tensors: the model image of the frame loop is not touched.
-        `normals=True` (any volume): the normal image f32[h, w, 3] comes last, and the rgb only from a colour volume."""
+        `normals=True` (any volume): the normal image f32[h, w, 3] comes last, and the rgb only from a colour volume.  `labels=True` (a label volume):
+        the instance image i32[h, w] comes after them; rgb from a colour volume, normals when asked for."""
+        if labels:
+            more = dict(self._more, **({"normals": True} if normals else {}))
+            return self.volume.raycast(self.K, self._hw[0], self._hw[1], c2w, self.near, self.far, **more)
         if not normals:
             return self.volume.raycast(self.K, self._hw[0], self._hw[1], c2w, self.near, self.far, color=True)
         return self.volume.raycast(self.K, self._hw[0], self._hw[1], c2w, self.near, self.far, **({"color": True} if self.color else {}), normals=True)

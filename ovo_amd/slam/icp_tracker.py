@@ -42,7 +42,7 @@ class IcpTracker:
                  loop_min_overlap: float = 0.3, loop_max_rms: float = 0.02, loop_max_correction=(0.3, 10.0), loop_min_shift=(0.01, 0.2),
                  loop_max_keyframes: int = 256, model: str = "keyframe", tsdf_dims=(512, 512, 512), tsdf_voxel: float = 0.02, tsdf_origin=None,
                  tsdf_trunc=None, tsdf_max_weight: float = 64, tsdf_near: float = 0.05, tsdf_far=None, tsdf_history: int = 0,
-                 tsdf_color: bool = False) -> None:
+                 tsdf_color: bool = False, tsdf_labels: bool = False) -> None:
         """No GPU work happens here: buffers are made with the first frame.  The loop_* parameters are read and checked by `LoopCloser`, the
         tsdf_* parameters by `TsdfReference`, whichever mode is chosen.
 
@@ -74,7 +74,12 @@ class IcpTracker:
 
         tsdf_color (model="tsdf" only): the volume also fuses the colour image of every tracked frame (1 GB more at 512^3,
         0.84 MB a frame more in the history), `render_model` shows the model in colour and `extract_mesh(colors=True)` puts it on the mesh.
-        Colour takes no part in the alignment: the model image stays the depth-only ray cast, and poses are bit-identical with it on or off."""
+        Colour takes no part in the alignment: the model image stays the depth-only ray cast, and poses are bit-identical with it on or off.
+
+        tsdf_labels (model="tsdf" only): a label array beside the volume (1 GB more at 512^3, 1.12 MB a frame more in the
+        history).  The frame loop never touches it: `fuse_labels(ins)` votes a keyframe's instance image (`OVO.instance_image`) into it,
+        `render_model(labels=True)` and `extract_mesh(labels=True)` read it back, `volume.remap_labels(OVO.last_instance_table)` follows the map's
+        merges.  Poses, the volume and the model image are bit-identical with it on or off."""
         self.K = np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, dtype=np.float32)[:3, :3].copy()
         self.levels, self.iters = int(levels), tuple(int(i) for i in iters)
         if not 1 <= self.levels <= U.MAX_LEVELS or len(self.iters) != self.levels:
@@ -100,8 +105,11 @@ class IcpTracker:
         self.tsdf_color = bool(tsdf_color)
         if self.tsdf_color and self.model != "tsdf":
             raise ValueError("IcpTracker: tsdf_color fuses colour into the volume and needs model='tsdf'")
+        self.tsdf_labels = bool(tsdf_labels)
+        if self.tsdf_labels and self.model != "tsdf":
+            raise ValueError("IcpTracker: tsdf_labels votes instance labels into the volume and needs model='tsdf'")
         tsdf = TsdfReference(self._prepare, self.K, self.max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far,
-                             history=self.tsdf_history, color=self.tsdf_color)
+                             history=self.tsdf_history, color=self.tsdf_color, **({"labels": True} if self.tsdf_labels else {}))
         self.tsdf_trunc, self.tsdf_far = tsdf.trunc, tsdf.far
         self._ref = tsdf if self.model == "tsdf" else KeyframeReference(self._prepare)
         self.device = device
@@ -186,6 +194,24 @@ class IcpTracker:
                 self._row = self._keyframes[n]
                 ref.corrected(X, self._c2w)                # model="tsdf": the volume fused again from its history, the model image cast again
 
+    def fuse_labels(self, ins) -> None:
+        """tsdf_labels: votes the instance image ins (i32 [h, w] of the depth's size, an array or a tensor; negative = no label) into the label volume
+        with the depth and the pose of the most recent fused frame -- call it after `process_image_rgbd` of a keyframe, once its instances are known.
+        With a history the image is kept in that frame's slot and voted again by a re-fusion.  Queued on the current stream; never waits."""
+        if self.closed:
+            raise RuntimeError("IcpTracker: shut down")
+        if not self.tsdf_labels:
+            raise ValueError("IcpTracker.fuse_labels: the model holds no labels (build the tracker with model='tsdf', tsdf_labels=True)")
+        if self.volume is None or self._ref._last is None:
+            raise ValueError("IcpTracker.fuse_labels: no frame fused yet (the volume is made with the first frame)")
+        hw = tuple(int(x) for x in self._ref._last[0].shape)
+        if isinstance(ins, np.ndarray) and ins.dtype == np.int32:
+            ins = torch.from_numpy(np.ascontiguousarray(ins))
+        if not isinstance(ins, torch.Tensor) or ins.dtype != torch.int32 or tuple(ins.shape) != hw:
+            got = f"{ins.dtype} {tuple(ins.shape)}" if isinstance(ins, (torch.Tensor, np.ndarray)) else type(ins).__name__
+            raise ValueError(f"IcpTracker.fuse_labels: ins must be an i32 array or tensor {list(hw)} (got {got})")
+        self._ref.fuse_labels(ins.to(device=self.device).contiguous())
+
     def _need_frame(self) -> None:
         if self._row is None:
             raise RuntimeError("IcpTracker: no frame processed yet")
@@ -212,25 +238,32 @@ class IcpTracker:
         """model="tsdf": `TsdfVolume.extract_mesh(**kw)` of the fused model, (vertices f32[V, 3], faces i32[T, 3]) on the device, in the tracker's
         frame (that of the first camera: a world_ref is applied by whoever holds it, e.g. `OVO.semantic_mesh(transform=)`).  With tsdf_color,
         `colors=True` adds rgb u8[V, 3], which `OVO.semantic_mesh(rgb=)` carries into the PLY.  `normals=True` adds vertex normals f32[V, 3] last
-        (the volume's gradient), which `OVO.semantic_mesh(normals=)` carries likewise."""
+        (the volume's gradient), which `OVO.semantic_mesh(normals=)` carries likewise.  With tsdf_labels, `labels=True` adds
+        vertex instance ids i32[V] after them, which `OVO.semantic_mesh(instance=)` takes in place of its 5-NN transfer."""
         if self.model != "tsdf":
             raise ValueError("IcpTracker.extract_mesh: model='keyframe' keeps no fused model (build the tracker with model='tsdf')")
         if self.volume is None:
             raise ValueError("IcpTracker.extract_mesh: no frame processed yet (the volume is made with the first frame)")
         return self.volume.extract_mesh(**kw)
 
-    def render_model(self, c2w=None, normals: bool = False):
+    def render_model(self, c2w=None, normals: bool = False, labels: bool = False):
         """tsdf_color: the fused model seen from `c2w` (None: the last good pose), in the tracker's frame: (depth f32[h, w], rgb u8[h, w, 3]) on
         the device, new tensors; the depth has the bits `model_depth` has at that pose.  Queued on the current stream, not waited for.
         `normals=True` (any model="tsdf" tracker): (depth, normals f32[h, w, 3]), or (depth, rgb, normals) with tsdf_color --
-        unit normals in the tracker's frame from the volume's gradient, zeros where there is no surface; `tsdf_utils.shade_normals` makes a picture of them."""
+        unit normals in the tracker's frame from the volume's gradient, zeros where there is no surface; `tsdf_utils.shade_normals` makes a picture of them.
+        `labels=True` (tsdf_labels) appends the instance image i32[h, w]: an occlusion-correct, hole-free view of the labels, -1 where
+        there is no surface or no label -- (depth, ins), (depth, rgb, ins), (depth, normals, ins) or (depth, rgb, normals, ins)."""
+        if labels and not self.tsdf_labels:
+            raise ValueError("IcpTracker.render_model: the model holds no labels (build the tracker with model='tsdf', tsdf_labels=True)")
         if normals and self.model != "tsdf":
             raise ValueError("IcpTracker.render_model: model='keyframe' keeps no fused model (build the tracker with model='tsdf')")
-        if not normals and not self.tsdf_color:
+        if not normals and not labels and not self.tsdf_color:
             raise ValueError("IcpTracker.render_model: the model holds no colour (build the tracker with model='tsdf', tsdf_color=True)")
         if self.volume is None:
             raise ValueError("IcpTracker.render_model: no frame processed yet (the volume is made with the first frame)")
         pose = self._c2w if c2w is None else np.asarray(c2w.detach().cpu() if isinstance(c2w, torch.Tensor) else c2w, dtype=np.float32)
+        if labels:
+            return self._ref.render(pose, normals=bool(normals), labels=True)
         return self._ref.render(pose, normals=True) if normals else self._ref.render(pose)
 
     def shutdown(self) -> None:

@@ -3,7 +3,9 @@ ray-cast back into a depth image from any pose (`ovo_tsdf_raycast`) and turned i
 csrc/tsdf.hip, csrc/mesh.hip, DESIGN.md sections 17 and 18.  With `color=True` a second array holds the fused colour of every voxel, and the
 same three steps carry it along (`ovo_tsdf_integrate_color`, `ovo_tsdf_raycast_color`, `ovo_tsdf_mesh_colors`: section 20).  The gradient of F is the surface
 normal: `raycast(normals=True)` and `extract_mesh(normals=True)` return it (`ovo_tsdf_raycast_normals`, `ovo_tsdf_mesh_normals`: section 21) and `shade_normals` makes a lit picture of it.  `TsdfHistory` keeps the depth images a volume was fused from, and
-`TsdfVolume.refuse` fuses it again from them at other poses -- what a loop closure needs (section 19).  `frustum_box`, `rigid_inverse_f32` and `volume_desc` / `camera_desc` are pure numpy / ctypes and need no GPU."""
+`TsdfVolume.refuse` fuses it again from them at other poses -- what a loop closure needs (section 19).  With `labels=True` a label array (L, C) beside the
+volume takes the instance images of the keyframes as votes (`integrate_labels`), follows the map's instance merges (`remap_labels`), and `raycast(labels=True)` /
+`extract_mesh(labels=True)` read it back (`ovo_tsdf_integrate_labels`, `ovo_tsdf_labels_remap`, `ovo_tsdf_raycast_labels`, `ovo_tsdf_mesh_labels`: section 22).  `frustum_box`, `rigid_inverse_f32` and `volume_desc` / `camera_desc` are pure numpy / ctypes and need no GPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -75,10 +77,12 @@ def frustum_box(dims: Sequence[int], voxel: float, origin: Sequence[float], trun
 class TsdfVolume:
     """A dense TSDF volume on the device: `vol` is f32[nz, ny, nx, 2] = (F, W), zero = unobserved.  dims = (nx, ny, nz); voxel (i, j, k) sits at
     origin + voxel * (i, j, k) in the frame the poses are given in.  512^3 is 1 GB.  `color=True`: `col` is int16[nz, ny, nx, 4] holding the bits of
-    u16 (R, G, B, spare), a channel = level * 256, zero = unobserved; it shares W with `vol`, and every `integrate` then needs `rgb`.  1 GB more."""
+    u16 (R, G, B, spare), a channel = level * 256, zero = unobserved; it shares W with `vol`, and every `integrate` then needs `rgb`.  1 GB more.
+    `labels=True`: `lab` is int32[nz, ny, nx, 2] = (L, C), L = instance id + 1 (0: none), C the label's confidence count, zero = no label; it is
+    voted on by `integrate_labels` alone, never by `integrate`.  1 GB more."""
 
     def __init__(self, dims: Sequence[int], voxel: float, origin: Sequence[float], trunc: float, max_weight: float = 64, device="cuda",
-                 color: bool = False) -> None:
+                 color: bool = False, labels: bool = False) -> None:
         self.dims = tuple(int(d) for d in dims)
         self.voxel, self.trunc, self.max_weight = float(voxel), float(trunc), float(max_weight)
         self.origin = tuple(float(o) for o in origin)
@@ -97,11 +101,54 @@ class TsdfVolume:
             if int(L.load().ovo_tsdf_color_bytes(C.byref(self.desc))) != nbytes:
                 raise L.OvoHipError("TsdfVolume: the library's colour volume is not 8 bytes a voxel")
             self.col = torch.zeros((nz, ny, nx, 4), dtype=torch.int16, device=device)
+        self.lab = None
+        if labels:
+            if int(L.load().ovo_tsdf_label_bytes(C.byref(self.desc))) != nbytes:
+                raise L.OvoHipError("TsdfVolume: the library's label volume is not 8 bytes a voxel")
+            self.lab = torch.zeros((nz, ny, nx, 2), dtype=torch.int32, device=device)
 
     def reset(self) -> None:
         self.vol.zero_()
         if self.col is not None:
             self.col.zero_()
+        if getattr(self, "lab", None) is not None:
+            self.lab.zero_()
+
+    def _labelled(self, what: str) -> torch.Tensor:
+        lab = getattr(self, "lab", None)
+        if lab is None:
+            raise L.OvoHipError(f"TsdfVolume.{what}: needs a volume made with labels=True")
+        return lab
+
+    def integrate_labels(self, depth: torch.Tensor, ins: torch.Tensor, K, c2w, near: float = 0.05, far: float = 10.0, box: Optional[Box] = None,
+                         max_count: int = 255) -> Optional[Box]:
+        """Votes the instance image ins i32[h, w] (device; negative = no label) of the frame depth f32[h, w] seen from `c2w` into `lab` on the current
+        stream (`ovo_tsdf_integrate_labels`): a voxel that `integrate` would update from this depth with a sample f < 1 takes its pixel's id as a vote.
+        `vol` is neither read nor written.  `box=None` visits `frustum_box(...)`, as `integrate` does; returns the box (None: nothing queued)."""
+        lab = self._labelled("integrate_labels")
+        L.dev(depth, torch.float32, "depth")
+        L.dev(ins, torch.int32, "ins")
+        if depth.dim() != 2 or tuple(ins.shape) != tuple(depth.shape):
+            raise L.OvoHipError(f"TsdfVolume.integrate_labels: depth and ins must both be [h, w] (got {tuple(depth.shape)} and {tuple(ins.shape)})")
+        h, w = int(depth.shape[0]), int(depth.shape[1])
+        if box is None:
+            box = self.frustum_box(K, h, w, c2w, near, far)
+            if box is None:
+                return None
+        cam = camera_desc(K, h, w, c2w, near, far)
+        lo, hi = (C.c_int32 * 3)(*(int(x) for x in box[0])), (C.c_int32 * 3)(*(int(x) for x in box[1]))
+        L.check(L.load().ovo_tsdf_integrate_labels(L.ptr(lab), C.byref(self.desc), L.ptr(depth), L.ptr(ins), C.byref(cam), lo, hi, int(max_count), L.stream()))
+        return box
+
+    def remap_labels(self, table: torch.Tensor) -> None:
+        """Every voxel's instance id i becomes table[i] (i32[n] on the device: `OVO.last_instance_table`); a negative entry clears the voxel, an id at or
+        above n stays.  Counts are kept.  Queued on the current stream (`ovo_tsdf_labels_remap`)."""
+        lab = self._labelled("remap_labels")
+        L.dev(table, torch.int32, "table")
+        if table.dim() != 1:
+            raise L.OvoHipError(f"TsdfVolume.remap_labels: table must be i32 [n] (got {tuple(table.shape)})")
+        if table.numel() > 0:
+            L.check(L.load().ovo_tsdf_labels_remap(L.ptr(lab), C.byref(self.desc), L.ptr(table), int(table.numel()), L.stream()))
 
     def _rgb(self, rgb, shape, what: str):
         """The colour image of a call, checked against the volume's kind -- u8 on the device for a colour volume, None for a plain one -- and, when
@@ -147,7 +194,8 @@ class TsdfVolume:
         """Fuses the volume again from the frames of `history` at `poses` (one per live entry, oldest first: `history.poses(X)`): `reset()`, then
         one `integrate` (`ovo_tsdf_integrate`, the single-frame kernel) per entry in the history's order.  Queues work and never waits.
         40 us a frame on the device at 456 x 616 into 512^3.  A colour volume fuses its colour again too, from the
-        history's `colors` (a history made with color=True)."""
+        history's `colors` (a history made with color=True).  A label volume then votes every live entry that has labels (`TsdfHistory.set_labels`)
+        again, in the history's order, at its new pose: `reset()` has zeroed `lab`."""
         entries = history.entries()
         if len(entries) != len(poses):
             raise L.OvoHipError(f"TsdfVolume.refuse: {len(poses)} poses for {len(entries)} frames of the history")
@@ -158,6 +206,10 @@ class TsdfVolume:
         for e, c2w in zip(entries, poses):
             rgb = {"rgb": history.colors[e["slot"]]} if color else {}      # (a plain volume is called as before colour existed: stand-ins take no `rgb`)
             self.integrate(history.depths[e["slot"]], K, c2w, near, far, **rgb)
+        if getattr(self, "lab", None) is not None and getattr(history, "labels", None) is not None:
+            for e, c2w in zip(entries, poses):
+                if history.has_labels[e["slot"]]:
+                    self.integrate_labels(history.depths[e["slot"]], history.labels[e["slot"]], K, c2w, near, far)
 
     def _image(self, given: Optional[torch.Tensor], shape: tuple, dtype: torch.dtype, name: str) -> torch.Tensor:
         """An output image of a ray cast: `given`, checked to be on the device with this shape and dtype, or a new one."""
@@ -168,12 +220,19 @@ class TsdfVolume:
         return out
 
     def raycast(self, K, h: int, w: int, c2w, near: float, far: float, dz: Optional[float] = None, out: Optional[torch.Tensor] = None,
-                color: bool = False, out_rgb: Optional[torch.Tensor] = None, normals: bool = False, out_normals: Optional[torch.Tensor] = None):
+                color: bool = False, out_rgb: Optional[torch.Tensor] = None, normals: bool = False, out_normals: Optional[torch.Tensor] = None,
+                labels: bool = False, min_count: int = 1, out_ins: Optional[torch.Tensor] = None):
         """The model's depth image f32[h, w] from `c2w` on the current stream (0 = no surface); dz defaults to trunc / 2.  `color=True` (a colour
         volume only): (depth, rgb u8[h, w, 3]), the colour blended at the hit, (0, 0, 0) where there is none; the depth has the same bits.
         `normals=True` appends the normal image f32[h, w, 3] (`ovo_tsdf_raycast_normals`): the unit gradient of F at the hit, in
-        the volume's frame, pointing into free space, zeros where there is no surface -- (depth, normals) or (depth, rgb, normals), same bits."""
+        the volume's frame, pointing into free space, zeros where there is no surface -- (depth, normals) or (depth, rgb, normals), same bits.
+        `labels=True` (a label volume only) appends the instance image i32[h, w] (`ovo_tsdf_raycast_labels`): the id of the voxel nearest
+        to the hit if its count is >= min_count, else -1; -1 where there is no surface.  Alone it is one launch, which writes the depth too; beside `color` / `normals` it is a second launch of the march, with the same depth bits."""
         dz = self.trunc / 2 if dz is None else float(dz)
+        if labels:
+            self._labelled("raycast")
+        if out_ins is not None and not labels:
+            raise L.OvoHipError("TsdfVolume.raycast: out_ins is only written with labels=True")
         if color and self.col is None:
             raise L.OvoHipError("TsdfVolume.raycast: color=True needs a volume made with color=True")
         if out_rgb is not None and not color:
@@ -190,16 +249,29 @@ class TsdfVolume:
                               (True, False): ("ovo_tsdf_raycast_color", (vol, col, desc, cam, dz, d, c), (out, out_rgb)),
                               (False, True): ("ovo_tsdf_raycast_normals", (vol, None, desc, cam, dz, d, None, n), (out, out_normals)),
                               (True, True): ("ovo_tsdf_raycast_normals", (vol, col, desc, cam, dz, d, c, n), (out, out_rgb, out_normals))}[bool(color), bool(normals)]
+        if labels and not (color or normals):               # the label form writes the depth too: one launch
+            out_ins = self._image(out_ins, (h, w), torch.int32, "out_ins")
+            L.check(L.load().ovo_tsdf_raycast_labels(vol, L.ptr(self.lab), desc, cam, dz, int(min_count), d, L.ptr(out_ins), L.stream()))
+            return (out, out_ins)
         L.check(getattr(L.load(), name)(*args, L.stream()))
+        if labels:
+            out_ins = self._image(out_ins, (h, w), torch.int32, "out_ins")
+            L.check(L.load().ovo_tsdf_raycast_labels(vol, L.ptr(self.lab), desc, cam, dz, int(min_count), d, L.ptr(out_ins), L.stream()))
+            result += (out_ins,)
         return result
 
-    def extract_mesh(self, box: Optional[Box] = None, min_weight: float = 1.0, colors: bool = False, normals: bool = False):
+    def extract_mesh(self, box: Optional[Box] = None, min_weight: float = 1.0, colors: bool = False, normals: bool = False, labels: bool = False,
+                     min_count: int = 1):
         """The surface inside the index box (None: the whole volume) as a welded triangle mesh on the device: (vertices f32[V, 3] in the volume's
         frame, faces i32[T, 3]); marching tetrahedra over the cells whose eight corners have W >= min_weight (include/ovo_hip.h states the
         contract).  Normals point into free space.  One host wait, for (V, T); V = 0 returns empty tensors and queues no second call.
         `colors=True` (a colour volume only): (vertices, faces, rgb u8[V, 3]), each vertex's colour blended between the two ends of its edge.
         `normals=True` appends vertex normals f32[V, 3] (`ovo_tsdf_mesh_normals`): the unit gradient of F blended between the two
-        ends of the vertex's edge, in the volume's frame; the zero vector where the gradient vanishes.  V = 0: an empty [0, 3] tensor and no call."""
+        ends of the vertex's edge, in the volume's frame; the zero vector where the gradient vanishes.  V = 0: an empty [0, 3] tensor and no call.
+        `labels=True` (a label volume only) appends vertex instance ids i32[V] (`ovo_tsdf_mesh_labels`): the id of the nearer end of
+        the vertex's edge if its count is >= min_count, else the other end's, else -1 -- what `OVO.semantic_mesh(instance=)` takes."""
+        if labels:
+            self._labelled("extract_mesh")
         if colors and self.col is None:
             raise L.OvoHipError("TsdfVolume.extract_mesh: colors=True needs a volume made with color=True")
         box = ((0, 0, 0), self.dims) if box is None else box
@@ -230,6 +302,12 @@ class TsdfVolume:
             if V > 0:
                 L.check(lib.ovo_tsdf_mesh_normals(L.ptr(self.vol), C.byref(self.desc), lo, hi, float(min_weight), L.ptr(ws), nbytes, L.ptr(nrm), V, L.stream()))
             result += (nrm,)
+        if labels:
+            ins = torch.empty((V,), dtype=torch.int32, device=dev)
+            if V > 0:
+                L.check(lib.ovo_tsdf_mesh_labels(L.ptr(self.vol), L.ptr(self.lab), C.byref(self.desc), lo, hi, float(min_weight), L.ptr(ws), nbytes, int(min_count),
+                                                 L.ptr(ins), V, L.stream()))
+            result += (ins,)
         return result
 
 
@@ -238,14 +316,18 @@ class TsdfHistory:
     f32[capacity, h, w] on the device -- f32, the exact bits that were fused live -- and, on the host, each entry's time stamp, the index `kf`
     of the keyframe it hangs on and `rel` = inv(kf_c2w) @ c2w in f64 (the exact identity for a keyframe itself).  When the ring is full the
     oldest entry is overwritten: after the next re-fusion the model no longer holds that frame.  1.12 MB a frame at 456 x 616, 1.15 GB at 1024.
-    `color=True`: a ring `colors` u8[capacity, h, w, 3] beside it, slot for slot (0.84 MB a frame more), and `add` needs `rgb`."""
+    `color=True`: a ring `colors` u8[capacity, h, w, 3] beside it, slot for slot (0.84 MB a frame more), and `add` needs `rgb`.
+    `labels=True`: a ring `labels` i32[capacity, h, w] beside it (1.12 MB a frame more) and a flag per slot, `has_labels`: `add` clears the slot's
+    flag, `set_labels(slot, ins)` fills the slot after the fact -- instance images exist for keyframes only, and later than the frame."""
 
-    def __init__(self, capacity: int, h: int, w: int, device="cuda", color: bool = False) -> None:
+    def __init__(self, capacity: int, h: int, w: int, device="cuda", color: bool = False, labels: bool = False) -> None:
         self.capacity, self.h, self.w = int(capacity), int(h), int(w)
         if not 1 <= self.capacity <= MAX_HISTORY:
             raise ValueError(f"TsdfHistory: capacity must be 1 .. {MAX_HISTORY}")
         self.depths = torch.zeros((self.capacity, self.h, self.w), dtype=torch.float32, device=device)
         self.colors = torch.zeros((self.capacity, self.h, self.w, 3), dtype=torch.uint8, device=device) if color else None
+        self.labels = torch.zeros((self.capacity, self.h, self.w), dtype=torch.int32, device=device) if labels else None
+        self.has_labels = [False] * self.capacity
         self._entries: list = []                           # live entries, oldest first
         self._next = 0                                     # the slot the next frame is written to
 
@@ -265,11 +347,23 @@ class TsdfHistory:
         self.depths[slot].copy_(depth)
         if rgb is not None:
             self.colors[slot].copy_(rgb)
+        self.has_labels[slot] = False                      # whatever instance image the slot held belonged to the frame it held
         if len(self._entries) == self.capacity:
             self._entries.pop(0)                           # it held `slot`
         self._entries.append({"slot": slot, "t": t, "kf": int(kf), "rel": np.array(rel, dtype=np.float64)})
         self._next = (slot + 1) % self.capacity
         return slot
+
+    def set_labels(self, slot: int, ins: torch.Tensor) -> None:
+        """Copies ins i32[h, w] into slot `slot` (what `add` returned for the frame) on the current stream and marks the slot as labelled."""
+        if self.labels is None:
+            raise ValueError("TsdfHistory.set_labels: needs a history made with labels=True")
+        if not any(e["slot"] == int(slot) for e in self._entries):
+            raise ValueError(f"TsdfHistory.set_labels: slot {slot} holds no live frame")
+        if tuple(ins.shape) != (self.h, self.w) or ins.dtype != torch.int32:
+            raise ValueError(f"TsdfHistory.set_labels: ins must be i32 [{self.h}, {self.w}] (got {ins.dtype} {tuple(ins.shape)})")
+        self.labels[int(slot)].copy_(ins)
+        self.has_labels[int(slot)] = True
 
     def entries(self) -> list:
         return list(self._entries)
