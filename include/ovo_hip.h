@@ -1067,6 +1067,33 @@ int ovo_tsdf_mesh_labels(const void *vol, const void *lab, const ovo_tsdf_volume
                          const void *ws, size_t ws_bytes, int32_t min_count, int32_t *ins_out, int64_t V, ovo_stream_t stream);
 int ovo_tsdf_labels_remap(void *lab, const ovo_tsdf_volume_t *desc, const int32_t *table, int32_t n_table, ovo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The volume read at arbitrary points (still ABI v23: an entry point added, none changed; restated in
+ * tests/tsdf_sample_restatement.py).  points: device f32 [n][3], dense, in the volume's frame.  One launch, one thread a point.
+ *
+ * Per point p every step is one f32 IEEE operation in the order written (no FMA chain anywhere, so numpy in f32 reproduces every bit):
+ *   cell      g[a] = (p[a] - origin[a]) / voxel, b[a] = floorf(g[a]), t[a] = g[a] - b[a].  INSIDE iff 0 <= b[a] <= n[a] - 2 on all three axes (NaN
+ *             and the infinities fail); no float becomes an index, and no address is formed, before that test has passed.
+ *   seen      SEEN iff INSIDE and all eight corners b + {0, 1}^3 have W > 0 (the ray cast's validity).
+ *   not SEEN  f_out = 2.0f (outside [-1, 1], fixed bits), normals_out three +0.0f, rgb_out (0, 0, 0), ins_out -1.
+ *   f_out     the trilinear blend of F with lerp(a, b, t) = a + t * (b - a), along x, then y, then z: ovo_tsdf_raycast's sample.
+ *   normals   unit() of the trilinear blend, per component and in the same order, of grad(corner; W > 0) over the eight corners:
+ *             ovo_tsdf_raycast_normals' expressions on this point's (b, t).
+ *   rgb       per channel rint(clamp(blend / 256, 0, 255)) of the trilinear blend of the eight corners' channels: ovo_tsdf_raycast_color's.
+ *   ins, label_mode 0 (nearest): the corner b + (t[a] >= 0.5f) answers L - 1 if L > 0 and C >= min_count, else -1: ovo_tsdf_raycast_labels' rule.
+ *   ins, label_mode 1 (vote): a corner is eligible iff L > 0 and C >= min_count; for every distinct L among the eligible corners the sum of its C,
+ *             as int64; the largest sum wins; among tied labels the one the nearest corner holds, if that corner is eligible and holds one of
+ *             them, else the smallest L; -1 if no corner is eligible.  Integers only.
+ * A col or lab given without its output is ignored.  n == 0 returns OVO_OK and queues nothing.  Nothing is written beyond index n - 1, and no
+ * volume is written at all.
+ *
+ * OVO_E_ARG, nothing queued and nothing written: a null vol, desc or f_out; a null points with n > 0; n < 0 or n > 2^31 - 1; a descriptor the other
+ * entry points refuse; a vol, col or lab not 16-byte aligned (points and the f32 / i32 outputs: 4); rgb_out without col; ins_out without lab;
+ * label_mode not 0 or 1; min_count outside 1 .. 2^30. */
+int ovo_tsdf_sample_points(const void *vol, const void *col /* may be NULL */, const void *lab /* may be NULL */, const ovo_tsdf_volume_t *desc,
+                           const float *points, int64_t n, int32_t label_mode, int32_t min_count, float *f_out, float *normals_out /* or NULL */,
+                           uint8_t *rgb_out /* or NULL */, int32_t *ins_out /* or NULL */, ovo_stream_t stream);
+
 
 /* =============================================================================================
  * The keyframe chain without host round trips (MI355X extension of a6 / a9; what the reference does with a `.sum()` / vstack

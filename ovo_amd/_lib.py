@@ -283,6 +283,7 @@ _SIGNATURES = {
     "ovo_tsdf_raycast_labels": (_I32, [_P, _P, C.POINTER(TsdfVolume), C.POINTER(TsdfCamera), _F32, _I32, _P, _P, _P]),
     "ovo_tsdf_mesh_labels": (_I32, [_P, _P, C.POINTER(TsdfVolume), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F32, _P, _SZ, _I32, _P, _I64, _P]),
     "ovo_tsdf_labels_remap": (_I32, [_P, C.POINTER(TsdfVolume), _P, _I32, _P]),
+    "ovo_tsdf_sample_points": (_I32, [_P, _P, _P, C.POINTER(TsdfVolume), _P, _I64, _I32, _I32, _P, _P, _P, _P, _P]),
     "ovo_sam_i2t_attention": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_sam_t2i_attention": (_I32, [_P, _P, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _F32, _P]),
     "ovo_paint_segmap": (_I32, [_P, _I32, _I64, _P, _P]),

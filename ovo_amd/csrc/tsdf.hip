@@ -13,6 +13,9 @@
 //                                integers; `vol` is neither read nor written
 //   ovo_tsdf_raycast_labels      k_tsdf_raycast<false, false, true>   the same march; at a hit the label of the one voxel nearest to the surface point
 //   ovo_tsdf_labels_remap        k_tsdf_labels_remap   a grid-stride pass over voxel pairs: L <- table[L - 1] + 1, stored only where it changes
+//   ovo_tsdf_sample_points       k_tsdf_sample_points<NORMALS, COLOR, LABELS>    the volume read at arbitrary points: one launch, one
+//                                thread a point, grid-stride; the ray cast's sample, gradient, colour and label expressions on a GIVEN position, and
+//                                a count-weighted vote of the eight corners' labels; reads only
 // The volume is float2 [nz][ny][nx] = (F, W), x fastest; all-zero bytes are "unobserved".  The colour volume is uint2 [nz][ny][nx] (four u16: R, G, B,
 // spare) with the volume's indexing.  No atomics, no cross-thread traffic: every result is a pure function of the inputs, bit-equal from run to run
 // and whatever OVO_TSDF_GRID_CAP says (it only changes which workgroup visits a voxel).
@@ -394,6 +397,110 @@ __global__ void __launch_bounds__(256) k_tsdf_labels_remap(int2 *__restrict__ la
     }
 }
 
+// ---- the volume read at arbitrary points.  One thread a point, grid-stride.  The blends are stated HERE a second time, on a given
+// (b, t) instead of a ray's sample k: tsdf_cell, tsdf_cell_color and tsdf_cell_gradient form their position from the ray inside themselves, and the
+// ray-cast kernels keep their instruction streams only if those stay as they are.  The expressions are the same ones, in the same order.
+// The vote of eight (L, C) corners (label_mode 1, LABELS == 2): a corner is eligible iff L > 0 && C >= min_count; every eligible corner's label gets the int64 sum
+// of the counts of the eligible corners that hold it; the largest sum wins; among tied labels the one the nearest corner `near` holds if that corner
+// is eligible and its label is one of them, else the smallest L.  Returns L - 1, or -1 when no corner is eligible.
+__device__ __forceinline__ int tsdf_vote8(const int2 e[8], int near, int min_count) {
+    int64_t best = 0, near_sum = 0;                        // an eligible corner's own sum is >= its C >= min_count >= 1
+    int L = 0, near_L = 0;
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        const bool ok = e[a].x > 0 && e[a].y >= min_count;
+        int64_t sum = 0;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) sum += ok && e[b].x == e[a].x && e[b].y >= min_count ? (int64_t)e[b].y : 0;
+        if (sum > best || (sum == best && ok && e[a].x < L)) { best = sum; L = e[a].x; }      // the largest sum; among equals the smallest L
+        if (a == near) { near_sum = sum; near_L = e[a].x; }                                    // (a compile-time a against a run-time near: no indexed register)
+    }
+    if (best == 0) return -1;
+    return (near_sum == best ? near_L : L) - 1;
+}
+
+// A pointer that a form does not use (`normals_out` without NORMALS, `col` and `rgb_out` without COLOR, `lab` and `ins_out` without LABELS) is never
+// touched.  Every address into the three volumes is base + {0, 1} per axis of a cell that passed the INSIDE test -- bf[a] in [0, n[a] - 2], tested on
+// the floats before any of them becomes an index -- except the gradient's neighbours, which tsdf_gradient tests against [0, n) itself.  Every output
+// is written at index i < n only.
+// LABELS: 0 none, 1 the nearest corner's label (one 8-byte load), 2 the vote (eight): a form of its own each, since the vote's sums cost registers.
+template <bool NORMALS, bool COLOR, int LABELS>
+__global__ void __launch_bounds__(256) k_tsdf_sample_points(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const int2 *__restrict__ lab, const TsdfVol v,
+                                                            const float *__restrict__ points, int64_t n, int min_count, float *__restrict__ f_out,
+                                                            float *__restrict__ normals_out, uint8_t *__restrict__ rgb_out, int32_t *__restrict__ ins_out) {
+    const float org[3] = {v.ox, v.oy, v.oz};
+    const int dim[3] = {v.nx, v.ny, v.nz};
+    const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float bf[3], tt[3];
+        bool inside = true;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float g = (points[3 * i + a] - org[a]) / v.voxel;
+            bf[a] = floorf(g);
+            tt[a] = g - bf[a];
+            inside &= (bf[a] >= 0.0f) & (bf[a] <= (float)(dim[a] - 2));      // (NaN and the infinities fail)
+        }
+        float f = 2.0f, nrm[3] = {0.0f, 0.0f, 0.0f}, rgbf[3] = {0.0f, 0.0f, 0.0f};
+        int label = -1;
+        if (inside) {                                      // only now does a float become an index
+            const int b[3] = {(int)bf[0], (int)bf[1], (int)bf[2]};
+            const int64_t at = ((int64_t)b[2] * v.ny + b[1]) * v.nx + b[0];
+            const float2 *p = vol + at;
+            const float2 c000 = p[0], c100 = p[1], c010 = p[sy], c110 = p[sy + 1], c001 = p[sz], c101 = p[sz + 1], c011 = p[sz + sy], c111 = p[sz + sy + 1];
+            // the blend is formed whether or not the cell is seen and then selected, so that a corner's F travels with its W in one load, not in a
+            // second round of loads behind the test (an unobserved corner's F is only arithmetic on whatever bits it holds)
+            const float blend = lerp1(lerp1(lerp1(c000.x, c100.x, tt[0]), lerp1(c010.x, c110.x, tt[0]), tt[1]),
+                                      lerp1(lerp1(c001.x, c101.x, tt[0]), lerp1(c011.x, c111.x, tt[0]), tt[1]), tt[2]);
+            const bool seen = (c000.y > 0.0f) & (c100.y > 0.0f) & (c010.y > 0.0f) & (c110.y > 0.0f) & (c001.y > 0.0f) & (c101.y > 0.0f) & (c011.y > 0.0f) & (c111.y > 0.0f);
+            f = seen ? blend : 2.0f;
+            if (seen) {
+                if (NORMALS) {
+                    const float Fc[8] = {c000.x, c100.x, c010.x, c110.x, c001.x, c101.x, c011.x, c111.x};
+                    float gc[8][3], g[3];                  // corner x + 2 y + 4 z
+#pragma unroll
+                    for (int cn = 0; cn < 8; ++cn) tsdf_gradient(vol, v, b[0] + (cn & 1), b[1] + (cn >> 1 & 1), b[2] + (cn >> 2), Fc[cn], TsdfSeen{}, gc[cn]);
+#pragma unroll
+                    for (int a = 0; a < 3; ++a)
+                        g[a] = lerp1(lerp1(lerp1(gc[0][a], gc[1][a], tt[0]), lerp1(gc[2][a], gc[3][a], tt[0]), tt[1]),
+                                     lerp1(lerp1(gc[4][a], gc[5][a], tt[0]), lerp1(gc[6][a], gc[7][a], tt[0]), tt[1]), tt[2]);
+                    tsdf_unit(g, nrm);
+                }
+                if (COLOR) {
+                    const uint2 *q = col + at;
+                    const uint2 q000 = q[0], q100 = q[1], q010 = q[sy], q110 = q[sy + 1], q001 = q[sz], q101 = q[sz + 1], q011 = q[sz + sy], q111 = q[sz + sy + 1];
+#pragma unroll
+                    for (int ch = 0; ch < 3; ++ch)
+                        rgbf[ch] = lerp1(lerp1(lerp1(color_channel(q000, ch), color_channel(q100, ch), tt[0]), lerp1(color_channel(q010, ch), color_channel(q110, ch), tt[0]), tt[1]),
+                                         lerp1(lerp1(color_channel(q001, ch), color_channel(q101, ch), tt[0]), lerp1(color_channel(q011, ch), color_channel(q111, ch), tt[0]), tt[1]),
+                                         tt[2]);
+                }
+                if (LABELS) {
+                    const int ni = tt[0] >= 0.5f ? 1 : 0, nj = tt[1] >= 0.5f ? 1 : 0, nk = tt[2] >= 0.5f ? 1 : 0;      // the nearest corner
+                    const int2 *l = lab + at;
+                    if (LABELS == 2) {
+                        const int2 e[8] = {l[0], l[1], l[sy], l[sy + 1], l[sz], l[sz + 1], l[sz + sy], l[sz + sy + 1]};
+                        label = tsdf_vote8(e, ni + 2 * nj + 4 * nk, min_count);
+                    } else {
+                        const int2 e = l[nk * sz + nj * sy + ni];
+                        if (e.x > 0 && e.y >= min_count) label = e.x - 1;
+                    }
+                }
+            }
+        }
+        f_out[i] = f;
+        if (NORMALS) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) normals_out[3 * i + a] = nrm[a];
+        }
+        if (COLOR) {
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) rgb_out[3 * i + ch] = color_level(rgbf[ch]);
+        }
+        if (LABELS) ins_out[i] = label;
+    }
+}
+
 const char *tsdf_camera_check(const ovo_tsdf_camera_t *c) {
     if (!c) return "null pointer";
     if (!(c->h >= 1 && c->w >= 1 && (int64_t)c->h * c->w <= TSDF_MAX_PIXELS)) return "h, w >= 1 and h * w <= 2^26";
@@ -553,6 +660,33 @@ extern "C" int ovo_tsdf_labels_remap(void *lab, const ovo_tsdf_volume_t *desc, c
     if (n_table == 0) return OVO_OK;                         // no voxel has 0 < L <= 0: nothing to queue
     const int64_t nvox = (int64_t)desc->nx * desc->ny * desc->nz;
     k_tsdf_labels_remap<<<tsdf_grid((nvox + 1) / 2), 256, 0, (hipStream_t)stream>>>((int2 *)lab, nvox, table, n_table);
+    OVO_CHECK_LAUNCH();
+    return OVO_OK;
+}
+
+extern "C" int ovo_tsdf_sample_points(const void *vol, const void *col, const void *lab, const ovo_tsdf_volume_t *desc, const float *points, int64_t n,
+                                      int32_t label_mode, int32_t min_count, float *f_out, float *normals_out, uint8_t *rgb_out, int32_t *ins_out,
+                                      ovo_stream_t stream) {
+    OVO_REQUIRE(vol && desc && f_out, "null pointer");
+    OVO_REQUIRE(n >= 0 && n <= 0x7fffffffLL, "n must be 0 .. 2^31 - 1");
+    OVO_REQUIRE(points || n == 0, "null pointer");
+    const char *wrong = tsdf_volume_check(desc);
+    OVO_REQUIRE(!wrong, wrong);
+    OVO_REQUIRE(((uintptr_t)vol & 15) == 0 && ((uintptr_t)col & 15) == 0 && ((uintptr_t)lab & 15) == 0, "volume, colour volume or label volume not 16-byte aligned");
+    OVO_REQUIRE(((uintptr_t)points & 3) == 0 && ((uintptr_t)f_out & 3) == 0 && ((uintptr_t)normals_out & 3) == 0 && ((uintptr_t)ins_out & 3) == 0,
+                "points, f_out, normals_out or ins_out not 4-byte aligned");
+    OVO_REQUIRE(col || !rgb_out, "rgb_out needs col");
+    OVO_REQUIRE(lab || !ins_out, "ins_out needs lab");
+    OVO_REQUIRE(label_mode == 0 || label_mode == 1, "label_mode must be 0 (nearest) or 1 (vote)");
+    OVO_REQUIRE(min_count >= 1 && min_count <= TSDF_MAX_COUNT, "min_count must be 1 .. 2^30");
+    if (n == 0) return OVO_OK;                               // nothing to queue
+    using Kernel = void (*)(const float2 *, const uint2 *, const int2 *, TsdfVol, const float *, int64_t, int, float *, float *, uint8_t *, int32_t *);
+#define OVO_SAMPLE_FORMS(N, C) k_tsdf_sample_points<N, C, 0>, k_tsdf_sample_points<N, C, 1>, k_tsdf_sample_points<N, C, 2>
+    static const Kernel forms[12] = {OVO_SAMPLE_FORMS(false, false), OVO_SAMPLE_FORMS(false, true), OVO_SAMPLE_FORMS(true, false), OVO_SAMPLE_FORMS(true, true)};
+#undef OVO_SAMPLE_FORMS
+    const int form = (normals_out ? 6 : 0) + (rgb_out ? 3 : 0) + (ins_out ? 1 + label_mode : 0);      // a col or lab without its output is ignored
+    forms[form]<<<tsdf_grid(n), 256, 0, (hipStream_t)stream>>>((const float2 *)vol, (const uint2 *)col, (const int2 *)lab, tsdf_vol(*desc), points, n, min_count, f_out,
+                                                              normals_out, rgb_out, ins_out);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
 }

@@ -13,7 +13,10 @@ What is different, on purpose:
     (slam/icp_tracker.py); there is no Open3D visualiser process (`vis.stream` must be false);
   * no autocast context: the kernels choose their own arithmetic (bf16 MFMA operands, fp32 accumulation);
   * when a frame is segmented, the mask-independent half of the next segmented frame's feature extraction is not started
-    early here (a dataset may be a live camera); `ovo_amd.pipeline.FramePipeline` is the throughput-oriented driver that does.
+    early here (a dataset may be a live camera); `ovo_amd.pipeline.FramePipeline` is the throughput-oriented driver that does;
+  * opt-in: with config["semantic"]["volume_labels"] and a back end whose tracker was built with tsdf_labels
+    (`rgbd_icp`: config["slam"]["icp"]), every segmented keyframe's instance image is voted into the tracker's TSDF volume, the volume follows
+    the merges of `OVO.update_map`, and config["slam"]["save_mesh"] writes `semantic_mesh.ply`.  Without both, `run` makes the calls it made before.
 """
 from __future__ import annotations
 
@@ -106,6 +109,42 @@ class OVOSemMap:
         if self.config["slam"].get("save_estimated_cam", False):
             with open(self.output_path / "estimated_c2w.npy", "wb") as f:
                 torch.save(self.slam_backbone.get_cam_dict(), f)
+        tracker = self._label_tracker()
+        if self.config["slam"].get("save_mesh", False) and tracker is not None and tracker.volume is not None:
+            self._save_semantic_mesh(tracker)
+
+    # ------------------------------------------------------------------ the labelled volume beside the map (no reference counterpart)
+    def _label_tracker(self):
+        """The back end's tracker when its fused model takes the map's instance labels -- config["semantic"]["volume_labels"] and a tracker built with
+        tsdf_labels (`config["slam"]["icp"]`), both -- else None, and `run` makes exactly the calls it makes without the key."""
+        if not self.config["semantic"].get("volume_labels", False):
+            return None
+        tracker = getattr(self.slam_backbone, "tracker", None)
+        return tracker if getattr(tracker, "tsdf_labels", False) else None
+
+    def _fuse_labels(self, tracker, depth) -> None:
+        """Votes the keyframe just queued into the tracker's label volume: its instance image at the depth's size.  A frame the tracker did not fuse
+        (LOST, or none yet) is skipped: `fuse_labels` would vote with the depth and pose of an earlier frame."""
+        ok = getattr(self.slam_backbone, "ok_state", getattr(tracker, "OK", None))
+        if tracker.volume is None or tracker.get_tracking_state() != ok:
+            return
+        matched, binary_maps = self.ovo.keyframes_queue[-1][:2]
+        if binary_maps is None:
+            return
+        tracker.fuse_labels(self.ovo.instance_image(matched, binary_maps, hw=tuple(int(x) for x in depth.shape)))
+
+    def _save_semantic_mesh(self, tracker) -> None:
+        """<output_path>/semantic_mesh.ply: the fused model's surface with the volume's own instance labels, its normals and (tsdf_color) its colour,
+        moved into the map's frame by the back end's world_ref."""
+        from ..utils import mesh_utils
+        color = bool(getattr(tracker, "tsdf_color", False))
+        out = list(tracker.extract_mesh(labels=True, normals=True, colors=color))
+        vertices, faces = out[:2]
+        rgb = out[2] if color else None
+        normals, instance = out[-2], out[-1]
+        mesh = self.ovo.semantic_mesh(self.slam_backbone.get_map(), vertices, faces, instance=instance, normals=normals, rgb=rgb,
+                                      transform=self.slam_backbone.world_ref)
+        mesh_utils.write_ply(self.output_path / "semantic_mesh.ply", **mesh)
 
     def restore_representation(self) -> None:
         ckpt_path = self.output_path / "ovo_map.ckpt"
@@ -132,9 +171,13 @@ class OVOSemMap:
         else:
             ratio = ()
         scene_data = [frame_id, image, frame_data[2], ratio]
+        tracker = self._label_tracker()
+        queued = len(self.ovo.keyframes_queue) if tracker is not None else 0
         updated = self.ovo.detect_and_track_objects(scene_data, self.slam_backbone.get_map(), c2w)
         if updated is not None:
             self.slam_backbone.update_pcd_obj_ids(updated)
+        if tracker is not None and len(self.ovo.keyframes_queue) > queued:      # before compute_semantic_info consumes the queue
+            self._fuse_labels(tracker, frame_data[2])
         self.ovo.compute_semantic_info()
         self.logger.log_memory_usage(frame_id)
 
@@ -160,6 +203,9 @@ class OVOSemMap:
                     updated = self.ovo.update_map(self.slam_backbone.get_map(), self.slam_backbone.get_kfs())
                     if updated is not None:
                         self.slam_backbone.update_pcd_obj_ids(updated)
+                    tracker = self._label_tracker()
+                    if tracker is not None and tracker.volume is not None and self.ovo.last_instance_table is not None:
+                        tracker.volume.remap_labels(self.ovo.last_instance_table)      # the volume follows the merges and removals of the update
                     self.slam_backbone.map_updated = False
                     _sync()
                     t_lc = time.time() - t0

@@ -246,6 +246,18 @@ class IcpTracker:
             raise ValueError("IcpTracker.extract_mesh: no frame processed yet (the volume is made with the first frame)")
         return self.volume.extract_mesh(**kw)
 
+    def sample_model(self, points, **kw):
+        """model="tsdf": `TsdfVolume.sample(points, **kw)` of the fused model -- what the model says at points f32[n, 3] given in the
+        tracker's frame (that of the first camera; `transform=` takes points of another frame there, e.g. inv(world_ref) for world-frame points):
+        F f32[n], then what `colors=` / `normals=` / `labels=` ask for.  Reads the volume only: poses, volume and model image stay as they are."""
+        if self.model != "tsdf":
+            raise ValueError("IcpTracker.sample_model: model='keyframe' keeps no fused model (build the tracker with model='tsdf')")
+        if self.volume is None:
+            raise ValueError("IcpTracker.sample_model: no frame processed yet (the volume is made with the first frame)")
+        if kw.get("labels", False) and not self.tsdf_labels:
+            raise ValueError("IcpTracker.sample_model: the model holds no labels (build the tracker with model='tsdf', tsdf_labels=True)")
+        return self.volume.sample(points, **kw)
+
     def render_model(self, c2w=None, normals: bool = False, labels: bool = False):
         """tsdf_color: the fused model seen from `c2w` (None: the last good pose), in the tracker's frame: (depth f32[h, w], rgb u8[h, w, 3]) on
         the device, new tensors; the depth has the bits `model_depth` has at that pose.  Queued on the current stream, not waited for.

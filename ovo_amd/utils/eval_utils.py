@@ -181,6 +181,37 @@ def match_labels_to_vtx(points_3d_labels, points_3d, mesh_vtx, filter_unasigned:
     return mesh_labels.cpu(), mesh_instances_masks.cpu(), matched_instances_ids.cpu()
 
 
+def match_volume_to_vtx(volume, mesh_vtx, transform=None, min_count: int = 1, label_mode: str = "vote", max_dist: Optional[float] = None, fallback=None,
+                        device_out: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`match_labels_to_vtx`'s triple from a labelled TSDF volume (`TsdfVolume(labels=True)`) instead of the sparse map: every mesh
+    vertex takes the volume's instance at its own position (`volume.sample(..., labels=True, label_mode=, min_count=)`; `transform`: 4 x 4 from the
+    mesh's frame into the volume's, `tsdf_utils.transform_points`).  A vertex is -1 where the sampler answers -1, where the volume has not seen
+    all eight voxels around it, and, with `max_dist` (metres), where |F| * trunc > max_dist.  `fallback=(points_3d_labels, points_3d)` fills
+    exactly the -1 vertices from `match_labels_to_vtx` of the map: the volume answers where it has seen something, the 5-NN transfer elsewhere.
+    -1 is never a row of the masks.  No mirror in the reference: its evaluation has the 5-NN transfer only."""
+    vtx = mesh_vtx
+    if not (isinstance(vtx, torch.Tensor) and vtx.dtype == torch.float32 and vtx.device == volume.vol.device and vtx.is_contiguous()):
+        vtx = _to_dev(mesh_vtx, torch.float32, volume.vol.device)
+    F, ins = volume.sample(vtx, transform=transform, labels=True, min_count=min_count, label_mode=label_mode)
+    mesh_labels = ins.to(torch.int64)
+    drop = F > 1.0                                         # 2.0: not seen (the sampler answers -1 there already)
+    if max_dist is not None:
+        drop = drop | (F.abs() * float(volume.trunc) > float(max_dist))
+    mesh_labels = torch.where(drop, torch.full_like(mesh_labels, -1), mesh_labels)
+    if fallback is not None:
+        missing = mesh_labels < 0
+        if bool(missing.any()):
+            filled = match_labels_to_vtx(fallback[0], fallback[1], vtx[missing].contiguous(), device_out=True)[0]
+            mesh_labels = mesh_labels.clone()
+            mesh_labels[missing] = filled.to(mesh_labels.device)
+    matched_instances_ids = torch.unique(mesh_labels)
+    matched_instances_ids = matched_instances_ids[matched_instances_ids >= 0]
+    mesh_instances_masks = mesh_labels[None, :] == matched_instances_ids[:, None]
+    if device_out:
+        return mesh_labels, mesh_instances_masks, matched_instances_ids
+    return mesh_labels.cpu(), mesh_instances_masks.cpu(), matched_instances_ids.cpu()
+
+
 # ---- confusion matrix ---------------------------------------------------------------------------------------------
 def confusion_counts(gt_ids: torch.Tensor, pr_ids: torch.Tensor, num_classes: int, ignore) -> torch.Tensor:
     """u64-valued counts (int64 tensor [C, C] on the GPU) of the (gt, pr) pairs whose gt is not in `ignore`; IndexError where numpy's

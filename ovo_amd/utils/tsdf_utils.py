@@ -5,7 +5,8 @@ same three steps carry it along (`ovo_tsdf_integrate_color`, `ovo_tsdf_raycast_c
 normal: `raycast(normals=True)` and `extract_mesh(normals=True)` return it (`ovo_tsdf_raycast_normals`, `ovo_tsdf_mesh_normals`: section 21) and `shade_normals` makes a lit picture of it.  `TsdfHistory` keeps the depth images a volume was fused from, and
 `TsdfVolume.refuse` fuses it again from them at other poses -- what a loop closure needs (section 19).  With `labels=True` a label array (L, C) beside the
 volume takes the instance images of the keyframes as votes (`integrate_labels`), follows the map's instance merges (`remap_labels`), and `raycast(labels=True)` /
-`extract_mesh(labels=True)` read it back (`ovo_tsdf_integrate_labels`, `ovo_tsdf_labels_remap`, `ovo_tsdf_raycast_labels`, `ovo_tsdf_mesh_labels`: section 22).  `frustum_box`, `rigid_inverse_f32` and `volume_desc` / `camera_desc` are pure numpy / ctypes and need no GPU."""
+`extract_mesh(labels=True)` read it back (`ovo_tsdf_integrate_labels`, `ovo_tsdf_labels_remap`, `ovo_tsdf_raycast_labels`, `ovo_tsdf_mesh_labels`: section 22).  `sample(points, ...)` reads all of it -- distance, gradient, colour, instance -- at arbitrary points
+(`ovo_tsdf_sample_points`: section 23), and `transform_points` takes points of another frame into the volume's.  `frustum_box`, `rigid_inverse_f32` and `volume_desc` / `camera_desc` are pure numpy / ctypes and need no GPU."""
 from __future__ import annotations
 
 import ctypes as C
@@ -309,6 +310,56 @@ class TsdfVolume:
                                                  L.ptr(ins), V, L.stream()))
             result += (ins,)
         return result
+
+    def sample(self, points: torch.Tensor, transform=None, normals: bool = False, colors: bool = False, labels: bool = False, min_count: int = 1,
+               label_mode: str = "nearest"):
+        """What the model says at points f32[n, 3] (device, in the volume's frame; `transform` X 4 x 4: `transform_points(points, X)` first) on the
+        current stream, never waiting (`ovo_tsdf_sample_points`): F f32[n], the trilinear blend of the eight voxels around a point, 2.0
+        where the point lies outside the volume or one of the eight is unobserved.  The outputs asked for follow in `extract_mesh`'s order:
+        `colors=True` (a colour volume only) rgb u8[n, 3]; `normals=True` the unit gradient f32[n, 3] in the volume's frame; `labels=True` (a label volume
+        only) instance ids i32[n] -- label_mode "nearest": the nearest voxel's id if its count is >= min_count, else -1 (the ray cast's rule);
+        "vote": the id with the largest sum of counts over the eight voxels with a count >= min_count, ties to the nearest voxel's id, then to
+        the smallest.  A point that is not seen answers (0, 0, 0), three zeros and -1."""
+        if label_mode not in LABEL_MODES:
+            raise L.OvoHipError(f"TsdfVolume.sample: label_mode must be one of {sorted(LABEL_MODES)} (got {label_mode!r})")
+        if labels:
+            self._labelled("sample")
+        if colors and self.col is None:
+            raise L.OvoHipError("TsdfVolume.sample: colors=True needs a volume made with color=True")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+            raise L.OvoHipError(f"TsdfVolume.sample: points must be f32 [n, 3] (got {tuple(getattr(points, 'shape', ()))})")
+        L.dev(points, torch.float32, "points")
+        if transform is not None:
+            points = transform_points(points, transform)
+        n, dev = int(points.shape[0]), points.device
+        f = torch.empty((n,), dtype=torch.float32, device=dev)
+        rgb = torch.empty((n, 3), dtype=torch.uint8, device=dev) if colors else None
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=dev) if normals else None
+        ins = torch.empty((n,), dtype=torch.int32, device=dev) if labels else None
+        if n > 0:                                            # (no point: empty tensors have no address, and there is nothing to queue)
+            L.check(L.load().ovo_tsdf_sample_points(L.ptr(self.vol), L.ptr(self.col) if colors else None, L.ptr(self.lab) if labels else None, C.byref(self.desc),
+                                                    L.ptr(points), n, LABEL_MODES[label_mode], int(min_count), L.ptr(f), L.ptr(nrm), L.ptr(rgb), L.ptr(ins),
+                                                    L.stream()))
+        extra = tuple(x for x in (rgb, nrm, ins) if x is not None)
+        return (f,) + extra if extra else f
+
+
+LABEL_MODES = {"nearest": 0, "vote": 1}                    # ovo_tsdf_sample_points' label_mode
+
+
+def transform_points(points: torch.Tensor, X) -> torch.Tensor:
+    """(points.double() @ R.T + t).float() on the points' device for a 4 x 4 X = [R t; 0 1]: the product and the sum in f64, one rounding to f32.
+    The one documented way from world-frame points (the map, a GT mesh under world_ref) into a volume's frame: `TsdfVolume.sample(transform=X)` is
+    exactly `sample(transform_points(points, X))`."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise L.OvoHipError(f"transform_points: points must be [n, 3] (got {tuple(getattr(points, 'shape', ()))})")
+    X = _np(X, np.float64)                                 # (a host X: its twelve numbers travel as kernel arguments, and nothing waits)
+    if X.shape != (4, 4):
+        raise L.OvoHipError(f"transform_points: X must be 4 x 4 (got {X.shape})")
+    p = points.double()
+    # the product row by row, ((p0 R[a, 0] + p1 R[a, 1]) + p2 R[a, 2]) + t[a]: one f64 operation at a time, so that numpy restates every bit
+    cols = [((p[:, 0] * float(X[a, 0]) + p[:, 1] * float(X[a, 1])) + p[:, 2] * float(X[a, 2])) + float(X[a, 3]) for a in range(3)]
+    return torch.stack(cols, 1).float().contiguous()
 
 
 class TsdfHistory:
