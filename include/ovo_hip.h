@@ -1228,6 +1228,42 @@ int ovo_knn5_labels(const void *records, const int32_t *cell_start, int64_t n_po
 int ovo_confusion(const int64_t *gt, const int64_t *pr, int64_t n, int n_classes, const int64_t *ignore_host, int n_ignore,
                   uint64_t *confusion, int32_t *out_of_range, ovo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------------------
+ * Which old keyframe a frame looks like (additions to ABI v23): randomized depth ferns (Glocker et al., "Real-time RGB-D camera
+ * relocalization via randomized ferns") over one level of a prepared pyramid -- the index behind IcpTracker(relocalise=True) and loop_candidates="fern".
+ *
+ * A code: M ferns (a multiple of 8, 8 .. OVO_FERN_MAX_FERNS) of 4 tests each.  Test (f, b) is a pixel index pix[4 f + b] into pyramid level `level`
+ * (row-major, v * w_l + u) and a threshold tau[4 f + b]; its bit is 1 iff that pixel's depth flag is set (bit 0 of word 3 of the pixel's 8 words, what
+ * ovo_icp_align reads) AND z > tau in f32, z = word 2 (a NaN compares false).  The code is u32[W], W = M / 8: fern f is bits 4 (f % 8) .. 4 (f % 8) + 3
+ * of word f / 8, test b bit 4 (f % 8) + b.
+ *
+ * ovo_fern_encode: one launch; reads only the named level, writes W words of code_out (device, 4-byte aligned).  pix (i32[4 M]) and tau (f32[4 M]) are
+ * device tables; the kernel does NOT range-check pix: whoever makes the table validates it against the level it is made for, and declares that number
+ * of pixels as pix_limit -- a pix_limit above h_l * w_l of the named level is refused.
+ *
+ * ovo_fern_search: db is u32[n][W] (device, 4-byte aligned), 0 <= n <= OVO_FERN_MAX_ROWS.  dist[r] = the number of ferns whose nibble differs between
+ * code and row r (XOR, every nibble folded to one bit, popcount: BlockHD as an integer in 0 .. M), written to dist_out i32[n] when that is not NULL.
+ * limits: a HOST array of n_limits (1 .. OVO_FERN_MAX_LIMITS) row counts, each in 0 .. n, not decreasing.  For every limit i: the k
+ * (1 .. OVO_FERN_MAX_K) smallest keys (dist << 32) | r over the rows r < limits[i], ascending -- equal distances go to the lower row; missing entries
+ * are -1.  result_host: a pinned block (ovo_host_alloc) of OVO_FERN_RESULT_WORDS 8-byte words:
+ *     0 sequence | 1 n | 2 + 16 i + e: entry e of limit i's list (every word is written: lists >= n_limits and entries >= k are -1)
+ * published as ovo_icp_align publishes: the block, a system-scope fence, then the sequence word (seq, not 0) last; the host reads it with
+ * ovo_host_wait64.  ws: device scratch of ovo_fern_search_workspace_bytes(n, k) (0 for an n or k outside its range), 8-byte aligned.
+ * Two launches (one when n = 0, which gives all entries -1): distances and a partial list per virtual workgroup, then a one-workgroup merge.  Nothing
+ * crosses workgroups inside a launch; the result does not depend on the grid (OVO_FERN_GRID_CAP) and is equal bit for bit from run to run.
+ * OVO_E_ARG, nothing launched: a null pointer (dist_out excepted), M, W, k, n, n_limits or a limit out of range, a pix_limit above the level, a
+ * misaligned code, db, table or result block, a workspace that is too small, a sequence number of 0. */
+#define OVO_FERN_MAX_FERNS 4096
+#define OVO_FERN_MAX_ROWS (1 << 20)
+#define OVO_FERN_MAX_K 16
+#define OVO_FERN_MAX_LIMITS 4
+#define OVO_FERN_RESULT_WORDS 66
+int ovo_fern_encode(const void *pyramid, const ovo_icp_frame_t *frame, int level, const int32_t *pix, const float *tau, int M, int64_t pix_limit,
+                    uint32_t *code_out, ovo_stream_t stream);
+size_t ovo_fern_search_workspace_bytes(int64_t n, int k);
+int ovo_fern_search(const uint32_t *code, const uint32_t *db, int64_t n, int W, const int32_t *limits, int n_limits, int k, int32_t *dist_out,
+                    void *result_host, int64_t seq, void *ws, size_t ws_bytes, ovo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -298,6 +298,9 @@ _SIGNATURES = {
     "ovo_eval_grid_records": (_I32, [_P, _P, _I64, _P, _P]),
     "ovo_knn5_labels": (_I32, [_P, _P, _I64, C.POINTER(EvalGrid), _P, _P, _I64, _P, _P, _P, _P, _P, _P]),
     "ovo_confusion": (_I32, [_P, _P, _I64, _I32, C.POINTER(C.c_int64), _I32, _P, _P, _P]),
+    "ovo_fern_encode": (_I32, [_P, C.POINTER(IcpFrame), _I32, _P, _P, _I32, _I64, _P, _P]),
+    "ovo_fern_search_workspace_bytes": (_SZ, [_I64, _I32]),
+    "ovo_fern_search": (_I32, [_P, _P, _I64, _I32, C.POINTER(C.c_int32), _I32, _I32, _P, _P, _I64, _P, _SZ, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -54,6 +54,13 @@ class KeyframeReference:
     def corrected(self, X, c2w) -> None:
         pass                                               # the keyframe's own image is the model: nothing to rebuild
 
+    def relocalised(self, frame, T, cur, aligner) -> None:
+        """A LOST frame `cur` found itself at T against the kept keyframe pyramid `frame`: that keyframe is the reference
+        again and T the device pose the next frame starts from; the frame itself is no keyframe, and its buffer takes the next frame."""
+        self.frame = frame
+        aligner.set_pose(T)
+        self.spare = cur.pyramid
+
 
 class TsdfReference:
     """Every frame, from the identity, against the volume ray-cast at the last good pose: an OK frame is fused at its pose and the model image
@@ -135,6 +142,17 @@ class TsdfReference:
         if self._last is not None:
             self._last = (self._last[0], c2w, self._last[2])
         self._cast(c2w)
+
+    def cast_at(self, poses):
+        """Relocalisation: the model ray-cast and prepared at each of `poses` (4 x 4), into new buffers -- what a LOST frame is
+        verified against.  No history is needed.  Queued, not waited for."""
+        return [self.prepare(self.volume.raycast(self.K, self._hw[0], self._hw[1], np.asarray(X, dtype=np.float32), self.near, self.far), None)
+                for X in poses]
+
+    def relocalised(self, c2w, cur) -> None:
+        """A LOST frame `cur` found itself at c2w: nothing is fused, the model image is cast there for the next frame, and the frame's buffer takes it."""
+        self._cast(c2w)
+        self.spare = cur.pyramid
 
     def _fuse(self, depth, c2w, rgb=None) -> None:
         """Fuses a tracked frame at its pose and ray-casts the model there for the next frame: queued, not waited for."""

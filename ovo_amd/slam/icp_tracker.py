@@ -28,7 +28,9 @@ import torch
 from ..utils import icp_utils as U
 from ..utils.tsdf_utils import MAX_HISTORY
 from .icp_reference import KeyframeReference, TsdfReference
+from .keyframe_store import KeyframeStore
 from .loop_closer import LoopCloser
+from .relocaliser import Relocaliser
 
 
 class IcpTracker:
@@ -42,7 +44,10 @@ class IcpTracker:
                  loop_min_overlap: float = 0.3, loop_max_rms: float = 0.02, loop_max_correction=(0.3, 10.0), loop_min_shift=(0.01, 0.2),
                  loop_max_keyframes: int = 256, model: str = "keyframe", tsdf_dims=(512, 512, 512), tsdf_voxel: float = 0.02, tsdf_origin=None,
                  tsdf_trunc=None, tsdf_max_weight: float = 64, tsdf_near: float = 0.05, tsdf_far=None, tsdf_history: int = 0,
-                 tsdf_color: bool = False, tsdf_labels: bool = False) -> None:
+                 tsdf_color: bool = False, tsdf_labels: bool = False, relocalise: bool = False, fern_count: int = 256, fern_seed: int = 0,
+                 fern_tau=(0.3, None), reloc_max_candidates: int = 4, reloc_max_dissimilarity: float = 0.3, reloc_iters=None, reloc_dist_th: float = 0.2,
+                 reloc_min_overlap: float = 0.3, reloc_max_rms: float = 0.02, reloc_max_keyframes: int = 256, loop_candidates: str = "pose",
+                 loop_max_dissimilarity: float = 0.3) -> None:
         """No GPU work happens here: buffers are made with the first frame.  The loop_* parameters are read and checked by `LoopCloser`, the
         tsdf_* parameters by `TsdfReference`, whichever mode is chosen.
 
@@ -79,7 +84,25 @@ class IcpTracker:
         tsdf_labels (model="tsdf" only): a label array beside the volume (1 GB more at 512^3, 1.12 MB a frame more in the
         history).  The frame loop never touches it: `fuse_labels(ins)` votes a keyframe's instance image (`OVO.instance_image`) into it,
         `render_model(labels=True)` and `extract_mesh(labels=True)` read it back, `volume.remap_labels(OVO.last_instance_table)` follows the map's
-        merges.  Poses, the volume and the model image are bit-identical with it on or off."""
+        merges.  Poses, the volume and the model image are bit-identical with it on or off.
+
+        relocalise: every frame's fern code -- fern_count ferns (a multiple of 8) of 4 depth tests over the coarsest pyramid
+        level, pixels and thresholds drawn from fern_seed, thresholds uniform in fern_tau metres (None: max_depth / 2) -- is searched against the
+        keyframes' codes, queued in front of the frame's alignment: no extra wait.  A frame whose alignment is LOST is then verified, from the
+        identity, against the reloc_max_candidates (<= 16) most similar kept keyframes within reloc_max_dissimilarity (a fraction of the ferns) in
+        ONE `ovo_icp_align_batch` call with reloc_iters (default: iters) and reloc_dist_th -- one extra host wait, on such a frame only.
+        model="keyframe": against the kept pyramids of the last reloc_max_keyframes keyframes (one store with the loop closer's: with both on it
+        holds the larger of the two counts); model="tsdf": against the model ray-cast at the candidates' keyframe poses.  An entry passes when it is
+        OK, has pairs >= reloc_min_overlap * pixels and rms <= reloc_max_rms; the winner k has the most pairs, then the smaller rms, then the lower
+        index.  The frame is then OK at X_k @ T (an f64 product rounded once; X_k the graph's pose with close_loops, else the keyframe row), is no
+        keyframe, and is neither fused nor added to the history; `last_reloc` records the attempt.  model="keyframe": keyframe k is the reference
+        again and the next keyframe's odometry edge hangs on k; model="tsdf": the model image is cast at the new pose.  Without a winner the frame is
+        LOST as ever.  The fern_* and reloc_* defaults are JUDGEMENT, not measurement.  Limits: the codes see depth only, and an alignment of
+        views that overlap little can be OK at a wrong pose (a box sliding along its walls) -- the gates do not detect that.
+
+        loop_candidates (close_loops only): "pose" (by the pose estimate, as above), "fern" (by appearance: the kept keyframes k <= n -
+        loop_min_gap within loop_max_dissimilarity of the new keyframe's code, in (distance, k) order, each with the identity as its guess) or
+        "both" (by pose first, then by appearance into the slots left).  The verification batch, its one wait and the acceptance are the same."""
         self.K = np.asarray(K.detach().cpu() if isinstance(K, torch.Tensor) else K, dtype=np.float32)[:3, :3].copy()
         self.levels, self.iters = int(levels), tuple(int(i) for i in iters)
         if not 1 <= self.levels <= U.MAX_LEVELS or len(self.iters) != self.levels:
@@ -88,8 +111,17 @@ class IcpTracker:
         self.min_pairs_frac, self.min_pivot_ratio = float(min_pairs_frac), float(min_pivot_ratio)
         self.kf_translation, self.kf_rotation_deg, self.kf_min_overlap = float(kf_translation), float(kf_rotation_deg), float(kf_min_overlap)
         self.close_loops = bool(close_loops)
+        self.relocalise = bool(relocalise)
+        self._ferns = Relocaliser(self.iters, self.normal_th_deg, self.min_pivot_ratio, self.max_depth, fern_count, fern_seed, fern_tau,
+                                  reloc_max_candidates, reloc_max_dissimilarity, reloc_iters, reloc_dist_th, reloc_min_overlap, reloc_max_rms,
+                                  reloc_max_keyframes)
+        self._store = KeyframeStore(max(int(loop_max_keyframes), self._ferns.max_keyframes) if self.relocalise else int(loop_max_keyframes))
         self._loops = LoopCloser(self.iters, self.normal_th_deg, self.min_pivot_ratio, loop_min_gap, loop_radius, loop_angle_deg, loop_max_candidates,
-                                 loop_iters, loop_dist_th, loop_min_overlap, loop_max_rms, loop_max_correction, loop_min_shift, loop_max_keyframes)
+                                 loop_iters, loop_dist_th, loop_min_overlap, loop_max_rms, loop_max_correction, loop_min_shift, loop_max_keyframes,
+                                 loop_candidates, loop_max_dissimilarity, self._ferns.fern_count, self._store)
+        self._loop_ferns = self.close_loops and self._loops.candidates != "pose"
+        self._use_ferns = self.relocalise or self._loop_ferns      # False: no fern call is ever made
+        self._ref_kf = 0                                   # the keyframe the frames are aligned against (model="keyframe": not the newest after a relocalisation)
         self.loop_iters = self._loops.iters
         self.model = str(model)
         if self.model not in ("keyframe", "tsdf"):
@@ -128,6 +160,7 @@ class IcpTracker:
     history = property(lambda self: getattr(self._ref, "history", None))           # tsdf_history > 0: the TsdfHistory, made with the first frame
     loop_edges = property(lambda self: self._loops.loop_edges)                     # close_loops: see LoopCloser
     last_loop = property(lambda self: self._loops.last_loop)
+    last_reloc = property(lambda self: self._ferns.last_reloc)                     # relocalise: the last attempt, see Relocaliser.verify
     loop_poses = property(lambda self: self._loops.poses)                          # close_loops: the graph's keyframe poses in f64, what `history.poses` takes
 
     def _row_of(self, t, c2w: np.ndarray) -> np.ndarray:
@@ -154,7 +187,8 @@ class IcpTracker:
 
     def process_image_rgbd(self, rgb, depth, t) -> None:
         """Tracks one frame (the colour image takes no part in it; tsdf_color fuses it into the model of a tracked frame); returns when its pose
-        is on the host: one host wait per frame, and one more on a keyframe whose loop candidates are verified."""
+        is on the host: one host wait per frame, one more on a keyframe whose loop candidates are verified, and with relocalise one more on a LOST
+        frame that has keyframes to be verified against."""
         if self.closed:
             raise RuntimeError("IcpTracker: shut down")
         depth, ref = self._depth(depth), self._ref
@@ -165,16 +199,29 @@ class IcpTracker:
             self._state, self._is_kf, self.last = self.OK, True, None
             self._row = self._row_of(t, self._c2w)
             self._keyframes.append(self._row)
+            if self._use_ferns:                            # keyframe 0's code, from its own pyramid (model="tsdf" without a history keeps none: made here)
+                own = ref.frame if self.model == "keyframe" else ref._kf
+                if own is None:
+                    own = self._prepare(depth, None)
+                    ref.spare = own.pyramid
+                self._ferns.encode(own)
+                self._ferns.add_keyframe(0)
             return
         cur = self._prepare(depth, ref.spare)
         ref.aim(self._aligner)
         pixels = cur.h * cur.w
         min_pairs = int(np.ceil(self.min_pairs_frac * pixels))
+        if self._use_ferns:                                # code and search in front of the alignment: their block is there when the alignment's is
+            n = len(self._keyframes)                       # the index this frame would get as a keyframe
+            self._ferns.queue(cur, [n - self._loops.min_gap + 1, n] if self._loop_ferns else [n])
         seq = self._aligner.queue(ref.frame, cur, self.iters, self.dist_th, self.normal_th_deg, min_pairs, self.min_pivot_ratio)
         self.last = res = self._aligner.wait(seq)
+        matches = self._ferns.matches() if self._use_ferns else None
         self._is_kf = False
-        if res["state"] != U.OK:                           # the pose stays that of the last good frame, and the reference as it was
-            self._state = self.LOST
+        if res["state"] != U.OK:
+            if self.relocalise and self._relocalise(cur, t, matches[-1], pixels, min_pairs):
+                return                                     # found again: OK at a kept keyframe's pose times the verified alignment, no keyframe
+            self._state = self.LOST                        # the pose stays that of the last good frame, and the reference as it was
             ref.spare = cur.pyramid
             return
         self._state = self.OK
@@ -185,14 +232,56 @@ class IcpTracker:
             self._keyframes.append(self._row)
         n = len(self._keyframes) - 1                       # the keyframe this frame hangs on (itself, when it is one)
         old = ref.tracked(cur, depth, self._c2w, self._is_kf, self._aligner, t, n, relative, **color)
+        more = {}
+        if self._is_kf:
+            parent, self._ref_kf = self._ref_kf, n
+            if parent != n - 1:                            # after a relocalisation: the outgoing reference is an old keyframe, and the edge hangs on it
+                more["parent"] = parent
+            if self._use_ferns:
+                self._ferns.add_keyframe(n)
+            if self._loop_ferns:
+                more["fern"] = matches[0]
+            if self.relocalise and not self.close_loops and self.model == "keyframe":      # the loop closer's bookkeeping of the pyramids, without it
+                self._store.put(parent, old)
+                ref.spare = self._store.trim()
         if self._is_kf and self.close_loops:               # `old`'s pyramid is kept: the next frame takes the one that became free, or a new one
             # model="tsdf": `old` and `cur` are the keyframes' own images, and the edge is keyframe to keyframe, not the alignment to the model
-            X, ref.spare = self._loops.keyframe(n, old, cur, res, pixels, min_pairs, edge_T=relative if self.model == "tsdf" else None)
+            X, ref.spare = self._loops.keyframe(n, old, cur, res, pixels, min_pairs, edge_T=relative if self.model == "tsdf" else None, **more)
             if X is not None:                              # a closure moved the keyframes: their rows, rounded to f32, and this frame's pose
                 self._keyframes = [self._row_of(row[0], x) for row, x in zip(self._keyframes, X)]
                 self._kf_c2w = self._c2w = X[n].astype(np.float32)
                 self._row = self._keyframes[n]
                 ref.corrected(X, self._c2w)                # model="tsdf": the volume fused again from its history, the model image cast again
+
+    def _relocalise(self, cur: U.Frame, t, matches, pixels: int, min_pairs: int) -> bool:
+        """A LOST frame and its fern matches [(keyframe, distance)]: verifies the kept keyframes it looks like in one batch and, with a winner k,
+        takes the pose X_k @ T.  False: no candidate or no winner, and nothing has changed."""
+        ref, keyframe_mode = self._ref, self.model == "keyframe"
+        kept = (lambda k: k in self._store or k == self._ref_kf) if keyframe_mode else (lambda k: k < len(self._keyframes))
+        chosen = self._ferns.choose(matches, kept)
+        if not chosen:
+            return False
+        poses = self._loops.poses if self.close_loops else [np.vstack([row[1:].reshape(3, 4).astype(np.float64), [[0.0, 0.0, 0.0, 1.0]]]) for row in self._keyframes]
+        if keyframe_mode:
+            refs = [ref.frame if k == self._ref_kf else self._store[k] for k, _ in chosen]
+        else:
+            refs = ref.cast_at([poses[k] for k, _ in chosen])
+        k, res = self._ferns.verify(chosen, refs, cur, pixels, min_pairs)
+        if k is None:
+            return False
+        self._state = self.OK
+        self._c2w = (poses[k] @ res["T"].astype(np.float64)).astype(np.float32)      # an f64 product, rounded once
+        self._row = self._row_of(t, self._c2w)
+        if keyframe_mode:
+            if k != self._ref_kf:                          # the outgoing reference is a kept keyframe like any other
+                self._store.put(self._ref_kf, ref.frame)
+                self._ref_kf = k
+                self._store.trim(keep=k)
+            self._kf_c2w = poses[k].astype(np.float32)
+            ref.relocalised(refs[[c for c, _ in chosen].index(k)], res["T"], cur, self._aligner)
+        else:
+            ref.relocalised(self._c2w, cur)
+        return True
 
     def fuse_labels(self, ins) -> None:
         """tsdf_labels: votes the instance image ins (i32 [h, w] of the depth's size, an array or a tensor; negative = no label) into the label volume
@@ -281,4 +370,5 @@ class IcpTracker:
     def shutdown(self) -> None:
         self._aligner = self._ref = None                   # with the reference go the keyframe's pyramid, or the volume and its image
         self._loops.release()
+        self._ferns.release()
         self.closed = True

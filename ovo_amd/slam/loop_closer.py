@@ -3,19 +3,22 @@ pyramids and their batched verification (`ovo_icp_align_batch`).  The tracker te
 nothing here reaches into the tracker."""
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional
+from typing import Any, List, Optional
 
 import numpy as np
 
 from ..utils import icp_utils as U
 from . import pose_graph
+from .keyframe_store import KeyframeStore
 
 
 class LoopCloser:
     def __init__(self, iters, normal_th_deg: float, min_pivot_ratio: float, loop_min_gap: int, loop_radius: float, loop_angle_deg: float,
                  loop_max_candidates: int, loop_iters, loop_dist_th: float, loop_min_overlap: float, loop_max_rms: float, loop_max_correction,
-                 loop_min_shift, loop_max_keyframes: int) -> None:
-        """`iters`, `normal_th_deg` and `min_pivot_ratio` are the tracker's own; the loop_* parameters are described at `IcpTracker`."""
+                 loop_min_shift, loop_max_keyframes: int, loop_candidates: str = "pose", loop_max_dissimilarity: float = 0.3,
+                 fern_count: int = 256, store: Optional[KeyframeStore] = None) -> None:
+        """`iters`, `normal_th_deg` and `min_pivot_ratio` are the tracker's own; the loop_* parameters are described at `IcpTracker`.  `store`: the
+        keyframe store to keep the pyramids in (None: one of its own, of loop_max_keyframes)."""
         self.normal_th_deg, self.min_pivot_ratio = normal_th_deg, min_pivot_ratio
         self.min_gap, self.max_candidates, self.max_keyframes = int(loop_min_gap), int(loop_max_candidates), int(loop_max_keyframes)
         self.radius, self.angle_deg, self.dist_th = float(loop_radius), float(loop_angle_deg), float(loop_dist_th)
@@ -31,30 +34,44 @@ class LoopCloser:
             raise ValueError("IcpTracker: loop_max_correction (> 0) and loop_min_shift (>= 0) are (metres, degrees)")
         if not (self.radius > 0 and self.angle_deg > 0 and self.dist_th > 0 and 0 <= self.min_overlap <= 1 and self.max_rms > 0):
             raise ValueError("IcpTracker: loop_radius, loop_angle_deg, loop_dist_th and loop_max_rms must be > 0 and loop_min_overlap in [0, 1]")
+        self.candidates, self.max_dissimilarity, self.fern_count = str(loop_candidates), float(loop_max_dissimilarity), int(fern_count)
+        if self.candidates not in ("pose", "fern", "both"):
+            raise ValueError(f"IcpTracker: loop_candidates must be 'pose', 'fern' or 'both' (got {loop_candidates!r})")
+        if not 0 <= self.max_dissimilarity <= 1:
+            raise ValueError("IcpTracker: loop_max_dissimilarity is a fraction of the ferns, in [0, 1]")
         # the pose graph (f64), the kept pyramids by keyframe index (oldest first), what the last closure did
         self._batch: Optional[U.BatchAligner] = None
         self._X: List[np.ndarray] = [np.eye(4)]
         self._edges: List[Any] = []
-        self._db: Dict[int, U.Frame] = {}
+        self._db = KeyframeStore(self.max_keyframes) if store is None else store
         self.big_change = 0                                # goes up when a closure moved the keyframes
         self.loop_edges: List[Any] = []                    # (reference keyframe index, current keyframe index) of every accepted edge
         self.last_loop: Any = None                         # the last verification: {"n", "candidates", "results", "accepted", "applied", "graph"}
 
-    def keyframe(self, n: int, old: U.Frame, cur: U.Frame, res, pixels: int, min_pairs: int, edge_T=None):
+    def keyframe(self, n: int, old: U.Frame, cur: U.Frame, res, pixels: int, min_pairs: int, edge_T=None, parent: Optional[int] = None, fern=None):
         """The new keyframe n, `cur`, aligned to the outgoing keyframe `old` with result `res`: extends the graph, keeps `old`'s pyramid and
         verifies the candidates in one batch.  Returns (the corrected poses of keyframes 0 .. n in f64 when the optimised graph moved one, else
         None; the pyramid buffer that became free, else None).
         edge_T (model="tsdf"): the transform of the odometry edge n-1 -> n and of X[n] when it is not res["T"] -- there `res` aligned the frame to
         the MODEL, and the edge is keyframe n's pose in keyframe n-1's frame.  The edge's information stays `U.information(res["sums"])`, that of
-        the keyframe frame's alignment to the model: a judgement, not a measurement of the edge's own uncertainty."""
+        the keyframe frame's alignment to the model: a judgement, not a measurement of the edge's own uncertainty.
+        parent: the keyframe that `old` is and that the odometry edge hangs on, when it is not n - 1 -- a relocalised tracker
+        aligns against an old keyframe k, and its next keyframe's edge is (k, n).
+        fern (loop_candidates "fern" / "both"): the keyframe's appearance matches [(k, block distance)] in (distance, k) order;
+        those within loop_max_dissimilarity * fern_count that are kept, at least loop_min_gap back and not already chosen by pose fill the free slots, each with
+        the identity as its guess (`icp_utils.extend_by_appearance`)."""
+        p = n - 1 if parent is None else int(parent)
         T = (res["T"] if edge_T is None else np.asarray(edge_T)).astype(np.float64)
-        self._X.append(self._X[n - 1] @ T)
-        self._edges.append((n - 1, n, T, U.information(res["sums"])))
-        self._db[n - 1] = old
-        free = None
-        if len(self._db) > self.max_keyframes:            # the oldest leaves the candidate set (it stays a node); its buffer takes the next frame
-            free = self._db.pop(next(iter(self._db))).pyramid
-        candidates = U.select_candidates(self._X, n, list(self._db), self.min_gap, self.radius, self.angle_deg, self.max_candidates)
+        self._X.append(self._X[p] @ T)
+        self._edges.append((p, n, T, U.information(res["sums"])))
+        self._db.put(p, old)
+        free = self._db.trim()                             # the oldest leaves the candidate set (it stays a node); its buffer takes the next frame
+        candidates = []
+        if self.candidates != "fern":
+            candidates = U.select_candidates(self._X, n, self._db.keys(), self.min_gap, self.radius, self.angle_deg, self.max_candidates)
+        if self.candidates != "pose":
+            candidates = U.extend_by_appearance(candidates, fern or [], self._db.keys(), n, self.min_gap, self.max_dissimilarity * self.fern_count,
+                                                  self.max_candidates)
         self.last_loop = {"n": n, "candidates": [k for k, _ in candidates], "results": [], "accepted": [], "applied": False, "graph": None}
         if not candidates:
             return None, free
@@ -87,4 +104,5 @@ class LoopCloser:
         return list(self._X)
 
     def release(self) -> None:
-        self._batch, self._db = None, {}
+        self._batch = None
+        self._db.release()

@@ -116,6 +116,22 @@ def select_candidates(poses: Sequence[np.ndarray], n: int, available: Sequence[i
     return [(k, G) for _, k, G in found[:max_candidates]]
 
 
+def extend_by_appearance(chosen: List[Tuple[int, np.ndarray]], matches: Sequence[Tuple[int, int]], available: Sequence[int], n: int, min_gap: int,
+                         max_distance: float, max_candidates: int) -> List[Tuple[int, np.ndarray]]:
+    """Loop candidates by appearance: `chosen` (what `select_candidates` gave, or nothing) extended by the fern `matches`
+    [(k, block distance)], taken in the order given -- (distance, k) -- while slots are free: an `available` keyframe
+    k <= n - min_gap with distance <= max_distance that is not chosen already, with the identity as its guess."""
+    out, taken, kept = list(chosen), {k for k, _ in chosen}, {int(k) for k in available}
+    for k, d in matches:
+        if len(out) >= max_candidates:
+            break
+        k = int(k)
+        if k in kept and k not in taken and k <= n - min_gap and d <= max_distance:
+            out.append((k, np.eye(4)))
+            taken.add(k)
+    return out
+
+
 def accept_loop(res: Dict[str, Any], guess, pixels: int, min_overlap: float, max_rms: float, max_correction: Tuple[float, float]) -> bool:
     """Whether a verified candidate becomes a loop edge: OK, pairs >= min_overlap * pixels, rms <= max_rms, and a result within max_correction
     (metres, degrees) of the guess it started from."""
