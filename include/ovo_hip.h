@@ -1094,6 +1094,34 @@ int ovo_tsdf_sample_points(const void *vol, const void *col /* may be NULL */, c
                            const float *points, int64_t n, int32_t label_mode, int32_t min_count, float *f_out, float *normals_out /* or NULL */,
                            uint8_t *rgb_out /* or NULL */, int32_t *ins_out /* or NULL */, ovo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A frame aligned to the volume itself (still ABI v23: an entry point added, none changed; restated in
+ * tests/sdf_align_restatement.py): ovo_icp_align with the signed-distance field as the reference -- no ray cast, no model image, no projection.
+ * T: device f32[12], the top three rows of (volume frame <- current camera); read as the start value, advanced on the device, the final value written
+ * back.  ovo_icp_align_t, the result block of 40 words, the workspace (ovo_icp_align_workspace_bytes()), the launch count (2 + 2 * iterations), the
+ * f64 sums, the solve and the LOST rules (min_pairs >> 2l on level l, the pivot floor, T restored, the remaining iterations do nothing) are
+ * ovo_icp_align's, unchanged; only the reduce pass differs.  Per level and per current-level pixel with a valid vertex and a valid normal (p, n), every
+ * step one f32 IEEE operation in the order written unless it is one of the FMA chains of ovo_icp_align's transform:
+ *   transform  P = R p + t, N = R n (ovo_icp_align's chains).
+ *   cell       g[a] = (P[a] - origin[a]) / voxel, b[a] = floorf(g[a]), t[a] = g[a] - b[a]; INSIDE iff 0 <= b[a] <= n[a] - 2 on all three axes (NaN and
+ *              the infinities fail); no float becomes an index, and no address is formed, before that test has passed: ovo_tsdf_sample_points' cell.
+ *   seen       SEEN iff INSIDE and all eight corners b + {0, 1}^3 have W > 0.
+ *   value      f = the trilinear blend of the corners' F with lerp(a, b, t) = a + t * (b - a), along x, then y, then z: ovo_tsdf_raycast's sample.
+ *   gradient   the derivative of that same interpolant, from the same eight corners (F_xyz the corner at offset (x, y, z)), with no further load:
+ *                gx = lerp(lerp(F100 - F000, F110 - F010, ty), lerp(F101 - F001, F111 - F011, ty), tz)
+ *                gy = lerp(lerp(F010 - F000, F110 - F100, tx), lerp(F011 - F001, F111 - F101, tx), tz)
+ *                gz = lerp(lerp(F001 - F000, F101 - F100, tx), lerp(F011 - F010, F111 - F110, tx), ty)
+ *              nq = g / |g| (|g| = sqrt(gx gx + gy gy + gz gz), products first, sums left to right; the unit is F per voxel, nothing is divided by voxel).
+ *              This is NOT the gradient of ovo_tsdf_raycast_normals / ovo_tsdf_sample_points (central differences of the corners, blended: up to 56 more
+ *              loads a point).  It costs no load; the price is that it JUMPS across a cell face, where the two differ by the curvature of F.
+ *   kept       iff SEEN, |f| < 1, |g| positive and finite, a = trunc * f (one product) has |a| <= dist_th, and (N.x nq.x + N.y nq.y) + N.z nq.z >= cos_th.
+ *   terms      r = a, J = [cross(P, nq), nq] (rotation first): ovo_icp_align's expressions with nq in the place of the reference normal.
+ * The residual exists only where |f| < 1, i.e. within trunc of the surface: a start pose further off than that pairs nothing and is LOST.
+ * The volume is only read.  OVO_E_ARG, nothing launched: everything ovo_icp_align refuses about cur, align, T, result_host and ws; a null vol or
+ * desc; a descriptor the other ovo_tsdf entry points refuse; a vol not 16-byte aligned. */
+int ovo_icp_align_volume(const void *vol, const ovo_tsdf_volume_t *desc, const void *cur_pyramid, const ovo_icp_frame_t *cur,
+                         const ovo_icp_align_t *align, float *T, void *result_host, void *ws, size_t ws_bytes, ovo_stream_t stream);
+
 
 /* =============================================================================================
  * The keyframe chain without host round trips (MI355X extension of a6 / a9; what the reference does with a `.sum()` / vstack

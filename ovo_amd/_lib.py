@@ -264,6 +264,7 @@ _SIGNATURES = {
     "ovo_icp_prepare": (_I32, [_P, C.POINTER(IcpFrame), _P, _SZ, _P]),
     "ovo_icp_align_workspace_bytes": (_SZ, []),
     "ovo_icp_align": (_I32, [_P, C.POINTER(IcpFrame), _P, C.POINTER(IcpFrame), C.POINTER(IcpAlign), _P, _P, _P, _SZ, _P]),
+    "ovo_icp_align_volume": (_I32, [_P, C.POINTER(TsdfVolume), _P, C.POINTER(IcpFrame), C.POINTER(IcpAlign), _P, _P, _P, _SZ, _P]),
     "ovo_icp_align_batch_workspace_bytes": (_SZ, [_I32]),
     "ovo_icp_align_batch": (_I32, [_P, C.POINTER(IcpFrame), _P, C.POINTER(IcpFrame), C.POINTER(IcpAlign), _I32, _P, _P, _P, _SZ, _P]),
     "ovo_tsdf_volume_bytes": (_SZ, [C.POINTER(TsdfVolume)]),

@@ -7,8 +7,11 @@
 //   ovo_icp_align_batch  m alignments of ONE current frame against m references in the same launches: entry k is blockIdx.y
 //                     of the reduce pass and blockIdx.x of the other three kernels, with its own IcpState and slabs ICP_ENTRY_BYTES apart in the
 //                     workspace.  ovo_icp_align is the m = 1 case: one set of kernels, one per-pixel arithmetic, the same bits.
+//   ovo_icp_align_volume the same alignment with a fused TSDF volume as the reference: init, solve and publish as they are, and a
+//                     reduce pass of its own that reads the volume where the pixel's vertex falls -- F there is the residual, its gradient the normal
 //       k_icp_init      state := (T0, not lost, 0 iterations)
 //       k_icp_reduce    one pass over the current level: associate, residual and Jacobian row in f32, the 29 sums in f64 -> one slab per VIRTUAL workgroup
+//       k_icp_reduce_volume   the same pass against the volume: no projection and no reference pixel, the eight corners of the vertex's cell instead
 //       k_icp_solve     one workgroup: the slabs summed in a fixed order, 6 x 6 Cholesky in f64, T <- exp(xi) T, or LOST
 //       k_icp_publish   T -> the caller's buffer, the result block -> pinned host memory, sequence word last
 // Partials cross workgroups only at a kernel boundary (reduce | solve), with plain stores and plain loads: no atomics, no fences, no hand-off inside a launch.
@@ -19,6 +22,7 @@
 
 #include "common.h"
 #include "projection.h"
+#include "tsdf_gradient.h"
 
 namespace {
 
@@ -115,6 +119,37 @@ __global__ void k_icp_init(void *ws, const float *T) {
 // it into a branch behind the first use (it did both to the second reference pixel of a trip).
 #define ICP_PIN(f) asm volatile("" : "+v"((f).x), "+v"((f).y), "+v"((f).z), "+v"((f).w))
 
+// What the two reduce kernels share, each one statement of one thing.  icp_accumulate: a kept pixel's Jacobian row and residual into the 29 sums, every
+// product and every sum in f64.  icp_slab_tail: lanes -> wave (a fixed butterfly: every lane ends with the same sum) -> LDS -> the slab, waves in index order.
+__device__ __forceinline__ void icp_accumulate(double acc[ICP_SUMS], const float J[6], float r) {
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) { acc[e] = acc[e] + (double)J[i] * (double)J[j]; ++e; }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) acc[21 + i] = acc[21 + i] + (double)J[i] * (double)r;
+    acc[27] = acc[27] + (double)r * (double)r;
+    acc[28] = acc[28] + 1.0;
+}
+
+__device__ __forceinline__ void icp_slab_tail(double acc[ICP_SUMS], double (*s_part)[ICP_SLAB], double *slab) {
+#pragma unroll
+    for (int i = 0; i < ICP_SUMS; ++i) {
+        double s = acc[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
+        acc[i] = s;
+    }
+    __syncthreads();                                    // (the previous virtual workgroup's partials have been read)
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < ICP_SUMS; ++i) s_part[threadIdx.x >> 6][i] = acc[i];
+    }
+    __syncthreads();
+    if (threadIdx.x < ICP_SUMS) slab[threadIdx.x] = ((s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + s_part[2][threadIdx.x]) + s_part[3][threadIdx.x];
+}
+
 struct IcpReduce {
     const IcpPixel *ref[OVO_ICP_MAX_BATCH];                 // this level of every entry's reference: the table travels in the kernel arguments
     const IcpPixel *cur;
@@ -181,33 +216,108 @@ __global__ void __launch_bounds__(256) k_icp_reduce(const IcpReduce a) {
                 const float r = rn[k].x * dx + rn[k].y * dy + rn[k].z * dz;
                 const float J[6] = {P[k][1] * rn[k].z - P[k][2] * rn[k].y, P[k][2] * rn[k].x - P[k][0] * rn[k].z, P[k][0] * rn[k].y - P[k][1] * rn[k].x,
                                     rn[k].x, rn[k].y, rn[k].z};
-                int e = 0;
-#pragma unroll
-                for (int i = 0; i < 6; ++i)
-#pragma unroll
-                    for (int j = i; j < 6; ++j) { acc[e] = acc[e] + (double)J[i] * (double)J[j]; ++e; }
-#pragma unroll
-                for (int i = 0; i < 6; ++i) acc[21 + i] = acc[21 + i] + (double)J[i] * (double)r;
-                acc[27] = acc[27] + (double)r * (double)r;
-                acc[28] = acc[28] + 1.0;
+                icp_accumulate(acc, J, r);
             }
         }
-        // lanes -> wave (a fixed butterfly: every lane ends with the same sum) -> LDS -> the slab, waves in index order
+        icp_slab_tail(acc, s_part, slabs + (int64_t)vb * ICP_SLAB);
+    }
+}
+
+// ---- the reduce pass against a fused TSDF volume.  T is (volume frame <- current camera).  The pixel's vertex P falls into a cell
+// of the volume (tsdf_point_cell, the statement ovo_tsdf_sample_points uses); the trilinear blend f of the eight corners' F, times trunc, is the signed
+// distance to the surface -- the point-to-plane residual -- and the derivative of that same interpolant, from the same eight corners, its normal.
+// That gradient is NOT section 21's (central differences blended: up to 56 more loads a point): it costs no load and jumps across a cell face.
+// The same virtual workgroups, the same accumulation and the same tail as k_icp_reduce; k_icp_init, k_icp_solve and k_icp_publish run around it unchanged.
+#define ICP_PIN2(f) asm volatile("" : "+v"((f).x), "+v"((f).y))
+
+struct IcpReduceVolume {
+    const float2 *vol;
+    TsdfVol v;
+    const IcpPixel *cur;
+    int h, w;
+    float dist_th, cos_th;
+    void *ws;
+    int n_virtual;
+};
+
+// The eight corners are a gather: four pairs (x, x + 1) of 8-byte voxels, 16 bytes a pair, aligned to 8 (to 16 only where the base x is even and nx is too).
+// They are loaded for all ICP_ROWS pixels before any of them is used.  A dropped pixel (past the end, no vertex, no normal, not INSIDE) reads cell 0 --
+// voxels (0 .. 1)^3, which every volume has -- and is dropped again below: no branch around a load, and no address from a float that has not passed the test.
+__global__ void __launch_bounds__(256) k_icp_reduce_volume(const IcpReduceVolume a) {
+    __shared__ double s_part[4][ICP_SLAB];
+    const IcpState *st = icp_state(a.ws, 0);
+    if (st->lost) return;
+    double *slabs = icp_slabs(a.ws, 0);
+    float T[12];
 #pragma unroll
-        for (int i = 0; i < ICP_SUMS; ++i) {
-            double s = acc[i];
+    for (int i = 0; i < 12; ++i) T[i] = st->T[i];
+    const int64_t pixels = (int64_t)a.h * a.w, step = (int64_t)a.n_virtual * 256;
+    const int64_t sy = a.v.nx, sz = (int64_t)a.v.nx * a.v.ny;
+    for (int vb = blockIdx.x; vb < a.n_virtual; vb += gridDim.x) {
+        double acc[ICP_SUMS];
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
-            acc[i] = s;
+        for (int i = 0; i < ICP_SUMS; ++i) acc[i] = 0.0;
+        for (int64_t i0 = (int64_t)vb * 256 + threadIdx.x; i0 < pixels; i0 += ICP_ROWS * step) {
+            float4 cv[ICP_ROWS], cn[ICP_ROWS];
+            float2 c[ICP_ROWS][8];                         // corner x + 2 y + 4 z
+            float P[ICP_ROWS][3], N[ICP_ROWS][3], tt[ICP_ROWS][3];
+            int64_t at[ICP_ROWS];
+            bool ok[ICP_ROWS];
+#pragma unroll
+            for (int k = 0; k < ICP_ROWS; ++k) {
+                const int64_t i = i0 + k * step;
+                ok[k] = i < pixels;
+                const IcpPixel *q = a.cur + (ok[k] ? i : i0);       // (no branch around a load: a lane past the end re-reads its first pixel)
+                cv[k] = q->v; cn[k] = q->n;
+            }
+#pragma unroll
+            for (int k = 0; k < ICP_ROWS; ++k) { ICP_PIN(cv[k]); ICP_PIN(cn[k]); }      // (the normal's flag word was loaded apart, behind a branch)
+#pragma unroll
+            for (int k = 0; k < ICP_ROWS; ++k) {
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    P[k][r] = dot4(T + 4 * r, cv[k].x, cv[k].y, cv[k].z, 1.0f);
+                    N[k][r] = dot3(T + 4 * r, cn[k].x, cn[k].y, cn[k].z);
+                }
+                float bf[3];
+                const bool inside = tsdf_point_cell(a.v, P[k], bf, tt[k]);
+                ok[k] = ok[k] && flagged(cv[k].w) && flagged(cn[k].w) && inside;
+                // only a base cell that passed the test becomes an index: the select comes before the conversion
+                const int bx = (int)(ok[k] ? bf[0] : 0.0f), by = (int)(ok[k] ? bf[1] : 0.0f), bz = (int)(ok[k] ? bf[2] : 0.0f);
+                at[k] = ((int64_t)bz * a.v.ny + by) * a.v.nx + bx;
+            }
+#pragma unroll
+            for (int k = 0; k < ICP_ROWS; ++k) {
+                const float2 *q = a.vol + at[k];
+                c[k][0] = q[0]; c[k][1] = q[1]; c[k][2] = q[sy]; c[k][3] = q[sy + 1];
+                c[k][4] = q[sz]; c[k][5] = q[sz + 1]; c[k][6] = q[sz + sy]; c[k][7] = q[sz + sy + 1];
+            }
+#pragma unroll
+            for (int k = 0; k < ICP_ROWS; ++k)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) ICP_PIN2(c[k][e]);
+#pragma unroll
+            for (int k = 0; k < ICP_ROWS; ++k) {
+                const float F000 = c[k][0].x, F100 = c[k][1].x, F010 = c[k][2].x, F110 = c[k][3].x;
+                const float F001 = c[k][4].x, F101 = c[k][5].x, F011 = c[k][6].x, F111 = c[k][7].x;
+                const float tx = tt[k][0], ty = tt[k][1], tz = tt[k][2];
+                bool seen = true;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) seen &= c[k][e].y > 0.0f;
+                const float f = lerp1(lerp1(lerp1(F000, F100, tx), lerp1(F010, F110, tx), ty), lerp1(lerp1(F001, F101, tx), lerp1(F011, F111, tx), ty), tz);
+                const float g[3] = {lerp1(lerp1(F100 - F000, F110 - F010, ty), lerp1(F101 - F001, F111 - F011, ty), tz),
+                                    lerp1(lerp1(F010 - F000, F110 - F100, tx), lerp1(F011 - F001, F111 - F101, tx), tz),
+                                    lerp1(lerp1(F001 - F000, F101 - F100, tx), lerp1(F011 - F010, F111 - F110, tx), ty)};
+                float nq[3];
+                const bool has_normal = tsdf_unit(g, nq);
+                const float r = a.v.trunc * f;
+                const float cosang = N[k][0] * nq[0] + N[k][1] * nq[1] + N[k][2] * nq[2];
+                if (!(ok[k] && seen && fabsf(f) < 1.0f && has_normal && fabsf(r) <= a.dist_th && cosang >= a.cos_th)) continue;      // (NaN fails)
+                const float J[6] = {P[k][1] * nq[2] - P[k][2] * nq[1], P[k][2] * nq[0] - P[k][0] * nq[2], P[k][0] * nq[1] - P[k][1] * nq[0], nq[0], nq[1], nq[2]};
+                icp_accumulate(acc, J, r);
+            }
         }
-        __syncthreads();                                    // (the previous virtual workgroup's partials have been read)
-        if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-            for (int i = 0; i < ICP_SUMS; ++i) s_part[threadIdx.x >> 6][i] = acc[i];
-        }
-        __syncthreads();
-        if (threadIdx.x < ICP_SUMS)
-            slabs[(int64_t)vb * ICP_SLAB + threadIdx.x] = ((s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + s_part[2][threadIdx.x]) + s_part[3][threadIdx.x];
+        icp_slab_tail(acc, s_part, slabs + (int64_t)vb * ICP_SLAB);
     }
 }
 
@@ -387,20 +497,16 @@ extern "C" int ovo_icp_prepare(const float *depth, const ovo_icp_frame_t *frame,
 
 namespace {
 
-// Both entry points: everything is checked HERE, before anything is queued (the text of what is wrong, or null), then m alignments are queued.
-const char *icp_align_check(const void *const *refs, const ovo_icp_frame_t *ref, const void *cur_pyramid, const ovo_icp_frame_t *cur,
-                            const ovo_icp_align_t *align, int m, const float *T, const void *result_host, const void *ws, size_t ws_bytes) {
-    if (!(m >= 1 && m <= OVO_ICP_MAX_BATCH)) return "m outside 1 .. 16";
-    if (!(refs && ref && cur_pyramid && cur && align && T)) return "null pointer";
-    IcpLevel lv[ICP_MAX_LEVELS], lc[ICP_MAX_LEVELS];
-    if (!(icp_levels(*ref, lv) && icp_levels(*cur, lc)))
-        return "h, w >= 1, h * w <= 2^26, 1 <= levels <= 4 with a coarsest level of 3 x 3 or more, fx, fy, max_depth, depth_jump > 0";
-    if (!(ref->h == cur->h && ref->w == cur->w && ref->levels == cur->levels)) return "reference and current pyramid differ in size";
-    for (int k = 0; k < m; ++k)
-        if (!refs[k] || ((uintptr_t)refs[k] & 15) != 0) return "reference pyramid null or not 16-byte aligned";
+// Everything is checked HERE, before anything is queued (the text of what is wrong, or null).  icp_current_check: what every alignment asks of the
+// current frame, the settings, the pose, the result block and the workspace of m entries; icp_align_check: that, and the m reference pyramids.
+const char *icp_current_check(const void *cur_pyramid, const ovo_icp_frame_t *cur, const ovo_icp_align_t *align, int m, const float *T,
+                              const void *result_host, const void *ws, size_t ws_bytes) {
+    if (!(cur_pyramid && cur && align && T)) return "null pointer";
+    IcpLevel lc[ICP_MAX_LEVELS];
+    if (!icp_levels(*cur, lc)) return "h, w >= 1, h * w <= 2^26, 1 <= levels <= 4 with a coarsest level of 3 x 3 or more, fx, fy, max_depth, depth_jump > 0";
     if (((uintptr_t)cur_pyramid & 15) != 0 || ((uintptr_t)T & 3) != 0) return "pyramid not 16-byte aligned";
     int total = 0;
-    for (int k = 0; k < ref->levels; ++k) {
+    for (int k = 0; k < cur->levels; ++k) {
         if (!(align->iters[k] >= 0 && align->iters[k] <= ICP_MAX_ITERS)) return "iters outside 0 .. 64";
         total += align->iters[k];
     }
@@ -412,30 +518,54 @@ const char *icp_align_check(const void *const *refs, const ovo_icp_frame_t *ref,
     return nullptr;
 }
 
-int icp_align_queue(const void *const *refs, const ovo_icp_frame_t &fr, const void *cur_pyramid, const ovo_icp_align_t &a, int m, float *T,
-                    void *result_host, void *ws, hipStream_t st) {
+const char *icp_align_check(const void *const *refs, const ovo_icp_frame_t *ref, const void *cur_pyramid, const ovo_icp_frame_t *cur,
+                            const ovo_icp_align_t *align, int m, const float *T, const void *result_host, const void *ws, size_t ws_bytes) {
+    if (!(m >= 1 && m <= OVO_ICP_MAX_BATCH)) return "m outside 1 .. 16";
+    if (!(refs && ref)) return "null pointer";
     IcpLevel lv[ICP_MAX_LEVELS];
-    icp_levels(fr, lv);                                     // (reference and current frame have the same levels: checked)
+    if (!icp_levels(*ref, lv)) return "h, w >= 1, h * w <= 2^26, 1 <= levels <= 4 with a coarsest level of 3 x 3 or more, fx, fy, max_depth, depth_jump > 0";
+    if (const char *wrong = icp_current_check(cur_pyramid, cur, align, m, T, result_host, ws, ws_bytes)) return wrong;
+    if (!(ref->h == cur->h && ref->w == cur->w && ref->levels == cur->levels)) return "reference and current pyramid differ in size";
+    for (int k = 0; k < m; ++k)
+        if (!refs[k] || ((uintptr_t)refs[k] & 15) != 0) return "reference pyramid null or not 16-byte aligned";
+    return nullptr;
+}
+
+// The launches of m alignments of the frame `fr`: init, per level (coarse to fine) and iteration a reduce pass and a solve, publish.  `reduce(l, lv, n_virtual,
+// grid)` queues the reduce pass of level l -- the one thing in which an alignment to pyramids and an alignment to a volume differ.
+template <class Reduce>
+int icp_align_queue(const ovo_icp_frame_t &fr, const ovo_icp_align_t &a, int m, float *T, void *result_host, void *ws, hipStream_t st, const Reduce &reduce) {
+    IcpLevel lv[ICP_MAX_LEVELS];
+    icp_levels(fr, lv);                                     // (checked)
     k_icp_init<<<m, 64, 0, st>>>(ws, T);
     OVO_CHECK_LAUNCH();
     for (int k = 0; k < fr.levels; ++k) {                   // coarse to fine
         const int l = fr.levels - 1 - k;
-        IcpReduce r;
-        for (int e = 0; e < OVO_ICP_MAX_BATCH; ++e) r.ref[e] = e < m ? (const IcpPixel *)refs[e] + lv[l].first : nullptr;
-        r.cur = (const IcpPixel *)cur_pyramid + lv[l].first;
-        r.lv = lv[l]; r.dist2_th = a.dist_th * a.dist_th; r.cos_th = a.cos_th; r.ws = ws;
-        r.n_virtual = icp_virtual((int64_t)lv[l].h * lv[l].w);
-        const dim3 grid(icp_grid(r.n_virtual), m);
+        const int n_virtual = icp_virtual((int64_t)lv[l].h * lv[l].w);
+        const dim3 grid(icp_grid(n_virtual), m);
         for (int it = 0; it < a.iters[k]; ++it) {
-            k_icp_reduce<<<grid, 256, 0, st>>>(r);
+            reduce(l, lv[l], n_virtual, grid);
             OVO_CHECK_LAUNCH();
-            k_icp_solve<<<m, 256, 0, st>>>(ws, r.n_virtual, a.min_pairs >> (2 * l), (double)a.min_pivot_ratio);      // a level has a quarter of the pixels below it
+            k_icp_solve<<<m, 256, 0, st>>>(ws, n_virtual, a.min_pairs >> (2 * l), (double)a.min_pivot_ratio);      // a level has a quarter of the pixels below it
             OVO_CHECK_LAUNCH();
         }
     }
     k_icp_publish<<<m, 64, 0, st>>>(ws, T, (volatile long long *)result_host, (long long)a.seq);
     OVO_CHECK_LAUNCH();
     return OVO_OK;
+}
+
+// (reference and current frame have the same levels: checked)
+int icp_align_pyramids(const void *const *refs, const ovo_icp_frame_t &fr, const void *cur_pyramid, const ovo_icp_align_t &a, int m, float *T,
+                       void *result_host, void *ws, hipStream_t st) {
+    return icp_align_queue(fr, a, m, T, result_host, ws, st, [&](int l, const IcpLevel &lv, int n_virtual, dim3 grid) {
+        IcpReduce r;
+        for (int e = 0; e < OVO_ICP_MAX_BATCH; ++e) r.ref[e] = e < m ? (const IcpPixel *)refs[e] + lv.first : nullptr;
+        r.cur = (const IcpPixel *)cur_pyramid + lv.first;
+        r.lv = lv; r.dist2_th = a.dist_th * a.dist_th; r.cos_th = a.cos_th; r.ws = ws;
+        r.n_virtual = n_virtual;
+        k_icp_reduce<<<grid, 256, 0, st>>>(r);
+    });
 }
 
 }  // namespace
@@ -445,12 +575,29 @@ extern "C" int ovo_icp_align(const void *ref_pyramid, const ovo_icp_frame_t *ref
     OVO_REQUIRE(ref_pyramid, "null pointer");
     const char *wrong = icp_align_check(&ref_pyramid, ref, cur_pyramid, cur, align, 1, T, result_host, ws, ws_bytes);
     OVO_REQUIRE(!wrong, wrong);
-    return icp_align_queue(&ref_pyramid, *ref, cur_pyramid, *align, 1, T, result_host, ws, (hipStream_t)stream);
+    return icp_align_pyramids(&ref_pyramid, *ref, cur_pyramid, *align, 1, T, result_host, ws, (hipStream_t)stream);
 }
 
 extern "C" int ovo_icp_align_batch(const void *const *ref_pyramids, const ovo_icp_frame_t *ref, const void *cur_pyramid, const ovo_icp_frame_t *cur,
                                    const ovo_icp_align_t *align, int m, float *T, void *result_host, void *ws, size_t ws_bytes, ovo_stream_t stream) {
     const char *wrong = icp_align_check(ref_pyramids, ref, cur_pyramid, cur, align, m, T, result_host, ws, ws_bytes);
     OVO_REQUIRE(!wrong, wrong);
-    return icp_align_queue(ref_pyramids, *ref, cur_pyramid, *align, m, T, result_host, ws, (hipStream_t)stream);
+    return icp_align_pyramids(ref_pyramids, *ref, cur_pyramid, *align, m, T, result_host, ws, (hipStream_t)stream);
+}
+
+extern "C" int ovo_icp_align_volume(const void *vol, const ovo_tsdf_volume_t *desc, const void *cur_pyramid, const ovo_icp_frame_t *cur,
+                                    const ovo_icp_align_t *align, float *T, void *result_host, void *ws, size_t ws_bytes, ovo_stream_t stream) {
+    OVO_REQUIRE(vol && desc, "null pointer");
+    const char *wrong = tsdf_volume_check(desc);
+    OVO_REQUIRE(!wrong, wrong);
+    OVO_REQUIRE(((uintptr_t)vol & 15) == 0, "volume not 16-byte aligned");
+    wrong = icp_current_check(cur_pyramid, cur, align, 1, T, result_host, ws, ws_bytes);
+    OVO_REQUIRE(!wrong, wrong);
+    const ovo_icp_align_t a = *align;
+    const TsdfVol v = tsdf_vol(*desc);
+    hipStream_t st = (hipStream_t)stream;
+    return icp_align_queue(*cur, a, 1, T, result_host, ws, st, [&](int l, const IcpLevel &lv, int n_virtual, dim3 grid) {
+        const IcpReduceVolume r{(const float2 *)vol, v, (const IcpPixel *)cur_pyramid + lv.first, lv.h, lv.w, a.dist_th, a.cos_th, ws, n_virtual};
+        k_icp_reduce_volume<<<grid, 256, 0, st>>>(r);
+    });
 }

@@ -428,19 +428,11 @@ template <bool NORMALS, bool COLOR, int LABELS>
 __global__ void __launch_bounds__(256) k_tsdf_sample_points(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const int2 *__restrict__ lab, const TsdfVol v,
                                                             const float *__restrict__ points, int64_t n, int min_count, float *__restrict__ f_out,
                                                             float *__restrict__ normals_out, uint8_t *__restrict__ rgb_out, int32_t *__restrict__ ins_out) {
-    const float org[3] = {v.ox, v.oy, v.oz};
-    const int dim[3] = {v.nx, v.ny, v.nz};
     const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float pt[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
         float bf[3], tt[3];
-        bool inside = true;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float g = (points[3 * i + a] - org[a]) / v.voxel;
-            bf[a] = floorf(g);
-            tt[a] = g - bf[a];
-            inside &= (bf[a] >= 0.0f) & (bf[a] <= (float)(dim[a] - 2));      // (NaN and the infinities fail)
-        }
+        const bool inside = tsdf_point_cell(v, pt, bf, tt);      // (tsdf_desc.h: NaN and the infinities fail)
         float f = 2.0f, nrm[3] = {0.0f, 0.0f, 0.0f}, rgbf[3] = {0.0f, 0.0f, 0.0f};
         int label = -1;
         if (inside) {                                      // only now does a float become an index

@@ -36,10 +36,11 @@ __device__ __forceinline__ void tsdf_gradient(const float2 *__restrict__ vol, co
     }
 }
 
-// unit(g): products first, then the two sums left to right; three +0.0f unless the length is positive and finite.
-__device__ __forceinline__ void tsdf_unit(const float g[3], float out[3]) {
+// unit(g): products first, then the two sums left to right; three +0.0f unless the length is positive and finite.  Returns whether it is.
+__device__ __forceinline__ bool tsdf_unit(const float g[3], float out[3]) {
     const float len = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
     const bool ok = len > 0.0f && len < INFINITY;            // (NaN fails)
 #pragma unroll
     for (int a = 0; a < 3; ++a) out[a] = ok ? g[a] / len : 0.0f;
+    return ok;
 }

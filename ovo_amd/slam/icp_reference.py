@@ -1,18 +1,20 @@
-"""What `IcpTracker` aligns a frame to: the last keyframe's depth image (`KeyframeReference`, section 15) or a fused TSDF
-volume ray-cast at the last good pose (`TsdfReference`, section 17).  The tracker's frame loop is the same for both; a reference answers only what
-differs, through the same attributes and methods:
+"""What `IcpTracker` aligns a frame to: the last keyframe's depth image (`KeyframeReference`, section 15), a fused TSDF
+volume ray-cast at the last good pose (`TsdfReference`, section 17), or that volume itself (`VolumeReference`, section 25).  The tracker's frame loop
+is the same for all three; a reference answers only what differs, through the same attributes and methods:
 
     frame                    the prepared `Frame` the next alignment runs against
     spare                    the pyramid buffer the next frame is written into (None: a new one); a LOST frame's own, set by the tracker
     start(depth, aligner, t) the first frame (time stamp t), at the identity pose; `TsdfReference(color=True)` takes rgb= here and in `tracked`
     aim(aligner)             the device start pose before an alignment is queued
+    queue(aligner, cur, ...) queues the alignment of `cur` with the tracker's settings: `aligner.queue` against `frame`, or `aligner.queue_volume`
     compose(c2w, kf_c2w, T)  an alignment's result T -> (the frame's pose, the pose relative to the keyframe that `keyframe_decision` takes)
     tracked(cur, depth, c2w, is_kf, aligner, t=None, kf=0, relative=None)   after an OK frame at pose c2w (time stamp t, hanging on keyframe kf at
                              `relative`); returns the outgoing keyframe's `Frame` when there is one
     corrected(X, c2w)        after a loop closure moved the keyframes to X (f64) and this frame to c2w
 
-`prepare(depth, out)` is the tracker's `prepare_frame` with its own intrinsics and thresholds.  The two forms of `compose` ARE the contract
-(tests/icp_restatement.py, tests/tsdf_restatement.py): each is kept one operation at a time, and they are not to be unified."""
+`prepare(depth, out)` is the tracker's `prepare_frame` with its own intrinsics and thresholds.  The three forms of `compose` ARE the contract
+(tests/icp_restatement.py, tests/tsdf_restatement.py, tests/sdf_align_restatement.py): each is kept one operation at a time, and they are not to
+be unified."""
 from __future__ import annotations
 
 import numpy as np
@@ -38,6 +40,9 @@ class KeyframeReference:
 
     def aim(self, aligner) -> None:
         pass                                               # carried: the last alignment left its result there
+
+    def queue(self, aligner, cur, *settings) -> int:
+        return aligner.queue(self.frame, cur, *settings)
 
     def compose(self, c2w, kf_c2w, T):
         return (kf_c2w @ T).astype(np.float32), T          # an f32 product; the keyframe is decided on T itself
@@ -107,6 +112,9 @@ class TsdfReference:
     def aim(self, aligner) -> None:
         aligner.T.copy_(self._eye)                         # device to device: no host wait
 
+    def queue(self, aligner, cur, *settings) -> int:
+        return aligner.queue(self.frame, cur, *settings)
+
     def compose(self, c2w, kf_c2w, T):
         c2w = (c2w.astype(np.float64) @ T.astype(np.float64)).astype(np.float32)      # an f64 product, rounded once
         return c2w, U.rigid_inverse(kf_c2w) @ c2w.astype(np.float64)
@@ -175,3 +183,37 @@ class TsdfReference:
     def _cast(self, c2w) -> None:
         self.model_depth = self.volume.raycast(self.K, self._hw[0], self._hw[1], c2w, self.near, self.far, out=self.model_depth)
         self.frame = self.prepare(self.model_depth, None if self.frame is None else self.frame.pyramid)
+
+
+class VolumeReference(TsdfReference):
+    """Every frame against the volume ITSELF (`ovo_icp_align_volume`): the trilinear F where a pixel's vertex falls, times trunc,
+    is the residual and the gradient of F the normal, so nothing is ray-cast in the frame loop, no model image is prepared, and `model_depth` and
+    `frame` stay None.  The device pose IS the frame's pose in the volume's frame -- that of the first camera -- and is carried from frame to frame as
+    `KeyframeReference` carries its own: an OK alignment leaves c2w there, a LOST one restores it, `aim` does nothing.  Everything else -- fusing, the
+    history, colour, labels, `cast_at`, `render` -- is `TsdfReference`'s.  Limit: the residual exists only within trunc of the surface (|F| < 1), so a
+    start pose further off than that pairs nothing and is LOST, where the ray-cast form with its dist_th reaches further."""
+
+    def start(self, depth, aligner, t=None, rgb=None) -> None:
+        self._aligner = aligner                            # `corrected` and `relocalised` set the device pose and are not handed it
+        super().start(depth, aligner, t, rgb)
+        aligner.set_pose(EYE)
+
+    def aim(self, aligner) -> None:
+        pass                                               # carried: the last alignment left its result there, or restored it
+
+    def queue(self, aligner, cur, *settings) -> int:
+        return aligner.queue_volume(self.volume, cur, *settings)
+
+    def compose(self, c2w, kf_c2w, T):
+        return T, U.rigid_inverse(kf_c2w) @ T.astype(np.float64)      # c2w = T, no product; the keyframe is decided on inv(kf_c2w) @ c2w in f64
+
+    def corrected(self, X, c2w) -> None:
+        super().corrected(X, c2w)                          # the volume fused again from the history
+        self._aligner.set_pose(c2w)
+
+    def relocalised(self, c2w, cur) -> None:
+        super().relocalised(c2w, cur)
+        self._aligner.set_pose(c2w)
+
+    def _cast(self, c2w) -> None:
+        pass                                               # the frame loop needs no model image (`cast_at` and `render` cast on demand)

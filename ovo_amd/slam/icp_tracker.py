@@ -14,6 +14,9 @@ what differs between the two:
 `model="tsdf"`: frame to MODEL (`TsdfReference`) -- every tracked frame is fused into a dense TSDF volume
 (utils/tsdf_utils.py, csrc/tsdf.hip), and a frame is aligned to the volume's ray-cast depth image from the last good pose.
 
+`model="tsdf", tsdf_align="volume"`: frame to the volume ITSELF (`VolumeReference`) -- the signed distance where a pixel's
+vertex falls is the residual and its gradient the normal (`ovo_icp_align_volume`); nothing is ray-cast and no model image prepared in the frame loop.
+
 `close_loops=True` adds loop detection, verification and correction on keyframes (`LoopCloser`, slam/loop_closer.py): the
 new keyframe is aligned against the old keyframes its own pose estimate puts nearby -- all of them in the launches of one alignment
 (`ovo_icp_align_batch`) -- the ones that pass become edges of a pose graph (slam/pose_graph.py), and when the optimised graph moves a keyframe
@@ -27,7 +30,7 @@ import torch
 
 from ..utils import icp_utils as U
 from ..utils.tsdf_utils import MAX_HISTORY
-from .icp_reference import KeyframeReference, TsdfReference
+from .icp_reference import KeyframeReference, TsdfReference, VolumeReference
 from .keyframe_store import KeyframeStore
 from .loop_closer import LoopCloser
 from .relocaliser import Relocaliser
@@ -47,7 +50,7 @@ class IcpTracker:
                  tsdf_color: bool = False, tsdf_labels: bool = False, relocalise: bool = False, fern_count: int = 256, fern_seed: int = 0,
                  fern_tau=(0.3, None), reloc_max_candidates: int = 4, reloc_max_dissimilarity: float = 0.3, reloc_iters=None, reloc_dist_th: float = 0.2,
                  reloc_min_overlap: float = 0.3, reloc_max_rms: float = 0.02, reloc_max_keyframes: int = 256, loop_candidates: str = "pose",
-                 loop_max_dissimilarity: float = 0.3) -> None:
+                 loop_max_dissimilarity: float = 0.3, tsdf_align: str = "raycast") -> None:
         """No GPU work happens here: buffers are made with the first frame.  The loop_* parameters are read and checked by `LoopCloser`, the
         tsdf_* parameters by `TsdfReference`, whichever mode is chosen.
 
@@ -85,6 +88,16 @@ class IcpTracker:
         history).  The frame loop never touches it: `fuse_labels(ins)` votes a keyframe's instance image (`OVO.instance_image`) into it,
         `render_model(labels=True)` and `extract_mesh(labels=True)` read it back, `volume.remap_labels(OVO.last_instance_table)` follows the map's
         merges.  Poses, the volume and the model image are bit-identical with it on or off.
+
+        tsdf_align (model="tsdf" only): "raycast" (the default: all of the above) or "volume" -- a frame is aligned to the
+        volume itself (`ovo_icp_align_volume`): per pixel the trilinear F at its vertex, times trunc, is the point-to-plane residual and the
+        normalised gradient of F the plane normal.  The first frame is fused and nothing is cast; the device pose is the frame's pose in the volume's
+        frame (the first camera's), carried from frame to frame: c2w = T with no product, an OK frame is fused at it, a LOST one restores it.
+        `model_depth` stays None; keyframes are decided on inv(kf_c2w) @ c2w and the pairs against the volume.  A re-fusion after a loop closure
+        and a relocalisation set the device pose to the corrected / found pose.  tsdf_color, tsdf_labels, tsdf_history, close_loops, relocalise,
+        `extract_mesh`, `sample_model` and `render_model` work as with "raycast".  Limit: the residual exists only where |F| < 1, within
+        tsdf_trunc of the surface -- a start pose further off than that pairs nothing and is LOST, where "raycast" with its dist_th reaches further.
+        Anything else raises ValueError, and so does "volume" with model="keyframe".
 
         relocalise: every frame's fern code -- fern_count ferns (a multiple of 8) of 4 depth tests over the coarsest pyramid
         level, pixels and thresholds drawn from fern_seed, thresholds uniform in fern_tau metres (None: max_depth / 2) -- is searched against the
@@ -140,7 +153,12 @@ class IcpTracker:
         self.tsdf_labels = bool(tsdf_labels)
         if self.tsdf_labels and self.model != "tsdf":
             raise ValueError("IcpTracker: tsdf_labels votes instance labels into the volume and needs model='tsdf'")
-        tsdf = TsdfReference(self._prepare, self.K, self.max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far,
+        self.tsdf_align = str(tsdf_align)
+        if self.tsdf_align not in ("raycast", "volume"):
+            raise ValueError(f"IcpTracker: tsdf_align must be 'raycast' or 'volume' (got {tsdf_align!r})")
+        if self.tsdf_align == "volume" and self.model != "tsdf":
+            raise ValueError("IcpTracker: tsdf_align='volume' aligns to the fused volume and needs model='tsdf'")
+        tsdf = (VolumeReference if self.tsdf_align == "volume" else TsdfReference)(self._prepare, self.K, self.max_depth, tsdf_dims, tsdf_voxel, tsdf_origin, tsdf_trunc, tsdf_max_weight, tsdf_near, tsdf_far,
                              history=self.tsdf_history, color=self.tsdf_color, **({"labels": True} if self.tsdf_labels else {}))
         self.tsdf_trunc, self.tsdf_far = tsdf.trunc, tsdf.far
         self._ref = tsdf if self.model == "tsdf" else KeyframeReference(self._prepare)
@@ -214,7 +232,7 @@ class IcpTracker:
         if self._use_ferns:                                # code and search in front of the alignment: their block is there when the alignment's is
             n = len(self._keyframes)                       # the index this frame would get as a keyframe
             self._ferns.queue(cur, [n - self._loops.min_gap + 1, n] if self._loop_ferns else [n])
-        seq = self._aligner.queue(ref.frame, cur, self.iters, self.dist_th, self.normal_th_deg, min_pairs, self.min_pivot_ratio)
+        seq = ref.queue(self._aligner, cur, self.iters, self.dist_th, self.normal_th_deg, min_pairs, self.min_pivot_ratio)      # against its frame, or its volume
         self.last = res = self._aligner.wait(seq)
         matches = self._ferns.matches() if self._use_ferns else None
         self._is_kf = False

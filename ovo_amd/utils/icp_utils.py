@@ -227,8 +227,28 @@ class Aligner:
                                        C.c_void_p(slot), L.ptr(self.ws), self.ws.numel(), L.stream()))
         return seq
 
+    def queue_volume(self, volume, cur: Frame, iters, dist_th, normal_th_deg, min_pairs, min_pivot_ratio) -> int:
+        """`queue` with a fused TSDF volume (`tsdf_utils.TsdfVolume`) as the reference (`ovo_icp_align_volume`): T is
+        (volume frame <- current camera), read and advanced in place.  The volume is only read."""
+        if len(iters) != cur.levels:
+            raise L.OvoHipError(f"align_volume: {len(iters)} entries in iters for {cur.levels} levels")
+        L.dev(volume.vol, torch.float32, "volume")
+        seq, slot = self.ring.next()
+        desc = align_desc(iters, dist_th, normal_th_deg, min_pairs, min_pivot_ratio, seq)
+        L.check(L.load().ovo_icp_align_volume(L.ptr(volume.vol), C.byref(volume.desc), L.ptr(cur.pyramid), C.byref(cur.desc), C.byref(desc), L.ptr(self.T),
+                                              C.c_void_p(slot), L.ptr(self.ws), self.ws.numel(), L.stream()))
+        return seq
+
     def wait(self, seq: int) -> Dict[str, Any]:
         return decode_result(self.ring.wait(seq))
+
+
+def align_volume(volume, cur: Frame, T0, iters=(10, 5, 4), dist_th: float = 0.1, normal_th_deg: float = 30.0, min_pairs: int = 1,
+                 min_pivot_ratio: float = 1e-6, aligner: Optional[Aligner] = None) -> Dict[str, Any]:
+    """One alignment of a frame to a fused volume, start to result: T0 (4 x 4, volume frame <- current camera) -> what `align` returns.  One host wait."""
+    aligner = aligner or Aligner(cur.pyramid.device)
+    aligner.set_pose(T0)
+    return aligner.wait(aligner.queue_volume(volume, cur, iters, dist_th, normal_th_deg, min_pairs, min_pivot_ratio))
 
 
 def align(ref: Frame, cur: Frame, T0, iters=(10, 5, 4), dist_th: float = 0.1, normal_th_deg: float = 30.0, min_pairs: int = 1,
