@@ -22,7 +22,7 @@
 
 #include "common.h"
 #include "projection.h"
-#include "tsdf_gradient.h"
+#include "tsdf_cell.h"
 
 namespace {
 
@@ -224,12 +224,10 @@ __global__ void __launch_bounds__(256) k_icp_reduce(const IcpReduce a) {
 }
 
 // ---- the reduce pass against a fused TSDF volume.  T is (volume frame <- current camera).  The pixel's vertex P falls into a cell
-// of the volume (tsdf_point_cell, the statement ovo_tsdf_sample_points uses); the trilinear blend f of the eight corners' F, times trunc, is the signed
-// distance to the surface -- the point-to-plane residual -- and the derivative of that same interpolant, from the same eight corners, its normal.
+// of the volume (tsdf_cell.h: the cell, the corners, SEEN and the blend are the statements the ray cast and the sampler call); the blend f of the eight
+// corners' F, times trunc, is the signed distance to the surface -- the point-to-plane residual -- and the derivative of that same interpolant, from the same eight corners, its normal.
 // That gradient is NOT section 21's (central differences blended: up to 56 more loads a point): it costs no load and jumps across a cell face.
 // The same virtual workgroups, the same accumulation and the same tail as k_icp_reduce; k_icp_init, k_icp_solve and k_icp_publish run around it unchanged.
-#define ICP_PIN2(f) asm volatile("" : "+v"((f).x), "+v"((f).y))
-
 struct IcpReduceVolume {
     const float2 *vol;
     TsdfVol v;
@@ -240,9 +238,8 @@ struct IcpReduceVolume {
     int n_virtual;
 };
 
-// The eight corners are a gather: four pairs (x, x + 1) of 8-byte voxels, 16 bytes a pair, aligned to 8 (to 16 only where the base x is even and nx is too).
-// They are loaded for all ICP_ROWS pixels before any of them is used.  A dropped pixel (past the end, no vertex, no normal, not INSIDE) reads cell 0 --
-// voxels (0 .. 1)^3, which every volume has -- and is dropped again below: no branch around a load, and no address from a float that has not passed the test.
+// The eight corners (tsdf_corners: four x-pairs, 16 bytes a pair, aligned to 8) are loaded for all ICP_ROWS pixels before any of them is used.  A dropped pixel (past the end,
+// no vertex, no normal, not INSIDE) reads cell 0 -- which every volume has -- and is dropped again below: no branch around a load, and no address from a float that has not passed the test.
 __global__ void __launch_bounds__(256) k_icp_reduce_volume(const IcpReduceVolume a) {
     __shared__ double s_part[4][ICP_SLAB];
     const IcpState *st = icp_state(a.ws, 0);
@@ -252,7 +249,6 @@ __global__ void __launch_bounds__(256) k_icp_reduce_volume(const IcpReduceVolume
 #pragma unroll
     for (int i = 0; i < 12; ++i) T[i] = st->T[i];
     const int64_t pixels = (int64_t)a.h * a.w, step = (int64_t)a.n_virtual * 256;
-    const int64_t sy = a.v.nx, sz = (int64_t)a.v.nx * a.v.ny;
     for (int vb = blockIdx.x; vb < a.n_virtual; vb += gridDim.x) {
         double acc[ICP_SUMS];
 #pragma unroll
@@ -280,34 +276,27 @@ __global__ void __launch_bounds__(256) k_icp_reduce_volume(const IcpReduceVolume
                     N[k][r] = dot3(T + 4 * r, cn[k].x, cn[k].y, cn[k].z);
                 }
                 float bf[3];
+                int b[3];
                 const bool inside = tsdf_point_cell(a.v, P[k], bf, tt[k]);
                 ok[k] = ok[k] && flagged(cv[k].w) && flagged(cn[k].w) && inside;
                 // only a base cell that passed the test becomes an index: the select comes before the conversion
-                const int bx = (int)(ok[k] ? bf[0] : 0.0f), by = (int)(ok[k] ? bf[1] : 0.0f), bz = (int)(ok[k] ? bf[2] : 0.0f);
-                at[k] = ((int64_t)bz * a.v.ny + by) * a.v.nx + bx;
+#pragma unroll
+                for (int r = 0; r < 3; ++r) bf[r] = ok[k] ? bf[r] : 0.0f;
+                at[k] = tsdf_cell_at(a.v, bf, b);
             }
 #pragma unroll
-            for (int k = 0; k < ICP_ROWS; ++k) {
-                const float2 *q = a.vol + at[k];
-                c[k][0] = q[0]; c[k][1] = q[1]; c[k][2] = q[sy]; c[k][3] = q[sy + 1];
-                c[k][4] = q[sz]; c[k][5] = q[sz + 1]; c[k][6] = q[sz + sy]; c[k][7] = q[sz + sy + 1];
-            }
+            for (int k = 0; k < ICP_ROWS; ++k) tsdf_corners(a.vol, a.v, at[k], c[k]);
 #pragma unroll
-            for (int k = 0; k < ICP_ROWS; ++k)
-#pragma unroll
-                for (int e = 0; e < 8; ++e) ICP_PIN2(c[k][e]);
+            for (int k = 0; k < ICP_ROWS; ++k) tsdf_pin8(c[k]);
 #pragma unroll
             for (int k = 0; k < ICP_ROWS; ++k) {
-                const float F000 = c[k][0].x, F100 = c[k][1].x, F010 = c[k][2].x, F110 = c[k][3].x;
-                const float F001 = c[k][4].x, F101 = c[k][5].x, F011 = c[k][6].x, F111 = c[k][7].x;
+                float F[8];                                // corner x + 2 y + 4 z
+                const bool seen = tsdf_seen8(c[k], F);
                 const float tx = tt[k][0], ty = tt[k][1], tz = tt[k][2];
-                bool seen = true;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) seen &= c[k][e].y > 0.0f;
-                const float f = lerp1(lerp1(lerp1(F000, F100, tx), lerp1(F010, F110, tx), ty), lerp1(lerp1(F001, F101, tx), lerp1(F011, F111, tx), ty), tz);
-                const float g[3] = {lerp1(lerp1(F100 - F000, F110 - F010, ty), lerp1(F101 - F001, F111 - F011, ty), tz),
-                                    lerp1(lerp1(F010 - F000, F110 - F100, tx), lerp1(F011 - F001, F111 - F101, tx), tz),
-                                    lerp1(lerp1(F001 - F000, F101 - F100, tx), lerp1(F011 - F010, F111 - F110, tx), ty)};
+                const float f = trilerp(F, tt[k]);
+                const float g[3] = {lerp1(lerp1(F[1] - F[0], F[3] - F[2], ty), lerp1(F[5] - F[4], F[7] - F[6], ty), tz),
+                                    lerp1(lerp1(F[2] - F[0], F[3] - F[1], tx), lerp1(F[6] - F[4], F[7] - F[5], tx), tz),
+                                    lerp1(lerp1(F[4] - F[0], F[5] - F[1], tx), lerp1(F[6] - F[2], F[7] - F[3], tx), ty)};
                 float nq[3];
                 const bool has_normal = tsdf_unit(g, nq);
                 const float r = a.v.trunc * f;

@@ -31,8 +31,7 @@
 
 #include "common.h"
 #include "mesh_table.h"
-#include "tsdf_desc.h"
-#include "tsdf_gradient.h"
+#include "tsdf_cell.h"
 
 namespace {
 
@@ -280,7 +279,8 @@ struct MeshLabel {                                         // k_mesh_labels: the
         const int2 lq = pl[off];
         const bool p_near = t < 0.5f;                        // (a NaN t: q)
         const int2 a = p_near ? lp : lq, o = p_near ? lq : lp;
-        ins[vi] = a.x > 0 && a.y >= min_count ? a.x - 1 : (o.x > 0 && o.y >= min_count ? o.x - 1 : -1);
+        const int id = tsdf_label_id(a, min_count);          // (tsdf_cell.h: the ray cast's and the sampler's rule)
+        ins[vi] = id >= 0 ? id : tsdf_label_id(o, min_count);
     }
 };
 

@@ -5,33 +5,30 @@
 //                                volume beside the first; a voxel's colour is updated exactly when its (F, W) is, from the pixel
 //                                the depth was read at
 //   ovo_tsdf_raycast[_color | _normals]   k_tsdf_raycast<COLOR, NORMALS, LABELS>   one launch, one thread per pixel, 16 x 16 pixel tiles: a fixed-step march,
-//                                trilinear samples.  At a hit, COLOR: 16 eight-byte colour loads and three blends per channel; NORMALS (DESIGN.md
-//                                section 21): the gradient of F (tsdf_gradient.h) at the eight corners of the two bracketing samples, blended as F
-//                                is, normalised
+//                                trilinear samples.  At a hit, COLOR: the colour blends of the two bracketing samples; NORMALS:
+//                                the gradient of F (tsdf_gradient.h) at their eight corners each, blended as F is, normalised
 //   ovo_tsdf_integrate_labels    k_tsdf_integrate<V, TSDF_LABELS>    the same items and the same tsdf_sample, over a label array
 //                                int2 [nz][ny][nx] = (L, C) alone: a voxel whose sample is f < 1 and whose pixel carries an instance id votes, in
 //                                integers; `vol` is neither read nor written
 //   ovo_tsdf_raycast_labels      k_tsdf_raycast<false, false, true>   the same march; at a hit the label of the one voxel nearest to the surface point
 //   ovo_tsdf_labels_remap        k_tsdf_labels_remap   a grid-stride pass over voxel pairs: L <- table[L - 1] + 1, stored only where it changes
 //   ovo_tsdf_sample_points       k_tsdf_sample_points<NORMALS, COLOR, LABELS>    the volume read at arbitrary points: one launch, one
-//                                thread a point, grid-stride; the ray cast's sample, gradient, colour and label expressions on a GIVEN position, and
-//                                a count-weighted vote of the eight corners' labels; reads only
+//                                thread a point, grid-stride; a count-weighted vote of the eight corners' labels besides the nearest one; reads only
+// A cell and what is read from it (tsdf_cell.h: each thing stated once) is the same code for the ray cast, on a ray's sample k, and the sampler, on a GIVEN position.
 // The volume is float2 [nz][ny][nx] = (F, W), x fastest; all-zero bytes are "unobserved".  The colour volume is uint2 [nz][ny][nx] (four u16: R, G, B,
 // spare) with the volume's indexing.  No atomics, no cross-thread traffic: every result is a pure function of the inputs, bit-equal from run to run
 // and whatever OVO_TSDF_GRID_CAP says (it only changes which workgroup visits a voxel).
 // Every index is in range by construction.  Integrate: the box is checked against the volume on the host, one `idx` is added to both bases, and every
-// `rgb` address is formed from the (v, u) that tsdf_sample has tested against the image.  Ray cast: tsdf_cell tests a sample's base cell against
-// [0, n - 2] on all three axes and the march forms an address only after it passes; colour and gradient are read only at a hit, around the base cells
-// of the samples k - 1 and k, which both passed that test and are formed again by the same tsdf_cell (tsdf_cell_index says why that is safe); a
-// corner's neighbour is addressed only after its index has passed the test against [0, n) (tsdf_gradient); all three outputs are written at the one
-// pixel (pv, pu) that was tested against the image.
+// `rgb` address is formed from the (v, u) that tsdf_sample has tested against the image.  Ray cast and sampler: tsdf_point_cell tests a base cell against
+// [0, n - 2] on all three axes and an address is formed only after it passes (tsdf_cell_at); colour, gradient and label are read only around such a cell
+// -- at a hit those of the samples k - 1 and k, formed again by the same tsdf_cell (tsdf_cell_index says why that is safe); a corner's neighbour is addressed
+// only after its index has passed the test against [0, n) (tsdf_gradient); every output is written at the one pixel or point index that was tested.
 // This file is compiled with -ffp-contract=off (projection.h): f32 operations are single IEEE operations in the order written, except the dot3 / dot4 chains.
 #include <math.h>
 
 #include "common.h"
 #include "projection.h"
-#include "tsdf_desc.h"
-#include "tsdf_gradient.h"
+#include "tsdf_cell.h"
 
 namespace {
 
@@ -182,78 +179,48 @@ __global__ void __launch_bounds__(256) k_tsdf_integrate(float2 *__restrict__ vol
     }
 }
 
-// The samples of pixel (v, u) lie at z_k = near + k dz, k = 0 .. kmax, at t0 + z_k dw in the volume's frame.  tsdf_cell: sample k's base cell `bf`
-// (whole numbers, as floats) and its trilinear weights `tt`; returns whether the base cell lies in [0, n - 2] on all three axes, i.e. whether all
-// eight corners are voxels.  The march and the reads at a hit share this one statement of the expressions: a sample formed again is formed by the
-// same IEEE operations on the same values, which is what the bit-equality of depth, colour and normals across the four kernels rests on.
+// The samples of pixel (v, u) lie at z_k = near + k dz, k = 0 .. kmax, at t0 + z_k dw in the volume's frame.  tsdf_cell: sample k's position and its cell.  A
+// sample formed again at a hit is formed by the same IEEE operations on the same values: the bit-equality of depth, colour and normals across the kernels rests on it.
 __device__ __forceinline__ bool tsdf_cell(const TsdfVol &v, const TsdfCam &c, float dz, int k, const float t0[3], const float dw[3], float bf[3], float tt[3]) {
-    const float org[3] = {v.ox, v.oy, v.oz};
-    const int n[3] = {v.nx, v.ny, v.nz};
     const float zk = c.near + (float)k * dz;
-    bool inside = true;
+    float pos[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float pos = t0[a] + zk * dw[a];
-        const float g = (pos - org[a]) / v.voxel;
-        bf[a] = floorf(g);
-        tt[a] = g - bf[a];
-        inside &= (bf[a] >= 0.0f) & (bf[a] <= (float)(n[a] - 2));            // (NaN and the infinities fail; no short circuit: all three axes are computed anyway)
-    }
-    return inside;
+    for (int a = 0; a < 3; ++a) pos[a] = t0[a] + zk * dw[a];
+    return tsdf_point_cell(v, pos, bf, tt);
 }
 
-// The base cell of a sample as an index triple, for the reads at a hit.  They are only made for a sample the march found valid: the base cell is then
-// in [0, n - 2] already, and the clamp is a no-op that keeps every address in range without a second verdict to act on.
-__device__ __forceinline__ void tsdf_cell_index(const TsdfVol &v, const TsdfCam &c, float dz, int k, const float t0[3], const float dw[3], int b[3], float tt[3]) {
+// The base cell of a sample as an index triple and a linear index, for the reads at a hit.  They are only made for a sample the march found valid: the
+// base cell is then in [0, n - 2] already, and the clamp is a no-op that keeps every address in range without a second verdict to act on.
+__device__ __forceinline__ int64_t tsdf_cell_index(const TsdfVol &v, const TsdfCam &c, float dz, int k, const float t0[3], const float dw[3], int b[3], float tt[3]) {
     const int n[3] = {v.nx, v.ny, v.nz};
     float bf[3];
     tsdf_cell(v, c, dz, k, t0, dw, bf, tt);
 #pragma unroll
-    for (int a = 0; a < 3; ++a) b[a] = (int)fminf(fmaxf(bf[a], 0.0f), (float)(n[a] - 2));
+    for (int a = 0; a < 3; ++a) bf[a] = fminf(fmaxf(bf[a], 0.0f), (float)(n[a] - 2));
+    return tsdf_cell_at(v, bf, b);
 }
 
-// The three channels of sample k of a ray, each the trilinear blend of the eight corners' (float) q with the sample's own t, along x, then y, then z.
-__device__ __forceinline__ void tsdf_cell_color(const uint2 *__restrict__ col, const TsdfVol &v, const TsdfCam &c, float dz, int k, const float t0[3],
-                                                const float dw[3], float out[3]) {
-    float tt[3];
+// Gradient (NORMALS) and colour (COLOR) at sample k of a ray: the sample's cell formed again, then what tsdf_cell.h reads at a given (cell, t).
+template <bool COLOR, bool NORMALS>
+__device__ __forceinline__ void tsdf_cell_read(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol &v, const TsdfCam &c, float dz, int k,
+                                               const float t0[3], const float dw[3], float rgb[3], float grad[3]) {
+    float tt[3], F[8];
     int b[3];
-    tsdf_cell_index(v, c, dz, k, t0, dw, b, tt);
-    const uint2 *p = col + ((int64_t)b[2] * v.ny + b[1]) * v.nx + b[0];
-    const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
-    const uint2 c000 = p[0], c100 = p[1], c010 = p[sy], c110 = p[sy + 1], c001 = p[sz], c101 = p[sz + 1], c011 = p[sz + sy], c111 = p[sz + sy + 1];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-        out[ch] = lerp1(lerp1(lerp1(color_channel(c000, ch), color_channel(c100, ch), tt[0]), lerp1(color_channel(c010, ch), color_channel(c110, ch), tt[0]), tt[1]),
-                        lerp1(lerp1(color_channel(c001, ch), color_channel(c101, ch), tt[0]), lerp1(color_channel(c011, ch), color_channel(c111, ch), tt[0]), tt[1]),
-                        tt[2]);
-}
-
-// The gradient at sample k of a ray: each component the trilinear blend (x, then y, then z, the sample's own t) of grad(corner; W > 0) over the eight
-// corners.
-__device__ __forceinline__ void tsdf_cell_gradient(const float2 *__restrict__ vol, const TsdfVol &v, const TsdfCam &c, float dz, int k, const float t0[3],
-                                                   const float dw[3], float out[3]) {
-    float tt[3];
-    int b[3];
-    tsdf_cell_index(v, c, dz, k, t0, dw, b, tt);
-    float gc[8][3];                                          // corner x + 2 y + 4 z; every index below is a compile-time constant
-#pragma unroll
-    for (int cn = 0; cn < 8; ++cn) {
-        const int i = b[0] + (cn & 1), j = b[1] + (cn >> 1 & 1), kk = b[2] + (cn >> 2);      // within [0, n - 1]
-        const float Fp = vol[((int64_t)kk * v.ny + j) * v.nx + i].x;
-        tsdf_gradient(vol, v, i, j, kk, Fp, TsdfSeen{}, gc[cn]);
+    float2 cn[8];
+    const int64_t at = tsdf_cell_index(v, c, dz, k, t0, dw, b, tt);
+    if (NORMALS) {
+        tsdf_corners(vol, v, at, cn);
+        tsdf_seen8(cn, F);                                   // (seen: the march found this sample valid)
+        tsdf_gradient_at(vol, v, b, tt, F, grad);
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-        out[a] = lerp1(lerp1(lerp1(gc[0][a], gc[1][a], tt[0]), lerp1(gc[2][a], gc[3][a], tt[0]), tt[1]),
-                       lerp1(lerp1(gc[4][a], gc[5][a], tt[0]), lerp1(gc[6][a], gc[7][a], tt[0]), tt[1]), tt[2]);
+    if (COLOR) tsdf_color_at(col, v, at, tt, rgb);
 }
 
 // COLOR: at a hit the colour volume is read at the base cells of the two bracketing samples; the march itself is the same code for all four kernels.
-// NORMALS: the gradient is read around the same two cells of a hit, after the march (the loop only notes k and s); three +0.0f without a hit.
-// A pointer that a form does not use (`col` and `rgb_out` without COLOR, `normals_out` without NORMALS) is null and never touched.
-// LABELS (without COLOR and NORMALS): the loop notes k and s as for NORMALS; after it, one voxel of `lab` is read at a hit -- in the
-// cell of sample k - 1 if s < 0.5f, else of sample k, formed again by tsdf_cell_index, the corner with offset bit t[a] >= 0.5f on axis a -- and its
-// instance id, or -1, goes to ins_out at the pixel the depth goes to.  `lab`, `min_count` and `ins_out` come last and are null / unused otherwise.
+// NORMALS: the gradient is read around the same two cells of a hit, after the march (the loop only notes k and s); three +0.0f without a hit.  A pointer
+// that a form does not use (`col` and `rgb_out` without COLOR, `normals_out` without NORMALS) is null and never touched.
+// LABELS (without COLOR and NORMALS): the loop notes k and s as for NORMALS; after it, one voxel of `lab` is read at a hit -- the corner
+// nearest to sample k - 1 if s < 0.5f, else to sample k -- and its instance id, or -1, goes to ins_out.  `lab`, `min_count` and `ins_out` come last.
 template <bool COLOR, bool NORMALS, bool LABELS>
 __global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const TsdfVol v, const TsdfCam c,
                                                                         float dz, int kmax, int tiles_x, float *__restrict__ out, uint8_t *__restrict__ rgb_out,
@@ -297,24 +264,20 @@ __global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const flo
     for (int k = k0; k <= k1; ++k) {
         float bf[3], tt[3];
         if (!tsdf_cell(v, c, dz, k, t0, dw, bf, tt)) { valid_prev = false; continue; }      // no address is formed for such a sample
-        const float2 *p = vol + ((int64_t)(int)bf[2] * v.ny + (int)bf[1]) * v.nx + (int)bf[0];
-        const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
-        const float2 c000 = p[0], c100 = p[1], c010 = p[sy], c110 = p[sy + 1], c001 = p[sz], c101 = p[sz + 1], c011 = p[sz + sy], c111 = p[sz + sy + 1];
-        if (!(c000.y > 0.0f && c100.y > 0.0f && c010.y > 0.0f && c110.y > 0.0f && c001.y > 0.0f && c101.y > 0.0f && c011.y > 0.0f && c111.y > 0.0f)) {
-            valid_prev = false;
-            continue;
-        }
-        // along x, then y, then z
-        const float f = lerp1(lerp1(lerp1(c000.x, c100.x, tt[0]), lerp1(c010.x, c110.x, tt[0]), tt[1]),
-                              lerp1(lerp1(c001.x, c101.x, tt[0]), lerp1(c011.x, c111.x, tt[0]), tt[1]), tt[2]);
+        int b[3];
+        float2 cn[8];
+        float F[8];
+        tsdf_corners(vol, v, tsdf_cell_at(v, bf, b), cn);
+        if (!tsdf_seen8(cn, F)) { valid_prev = false; continue; }
+        const float f = trilerp(F, tt);
         if (valid_prev) {
             if (f_prev > 0.0f && f <= 0.0f) {
                 const float s = f_prev / (f_prev - f);
                 depth = (c.near + (float)(k - 1) * dz) + dz * s;
                 if (COLOR && !NORMALS) {                     // sample k - 1 was valid too (valid_prev), so all sixteen corners are observed
                     float ca[3], cb[3];
-                    tsdf_cell_color(col, v, c, dz, k - 1, t0, dw, ca);
-                    tsdf_cell_color(col, v, c, dz, k, t0, dw, cb);
+                    tsdf_cell_read<true, false>(vol, col, v, c, dz, k - 1, t0, dw, ca, nullptr);
+                    tsdf_cell_read<true, false>(vol, col, v, c, dz, k, t0, dw, cb, nullptr);
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) rgbf[ch] = lerp1(ca[ch], cb[ch], s);
                 }
@@ -333,8 +296,7 @@ __global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const flo
         for (int e = 0; e < 2; ++e) {                        // one sample at a time: this runs once a pixel, and the kernel keeps the march's occupancy
 #pragma unroll
             for (int a = 0; a < 3; ++a) { ga[a] = gb[a]; ca[a] = cb[a]; }
-            if (COLOR) tsdf_cell_color(col, v, c, dz, hit_k - 1 + e, t0, dw, cb);      // the same operations on the same values as the colour-only form's
-            tsdf_cell_gradient(vol, v, c, dz, hit_k - 1 + e, t0, dw, gb);
+            tsdf_cell_read<COLOR, true>(vol, col, v, c, dz, hit_k - 1 + e, t0, dw, cb, gb);      // the colour: the same operations on the same values as the colour-only form's
         }
 #pragma unroll
         for (int a = 0; a < 3; ++a) g[a] = lerp1(ga[a], gb[a], hit_s);
@@ -360,10 +322,8 @@ __global__ void __launch_bounds__(TSDF_TILE *TSDF_TILE) k_tsdf_raycast(const flo
         if (hit_k >= 0) {                                    // both samples passed tsdf_cell in the march: base cell + {0, 1} is a voxel on every axis
             float tt[3];
             int bc[3];
-            tsdf_cell_index(v, c, dz, hit_s < 0.5f ? hit_k - 1 : hit_k, t0, dw, bc, tt);
-            const int i = bc[0] + (tt[0] >= 0.5f ? 1 : 0), j = bc[1] + (tt[1] >= 0.5f ? 1 : 0), kk = bc[2] + (tt[2] >= 0.5f ? 1 : 0);      // within [0, n - 1]
-            const int2 e = lab[((int64_t)kk * v.ny + j) * v.nx + i];
-            if (e.x > 0 && e.y >= min_count) label = e.x - 1;
+            const int64_t at = tsdf_cell_index(v, c, dz, hit_s < 0.5f ? hit_k - 1 : hit_k, t0, dw, bc, tt);
+            label = tsdf_label_id(lab[at + tsdf_corner(v, tsdf_nearest(tt))], min_count);
         }
         ins_out[(int64_t)pv * c.w + pu] = label;
     }
@@ -397,18 +357,16 @@ __global__ void __launch_bounds__(256) k_tsdf_labels_remap(int2 *__restrict__ la
     }
 }
 
-// ---- the volume read at arbitrary points.  One thread a point, grid-stride.  The blends are stated HERE a second time, on a given
-// (b, t) instead of a ray's sample k: tsdf_cell, tsdf_cell_color and tsdf_cell_gradient form their position from the ray inside themselves, and the
-// ray-cast kernels keep their instruction streams only if those stay as they are.  The expressions are the same ones, in the same order.
-// The vote of eight (L, C) corners (label_mode 1, LABELS == 2): a corner is eligible iff L > 0 && C >= min_count; every eligible corner's label gets the int64 sum
-// of the counts of the eligible corners that hold it; the largest sum wins; among tied labels the one the nearest corner `near` holds if that corner
-// is eligible and its label is one of them, else the smallest L.  Returns L - 1, or -1 when no corner is eligible.
+// ---- the volume read at arbitrary points.  One thread a point, grid-stride; a point that is a ray's sample gets that sample's bits
+// because both call tsdf_cell.h.  The vote of eight (L, C) corners (label_mode 1, LABELS == 2): a corner is eligible iff the label rule gives it an id; every
+// eligible corner's label gets the int64 sum of the counts of the eligible corners that hold it; the largest sum wins; among tied labels the one the nearest
+// corner `near` holds if that corner is eligible and its label is one of them, else the smallest L.  Returns L - 1, or -1 when no corner is eligible.
 __device__ __forceinline__ int tsdf_vote8(const int2 e[8], int near, int min_count) {
     int64_t best = 0, near_sum = 0;                        // an eligible corner's own sum is >= its C >= min_count >= 1
     int L = 0, near_L = 0;
 #pragma unroll
     for (int a = 0; a < 8; ++a) {
-        const bool ok = e[a].x > 0 && e[a].y >= min_count;
+        const bool ok = e[a].x > 0 && e[a].y >= min_count;   // (tsdf_label_id's rule, stated here for all eight at once: through it the vote forms lose a wave of occupancy)
         int64_t sum = 0;
 #pragma unroll
         for (int b = 0; b < 8; ++b) sum += ok && e[b].x == e[a].x && e[b].y >= min_count ? (int64_t)e[b].y : 0;
@@ -420,63 +378,40 @@ __device__ __forceinline__ int tsdf_vote8(const int2 e[8], int near, int min_cou
 }
 
 // A pointer that a form does not use (`normals_out` without NORMALS, `col` and `rgb_out` without COLOR, `lab` and `ins_out` without LABELS) is never
-// touched.  Every address into the three volumes is base + {0, 1} per axis of a cell that passed the INSIDE test -- bf[a] in [0, n[a] - 2], tested on
-// the floats before any of them becomes an index -- except the gradient's neighbours, which tsdf_gradient tests against [0, n) itself.  Every output
-// is written at index i < n only.
+// touched; every output is written at index i < n only.
 // LABELS: 0 none, 1 the nearest corner's label (one 8-byte load), 2 the vote (eight): a form of its own each, since the vote's sums cost registers.
 template <bool NORMALS, bool COLOR, int LABELS>
 __global__ void __launch_bounds__(256) k_tsdf_sample_points(const float2 *__restrict__ vol, const uint2 *__restrict__ col, const int2 *__restrict__ lab, const TsdfVol v,
                                                             const float *__restrict__ points, int64_t n, int min_count, float *__restrict__ f_out,
                                                             float *__restrict__ normals_out, uint8_t *__restrict__ rgb_out, int32_t *__restrict__ ins_out) {
-    const int64_t sy = v.nx, sz = (int64_t)v.nx * v.ny;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const float pt[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
         float bf[3], tt[3];
-        const bool inside = tsdf_point_cell(v, pt, bf, tt);      // (tsdf_desc.h: NaN and the infinities fail)
+        const bool inside = tsdf_point_cell(v, pt, bf, tt);      // (NaN and the infinities fail)
         float f = 2.0f, nrm[3] = {0.0f, 0.0f, 0.0f}, rgbf[3] = {0.0f, 0.0f, 0.0f};
         int label = -1;
         if (inside) {                                      // only now does a float become an index
-            const int b[3] = {(int)bf[0], (int)bf[1], (int)bf[2]};
-            const int64_t at = ((int64_t)b[2] * v.ny + b[1]) * v.nx + b[0];
-            const float2 *p = vol + at;
-            const float2 c000 = p[0], c100 = p[1], c010 = p[sy], c110 = p[sy + 1], c001 = p[sz], c101 = p[sz + 1], c011 = p[sz + sy], c111 = p[sz + sy + 1];
-            // the blend is formed whether or not the cell is seen and then selected, so that a corner's F travels with its W in one load, not in a
-            // second round of loads behind the test (an unobserved corner's F is only arithmetic on whatever bits it holds)
-            const float blend = lerp1(lerp1(lerp1(c000.x, c100.x, tt[0]), lerp1(c010.x, c110.x, tt[0]), tt[1]),
-                                      lerp1(lerp1(c001.x, c101.x, tt[0]), lerp1(c011.x, c111.x, tt[0]), tt[1]), tt[2]);
-            const bool seen = (c000.y > 0.0f) & (c100.y > 0.0f) & (c010.y > 0.0f) & (c110.y > 0.0f) & (c001.y > 0.0f) & (c101.y > 0.0f) & (c011.y > 0.0f) & (c111.y > 0.0f);
-            f = seen ? blend : 2.0f;
+            int b[3];
+            const int64_t at = tsdf_cell_at(v, bf, b);
+            float2 cn[8];
+            float F[8];
+            tsdf_corners(vol, v, at, cn);
+            tsdf_pin8(cn);                                 // a corner's F travels with its W in one load: four 16-byte loads in every form
+            const bool seen = tsdf_seen8(cn, F);
+            f = seen ? trilerp(F, tt) : 2.0f;
             if (seen) {
                 if (NORMALS) {
-                    const float Fc[8] = {c000.x, c100.x, c010.x, c110.x, c001.x, c101.x, c011.x, c111.x};
-                    float gc[8][3], g[3];                  // corner x + 2 y + 4 z
-#pragma unroll
-                    for (int cn = 0; cn < 8; ++cn) tsdf_gradient(vol, v, b[0] + (cn & 1), b[1] + (cn >> 1 & 1), b[2] + (cn >> 2), Fc[cn], TsdfSeen{}, gc[cn]);
-#pragma unroll
-                    for (int a = 0; a < 3; ++a)
-                        g[a] = lerp1(lerp1(lerp1(gc[0][a], gc[1][a], tt[0]), lerp1(gc[2][a], gc[3][a], tt[0]), tt[1]),
-                                     lerp1(lerp1(gc[4][a], gc[5][a], tt[0]), lerp1(gc[6][a], gc[7][a], tt[0]), tt[1]), tt[2]);
+                    float g[3];
+                    tsdf_gradient_at(vol, v, b, tt, F, g);
                     tsdf_unit(g, nrm);
                 }
-                if (COLOR) {
-                    const uint2 *q = col + at;
-                    const uint2 q000 = q[0], q100 = q[1], q010 = q[sy], q110 = q[sy + 1], q001 = q[sz], q101 = q[sz + 1], q011 = q[sz + sy], q111 = q[sz + sy + 1];
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch)
-                        rgbf[ch] = lerp1(lerp1(lerp1(color_channel(q000, ch), color_channel(q100, ch), tt[0]), lerp1(color_channel(q010, ch), color_channel(q110, ch), tt[0]), tt[1]),
-                                         lerp1(lerp1(color_channel(q001, ch), color_channel(q101, ch), tt[0]), lerp1(color_channel(q011, ch), color_channel(q111, ch), tt[0]), tt[1]),
-                                         tt[2]);
-                }
-                if (LABELS) {
-                    const int ni = tt[0] >= 0.5f ? 1 : 0, nj = tt[1] >= 0.5f ? 1 : 0, nk = tt[2] >= 0.5f ? 1 : 0;      // the nearest corner
-                    const int2 *l = lab + at;
-                    if (LABELS == 2) {
-                        const int2 e[8] = {l[0], l[1], l[sy], l[sy + 1], l[sz], l[sz + 1], l[sz + sy], l[sz + sy + 1]};
-                        label = tsdf_vote8(e, ni + 2 * nj + 4 * nk, min_count);
-                    } else {
-                        const int2 e = l[nk * sz + nj * sy + ni];
-                        if (e.x > 0 && e.y >= min_count) label = e.x - 1;
-                    }
+                if (COLOR) tsdf_color_at(col, v, at, tt, rgbf);
+                if (LABELS == 2) {
+                    int2 e[8];
+                    tsdf_corners(lab, v, at, e);
+                    label = tsdf_vote8(e, tsdf_nearest(tt), min_count);
+                } else if (LABELS) {
+                    label = tsdf_label_id(lab[at + tsdf_corner(v, tsdf_nearest(tt))], min_count);
                 }
             }
         }

@@ -27,21 +27,4 @@ __device__ __forceinline__ float lerp1(float a, float b, float t) { return a + t
 __device__ __forceinline__ float color_channel(uint2 q, int ch) { return (float)(ch == 0 ? q.x & 0xffffu : ch == 1 ? q.x >> 16 : q.y & 0xffffu); }
 __device__ __forceinline__ uint8_t color_level(float c) { return (uint8_t)rintf(fminf(fmaxf(c / 256.0f, 0.0f), 255.0f)); }      // (fmaxf drops a NaN: 0)
 
-// The cell of a point p given in the volume's frame (DESIGN.md sections 23 and 25: ovo_tsdf_sample_points and ovo_icp_align_volume share this one statement):
-// g = (p - origin) / voxel, the base cell bf = floorf(g) as whole-numbered floats, the trilinear weights tt = g - bf.  Returns INSIDE: bf in [0, n - 2] on all
-// three axes, i.e. all eight corners are voxels (NaN and the infinities fail).  No float may become an index before this has returned true.
-__device__ __forceinline__ bool tsdf_point_cell(const TsdfVol &v, const float p[3], float bf[3], float tt[3]) {
-    const float org[3] = {v.ox, v.oy, v.oz};
-    const int n[3] = {v.nx, v.ny, v.nz};
-    bool inside = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float g = (p[a] - org[a]) / v.voxel;
-        bf[a] = floorf(g);
-        tt[a] = g - bf[a];
-        inside &= (bf[a] >= 0.0f) & (bf[a] <= (float)(n[a] - 2));
-    }
-    return inside;
-}
-
 static inline TsdfVol tsdf_vol(const ovo_tsdf_volume_t &d) { return TsdfVol{d.nx, d.ny, d.nz, d.voxel, d.origin[0], d.origin[1], d.origin[2], d.trunc, d.max_weight}; }

@@ -1,7 +1,7 @@
 """Digests of the fused TSDF model's outputs: `python tools/gen_tsdf_digests.py` on the GPU.
 
-Runs every case of tests/test_gpu_tsdf_bits.py (integrate plain and with colour, the four ray-cast forms, the mesh with colours and normals; the cases of
-the other TSDF tests) with the library as it stands and writes, per case, the sha256 of every output array and the mesh's (V, T) to
+Runs every case of tests/test_gpu_tsdf_bits.py (integrate plain and with colour, the four ray-cast forms, the mesh with colours and normals, the label
+vote, ray cast and mesh, the twelve sampler forms, the alignment to the volume; the cases of the other TSDF tests) with the library as it stands and writes, per case, the sha256 of every output array and the mesh's (V, T) to
 tests/golden/tsdf_digests.json.  Run it BEFORE a change that must not move the model's results, commit the file, then make the change: the test compares
 with the file.  Regenerate it only in a pull request that MEANS to move results (another weight, another clip, another blend order), and say so there; a
 refactor never does.  Only digests and counts go to disk.
