@@ -134,7 +134,9 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
                 for (int ks = 1; ks < 3; ++ks) s2 += (v[tt][ks][0].lo + v[tt][ks][0].hi) + (v[tt][ks][1].lo + v[tt][ks][1].hi);
                 s2 += ((v[tt][3][0].lo + v[tt][3][0].hi) + (v[tt][3][1].lo + v[tt][3][1].hi)) * real;
-                const float mean = quad_sum(s2.x + s2.y) * (1.0f / C);
+                // (a true division: the product with the rounded 1 / 112 put the mean of a row of equal values one f32 step off the values -- at 3e4
+                // that step squared, 3.8e-6, is a variance beside eps = 1e-6 and LayerNorm gave -0.89 gamma + beta for beta)
+                const float mean = quad_sum(s2.x + s2.y) / (float)C;
                 f32x2 q2 = {0.f, 0.f};
 #pragma unroll
                 for (int ks = 0; ks < KS; ++ks) {
@@ -298,7 +300,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2,
             f32x2 s2 = {0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KS2; ++ks) s2 += (v[ks][0].lo + v[ks][0].hi) + (v[ks][1].lo + v[ks][1].hi);
-            const float mean = quad_sum(s2.x + s2.y) * (1.0f / C2);
+            const float mean = quad_sum(s2.x + s2.y) / (float)C2;    // (a true division, as in k_win_attn112)
             f32x2 q2 = {0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < KS2; ++ks)
